@@ -8,13 +8,32 @@ Adam}.  Workload at --gpus 1 is the configuration the metric is quoted on (num_e
 obs 64, act 6, E=4, 4 minibatches, 2x64 tanh MLP); with N GPUs every rank keeps --envs-per-gpu
 envs (weak scaling, env-sharded, one gradient all-reduce per optimizer step).
 
-    python bench.py [--gpus N --steps K --warmup W]        (N > 1: spawns one child per GPU itself, before any GPU call)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                           (N > 1: spawns one child per GPU itself, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-The first (untimed) step is also the parity gate: at N=1 its advantages / returns / permutations / 16 x 9 loss scalars /
-final weights are compared with the oracle's reference-faithful CPU update of the same tensors (the update the
-cpu_baseline leg computes anyway) and the line carries "parity_checked".
+A plain run sets up, runs the untimed first step and W warm-up steps, times exactly K steps, writes the last timed
+step's outputs if --dump-outputs is given, and prints the JSON line ("value", "ms_per_step", ...).  Everything else
+runs only with --full:
+
+  * the parity gate: the first (untimed) step's advantages / returns / permutations / 16 x 9 loss scalars / final weights
+    against the oracle's reference-faithful CPU update of the same tensors (the update the cpu_baseline leg computes
+    anyway); the line then carries "parity_checked" true
+  * the CPU baseline ("cpu_baseline") and the roofline ("roofline": stand-alone probe launches of the dominant kernel
+    inside the timed region, side-stream events, the plain-fp32 K7 build timed beside the default one)
+  * BASELINE config 4's 512-envs/GPU shard ("config4_shard") and, at N > 1, the other gradient exchange ("other_exchange")
+  * robot workloads: the small-sample parity gate / CPU baseline and the torch.profiler kernel table behind "roofline"
+
+--dump-outputs DIR writes what the last timed step computed (returns, advantages, loss scalars, gradient norms, the
+policy's weights after the update) as DIR/<name>.npy in float32; the inputs are fixed by seeds, so two builds run with
+the same arguments can be compared output for output.  Every warm-up and timed step restarts from the initial weights
+and zero Adam moments (see run_workload), so the last step computes the same update of the same inputs in every run: two
+runs agree to the rounding of one update (K7's counter-dealt tiles fix no summation order, tests/test_determinism.py):
+<= 6e-8 in weights and loss scalars, advantages / returns bit-identical, at --steps 20 --warmup 5.  The robot workloads
+restart the same way, but the library convolutions they keep sum in a launch-dependent order and Adam turns that into
++-lr steps within the update (tests/test_robot_gpu.py): their outputs agree to that drift bound (~4e-3), not to rounding;
+deterministic library solvers would make one robot5 update 8x slower (3.13 s against 0.39 s).
 """
 from __future__ import annotations
 
@@ -66,6 +85,10 @@ def parse():
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the first (untimed) step")
     ap.add_argument("--force-dp", action="store_true", help="one rank, but the multi-GPU launch path: K7 grad -> RCCL "
                     "all-reduce (group of one) -> apply; rehearses the captured collective on a one-GPU box")
+    ap.add_argument("--full", action="store_true", help="also run the parity gate, CPU baseline, roofline probes, the config-4 "
+                    "shard and (N > 1) the other gradient exchange; a plain run only times the workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy "
+                    "(float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 100 if args.workload == "mlp" else 10
@@ -130,6 +153,30 @@ def usable_cores(cap=16):
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_ARRAY_MAX_ELEMS = 4 << 20       # 16 MB of float32 per array
+DUMP_TOTAL_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of ``arrays`` (name -> tensor / ndarray) as path/<name>.npy in float32, smallest first.
+    An array above DUMP_ARRAY_MAX_ELEMS elements, or above what is left of DUMP_TOTAL_MAX_BYTES, is written as a fixed
+    sample of its flattened elements instead: sorted positions drawn with seed 0, so the same for every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: (t.detach().float().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float32)
+            for k, t in arrays.items()}
+    total, sampled = 0, []
+    for name in sorted(host, key=lambda k: host[k].size):
+        a = host[name]
+        cap = min(DUMP_ARRAY_MAX_ELEMS, (DUMP_TOTAL_MAX_BYTES - total) // 4)
+        if a.size > cap:
+            pos = np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[pos]
+            sampled.append(name)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        total += a.nbytes
+    log(f"wrote {len(host)} output arrays ({total / 1e6:.1f} MB) to {path}" + (f"; sampled: {sampled}" if sampled else ""))
 
 
 def c_twins(args, data):
@@ -367,10 +414,22 @@ def run_workload(args, rank, world, dev, envs_per_gpu, steps, warmup, with_probe
     step_no = [0]
     mlp_events = []
     every = 5 if steps < 50 else 10          # the stand-alone probe launch: every 5th step of a short run, every 10th otherwise
+    last = {}                                # what the latest step handed back (--dump-outputs)
+    # Every warm-up and timed step restarts from the same optimizer state: the initial weights and zero Adam moments (the
+    # device step counter and the shuffle generator run on; both are exact).  K7 hands row tiles to workgroups through a
+    # counter, so one update's gradients differ from run to run in their last bits; chained over the steps, Adam would amplify
+    # that into visibly different weights.  Restarted, each step is the same update of the same inputs -- the same work
+    # as a chained one -- and what it computes is reproducible to one update's rounding.
+    assert agent._fused_adam, "bench.py restarts the flat Adam state of the trainer"
+    param0 = agent.bucket.flat_param.detach().clone()
 
     def one_step():
+        agent.bucket.flat_param.copy_(param0)
+        agent._adam_m.zero_()
+        agent._adam_v.zero_()
         returns, advantages = agent.advantages(next_obs, next_done)
-        agent.update(returns, advantages)
+        last["n_steps"] = agent.update(returns, advantages)
+        last["returns"], last["advantages"] = returns, advantages
         step_no[0] += 1
         if with_probe and probe.on and not args.no_probe and step_no[0] % every == 1:
             # The update replays as a hipGraph, whose kernels cannot carry readable events: every `every`-th
@@ -383,10 +442,10 @@ def run_workload(args, rank, world, dev, envs_per_gpu, steps, warmup, with_probe
             else:
                 agent.probe_gather(probe)
 
-    log(f"rank {rank}/{world}: {envs_per_gpu} envs/GPU: setup done; parity step, then {warmup} warm-up steps")
-    # step 0 (untimed, eager): the update the oracle's first CPU update is compared with
+    log(f"rank {rank}/{world}: {envs_per_gpu} envs/GPU: setup done; first (untimed) step, then {warmup} warm-up steps")
+    # step 0 (untimed, eager): with --full, the update the oracle's first CPU update is compared with
     dp = world > 1 or args.force_dp
-    if dp:
+    if dp and args.full:
         agent.first_grad_probe = []
     if getattr(agent, "_p2p", None) is not None:
         D.barrier()                      # the one-shot exchange polls its peers against a wall-clock bound: start the first update together
@@ -405,7 +464,7 @@ def run_workload(args, rank, world, dev, envs_per_gpu, steps, warmup, with_probe
     first_grad = agent.first_grad_probe[0].cpu().numpy() if (dp and agent.first_grad_probe) else None
     agent.first_grad_probe = None
     gpu_first = None
-    if rank == 0:
+    if rank == 0 and args.full:
         gpu_first = dict(adv=advantages.cpu().numpy(), ret=returns.cpu().numpy(), perms=agent._last_perms.cpu().numpy(),
                          scalars=agent._scalars[:n0].cpu().numpy().astype(np.float64), minibatch=agent.minibatch_size,
                          wide=bool((agent._mlp is not None and agent._mlp.get("wide")) or
@@ -417,7 +476,7 @@ def run_workload(args, rank, world, dev, envs_per_gpu, steps, warmup, with_probe
     log(f"{envs_per_gpu} envs/GPU: warm-up done, timing {steps} steps")
     probe.on = True
     side = []
-    agent._perm_events = [] if agent._perm_stream is not None else None
+    agent._perm_events = [] if (args.full and agent._perm_stream is not None) else None
     D.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -445,7 +504,7 @@ def run_workload(args, rank, world, dev, envs_per_gpu, steps, warmup, with_probe
     sc = agent._scalars.cpu().numpy()
     assert np.isfinite(sc).all(), "non-finite loss scalars in the timed region"
     return dict(agent=agent, hp=hp, N=N, dt=dt, data=data, init_sd=init_sd, gpu_first=gpu_first, probe=probe,
-                mlp_events=mlp_events, side=side, perm_events=perm_events, every=every)
+                mlp_events=mlp_events, side=side, perm_events=perm_events, every=every, last=last)
 
 
 def robot_small_sample(args, C, S):
@@ -523,11 +582,18 @@ def main_robot(args, json_fd):
     cfg = 3 if args.workload == "robot3" else 5
     C, S = (1, 128) if cfg == 3 else (3, 84)
     base = parity = None
-    if args.cpu_baseline_updates > 0 and not args.no_parity:
+    if args.full and args.cpu_baseline_updates > 0 and not args.no_parity:
         base, parity = robot_small_sample(args, C, S)
         log(f"small-sample parity: {parity}")
+
+    def dump(agent, ret, adv):
+        n = len(agent._last_scalars)
+        outs = {"returns": ret, "advantages": adv, "loss_scalars": agent._last_scalars, "grad_norms": agent._norms[:n]}
+        outs.update({f"policy.{k}": v for k, v in agent.policy.state_dict().items()})
+        dump_outputs(args.dump_outputs, outs)
+
     res = BR.run(cfg, epochs=args.epochs, minibatches=args.minibatches, updates=args.steps, warmup=max(1, args.warmup),
-                 kernel_table=True)
+                 kernel_table=args.full, on_timed=dump if args.dump_outputs else None, restart=True)
     res.pop("_agent", None)
     kt = res.get("kernel_table") or {}
     N, T = res["N"], res["T"]
@@ -549,6 +615,8 @@ def main_robot(args, json_fd):
                        "summed device time of every convolution kernel in one more steady-state update under torch.profiler in this "
                        "process; priced at the fp32 MFMA peak the same FLOPs would need (K11 / K12 issue six bf16 products per fp32 product: "
                        "their own pipe's ceiling is 2 500 / 6 = 417 TFLOP/s; Winograd does fewer multiplies than it is credited)"}
+    if not args.full:
+        roofline = None              # (the kernel table it is formed from is one more, profiled update: --full)
     out = {"metric": "env-steps/sec through GAE+PPO-update at num_envs=4096,T=128; 1/2/4/8 GPU",
            "value": N * T / (ms * 1e-3), "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": max(1, args.warmup),
            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -556,7 +624,9 @@ def main_robot(args, json_fd):
                                   + ", plain-CNN robot_actor_critic, NOT the headline configuration",
                       "policy": res["policy"], "minibatch_step": "K3 gather + K10 first block + K11 / K12 hidden convolutions (MIOpen: the 16 -> 32 block's gradients, the 1x1 tail) + K9 block tails + K5 loss + K6b"},
            "roofline": roofline, "cpu_baseline": base, "parity_checked": bool(parity["ok"]) if parity else False,
-           "parity": parity if parity else "not run (--cpu-baseline-updates 0 / --no-parity)", "graph_fallback": None}
+           "parity": parity if parity else ("not run (--cpu-baseline-updates 0 / --no-parity)" if args.full
+                                            else "not run (plain run: --full runs it)"),
+           "graph_fallback": None, "full": args.full}
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(out) + "\n").encode())
     if parity is not None and not parity["ok"]:
@@ -607,18 +677,25 @@ def main():
         local_rank = 0
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    run = run_workload(args, rank, world, dev, args.envs_per_gpu, args.steps, args.warmup, True)
-    # BASELINE config 4 / SURVEY 8e define the scaling curve at 512 envs per GPU: the same step at that shard size, in this
-    # same process (every N, so the driver can form the ratio from its N = 1 line)
+    run = run_workload(args, rank, world, dev, args.envs_per_gpu, args.steps, args.warmup, args.full)
+    if args.dump_outputs and rank == 0:
+        ag, last = run["agent"], run["last"]
+        outs = {"returns": last["returns"], "advantages": last["advantages"],
+                "loss_scalars": ag._scalars[:last["n_steps"]], "grad_norms": ag._norms[:last["n_steps"]]}
+        outs.update({f"policy.{k}": v for k, v in ag.policy.state_dict().items()})
+        dump_outputs(args.dump_outputs, outs)
+    # --full: BASELINE config 4 / SURVEY 8e define the scaling curve at 512 envs per GPU: the same step at that shard size, in
+    # this same process (every N, so the driver can form the ratio from its N = 1 line)
     shard = None
-    if args.shard_envs_per_gpu > 0 and args.shard_envs_per_gpu != args.envs_per_gpu:
+    if args.full and args.shard_envs_per_gpu > 0 and args.shard_envs_per_gpu != args.envs_per_gpu:
         shard = run_workload(args, rank, world, dev, args.shard_envs_per_gpu, args.steps, args.warmup, False)
     # One process per GPU: the same two workloads once more through the OTHER gradient exchange (RCCL's all-reduce <-> the one-shot
     # exchange over HIP-IPC peer memory), in this same process -- so that a single multi-GPU run of the default command says what
     # either costs.  `value` stays the primary arm's; this is the `other_exchange` object.  Every rank takes the same path (a
     # set-up failure is agreed on across ranks before anybody raises, dist.make_p2p_exchange).
     other = None
-    if (world > 1 or args.force_dp) and not args.one_exchange and args.num_layers == 2 and args.hidden_dim == 64 and not args.no_fused_mlp:
+    if (args.full and (world > 1 or args.force_dp) and not args.one_exchange and args.num_layers == 2 and args.hidden_dim == 64
+            and not args.no_fused_mlp):
         cur = D.allreduce_choice()
         alt = "p2p" if cur == "rccl" else "rccl"
         os.environ["AURPPO_DP_ALLREDUCE"] = alt
@@ -828,14 +905,16 @@ def main():
            "graph_fallback": (agent.graph_fallback[:200] if agent.graph_fallback else None),
            "other_exchange": other}
     parity = None
-    if world == 1 and not args.force_dp and args.cpu_baseline_updates > 0:
+    out["full"] = args.full
+    if args.full and world == 1 and not args.force_dp and args.cpu_baseline_updates > 0:
         out["cpu_baseline"], parity = cpu_baseline(args, run["data"], run["init_sd"], args.cpu_baseline_updates, run["gpu_first"])
     else:
         out["cpu_baseline"] = None
-        if (world > 1 or args.force_dp) and not args.no_parity:
+        if args.full and (world > 1 or args.force_dp) and not args.no_parity:
             parity = check_parity_sharded(args, run["hp"], N, world, run["init_sd"], run["gpu_first"], run["data"]["log_probs"])
     out["parity_checked"] = bool(parity["ok"]) if parity is not None else False
-    out["parity"] = parity if parity is not None else "not run (--cpu-baseline-updates 0 / --no-parity)"
+    out["parity"] = parity if parity is not None else (
+        "not run (--cpu-baseline-updates 0 / --no-parity)" if args.full else "not run (plain run: --full runs it)")
     shard_ok = True
     if shard is not None:
         sa, sN = shard["agent"], shard["N"]

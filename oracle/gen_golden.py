@@ -30,6 +30,36 @@ REF = os.environ.get("AURPPO_REFERENCE", "/root/reference")
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
+FIXTURE_MAX_BYTES = 1 << 20          # the repository's limit for one committed file
+PART_RAW_BYTES = 800_000             # raw array bytes per part: deflate gains little on random floats, headers add the rest
+
+
+def save_fixture(name, out):
+    """np.savez_compressed(tests/golden/<name>, **out); a fixture above FIXTURE_MAX_BYTES is stored instead as
+    <stem>.part0.npz, <stem>.part1.npz, ... (same keys, in order; tests/util.py::load merges them back)."""
+    stem = name[:-len(".npz")]
+    for f in os.listdir(OUT):
+        if f == name or (f.startswith(stem + ".part") and f.endswith(".npz")):
+            os.remove(os.path.join(OUT, f))
+    np.savez_compressed(os.path.join(OUT, name), **out)
+    if os.path.getsize(os.path.join(OUT, name)) <= FIXTURE_MAX_BYTES:
+        return
+    os.remove(os.path.join(OUT, name))
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        nb = np.asarray(v).nbytes
+        if cur and size + nb > PART_RAW_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += nb
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        path = os.path.join(OUT, f"{stem}.part{i}.npz")
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) <= FIXTURE_MAX_BYTES, (path, os.path.getsize(path))
+
+
 # ----------------------------------------------------------------------------- shims
 class _Space:
     def __init__(self, shape, n=None):
@@ -247,7 +277,7 @@ def gen_gae(ref_ppo, robot_gae):
                     out[f"{name}/adv_skip"] = adv_s.numpy().copy()
                     out[f"{name}/ret_skip"] = ret_s.numpy().copy()
     out["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "gae.npz"), **out)
+    save_fixture("gae.npz", out)
     print("gae.npz:", len(names), "cases")
 
 
@@ -272,7 +302,7 @@ def gen_shuffle():
             out[f"B{B}/tail"] = np.stack([p[-16:] for p in perms]).astype(np.int32)
             out[f"B{B}/sha"] = np.stack([np.frombuffer(hashlib.sha256(p.astype(np.int32).tobytes()).digest(),
                                                        dtype=np.uint8) for p in perms])
-    np.savez_compressed(os.path.join(OUT, "shuffle.npz"), **out)
+    save_fixture("shuffle.npz", out)
     print("shuffle.npz written")
 
 
@@ -392,7 +422,7 @@ def gen_loss(ref_ppo):
         out[name + "/scalars"] = np.array([sc["policy_loss"], sc["value_loss"], sc["entropy"], sc["old_approx_kl"],
                                            sc["approx_kl"], sc["clipfrac"]], dtype=np.float64)
     out["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "loss.npz"), **out)
+    save_fixture("loss.npz", out)
     print("loss.npz:", len(names), "cases")
 
 
@@ -468,7 +498,7 @@ def gen_trace(ref_ppo):
         out[f"{name}/scalar_tags"] = np.array(tags)
         out[f"{name}/scalars"] = np.array([[v for (t, v, s) in sc if t == tag] for tag in tags], dtype=np.float64).T
     out["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "trace.npz"), **out)
+    save_fixture("trace.npz", out)
     print("trace.npz:", names)
 
 
@@ -510,7 +540,7 @@ def gen_evaluate(ref_ac):
         for k, v in net2.state_dict().items():
             out[f"{name}/init/{k}"] = v.detach().numpy().copy()
     out["names"] = np.array(names)
-    np.savez_compressed(os.path.join(OUT, "evaluate.npz"), **out)
+    save_fixture("evaluate.npz", out)
     print("evaluate.npz:", names)
 
 
@@ -542,7 +572,7 @@ def gen_robot_eval():
     for k, v in (("state", state), ("obs", obs), ("act", act), ("plan", plan), ("actions", actions), ("unscaled", unscaled),
                  ("logp", logp), ("ent", ent), ("val", val), ("value_fn", v2), ("u_plan", u_plan), ("a_plan", a_plan)):
         out[k] = v.numpy().copy()
-    np.savez_compressed(os.path.join(OUT, "robot_eval.npz"), **out)
+    save_fixture("robot_eval.npz", out)
     print("robot_eval.npz written")
 
 

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (tests may import oracle/; the product may not)."""
+import glob
 import os
 
 import numpy as np
@@ -6,8 +7,29 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+class _Merged(dict):
+    """The arrays of a fixture stored as parts, with the ``files`` list of an NpzFile."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def load(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """tests/golden/<name>, or the union of its parts <stem>.part0.npz, <stem>.part1.npz, ... (oracle/gen_golden.py
+    splits a fixture that would exceed the repository's 1 MiB file limit)."""
+    path = os.path.join(GOLDEN, name)
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    stem = name[:-len(".npz")]
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(stem) + ".part*.npz")),
+                   key=lambda p: int(p[len(os.path.join(GOLDEN, stem)) + len(".part"):-len(".npz")]))
+    assert parts, f"no fixture {name} (nor parts of it) under {GOLDEN}"
+    out = _Merged()
+    for p in parts:
+        with np.load(p, allow_pickle=False) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 def gae_big_inputs(ci, T, N):

@@ -5,7 +5,7 @@ old=$1; new=$2; rounds=${3:-3}
 for r in $(seq $rounds); do
   for which in old new; do
     cp ${!which} aur_ppo_amd/libaurppo_hip.so
-    line=$(timeout -k 10 300 python bench.py --steps 40 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
+    line=$(timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
     python - "$which" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2]); r = d["roofline"]

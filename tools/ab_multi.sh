@@ -6,7 +6,7 @@ cp aur_ppo_amd/libaurppo_hip.so /tmp/ab_keep.so
 for r in $(seq $rounds); do
   for so in "$@"; do
     cp $so aur_ppo_amd/libaurppo_hip.so
-    line=$(timeout -k 10 300 python bench.py --steps 40 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
+    line=$(timeout -k 10 300 python bench.py --full --steps 40 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
     python - "$so" "$line" <<'PY'
 import json, sys
 try:

@@ -51,10 +51,12 @@ CONV_MARKS = ("miopen", "MIOpen", "winograd", "Winograd", "igemm", "Igemm", "con
 
 
 def run(config=3, envs=0, steps=0, epochs=4, minibatches=4, updates=2, warmup=1, channels_last=False, equivariant=False,
-        equiv_hidden=128, kernel_table=False, miopen_find=False, device=None):
+        equiv_hidden=128, kernel_table=False, miopen_find=False, device=None, on_timed=None, restart=False):
     """Time ``updates`` steady-state GAE + update passes of robot_ppo at the config's shape; returns a dict (see the keys at
     the end).  ``kernel_table``: one more update under torch.profiler -- per-kernel GPU time, from which the convolution
-    kernels' share and their aggregate FLOP rate are formed."""
+    kernels' share and their aggregate FLOP rate are formed.  ``on_timed(agent, returns, advantages)``: called right after the
+    timed updates with the last one's GAE outputs (bench.py --dump-outputs).  ``restart``: every update starts from the initial
+    weights and zero Adam moments (bench.py: the same update of the same inputs each time, reproducible run to run)."""
     from aur_ppo_amd.robot_ppo import robot_ppo
     from aur_ppo_amd.robot_run import build_parser, params_from_args
     start_heartbeat()
@@ -87,9 +89,16 @@ def run(config=3, envs=0, steps=0, epochs=4, minibatches=4, updates=2, warmup=1,
     note("rollout values filled (T forward passes at N rows: MIOpen picks/compiles its solvers on first use of a shape)")
     ns, no, nd = b.states[0].clone(), b.observations[0].clone(), torch.zeros(N, device="cuda")
     a.seed_all(1)
+    last = []
+    param0 = a.bucket.flat_param.detach().clone()
     def step():
+        if restart:
+            a.bucket.flat_param.copy_(param0)
+            a._adam_m.zero_()
+            a._adam_v.zero_()
         ret, adv = a.advantages(ns, no, nd, b, T)
         a.update(b.flatten(ret, adv), E, a.batch_size, a.minibatch_size, [])
+        last[:] = [ret, adv]
     for _ in range(max(1, warmup)):
         step()
     torch.cuda.synchronize()
@@ -99,6 +108,8 @@ def run(config=3, envs=0, steps=0, epochs=4, minibatches=4, updates=2, warmup=1,
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / updates
     note(f"timed: {dt * 1e3:.1f} ms per update")
+    if on_timed is not None:
+        on_timed(a, *last)
     flops = 3 * 2 * (equiv_flops(S, C + 1, equiv_hidden) if equivariant else conv_flops(S, C + 1)) * N * T * E
     out = {"policy": "C4-equivariant (build-defined)" if equivariant else "plain CNN",
            "workload": f"robot_ppo, config {config}: N={N} T={T} obs=({C},{S},{S}) E={E}, {minibatches} minibatches of {a.minibatch_size}",

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerates the round's committed evidence on the GPU box (outputs under gpurun_out/prof_final/; copy into profiles/rNN/):
-#   bench.json                          python bench.py (default flags: parity gate + cpu_baseline + both rooflines)
+#   bench.json                          python bench.py --full (parity gate + cpu_baseline + both rooflines)
 #   bench_under_rocprof.json + bench_kernel_stats.csv            the same workload under rocprofv3 --kernel-trace --stats, with
 #                                       --shard-envs-per-gpu 0: the 512-env shard bench.py measures second in the same process launches the
 #                                       same kernels at M = 16 384 and would be averaged into the same rows
@@ -30,13 +30,13 @@ export TMPDIR=/tmp
 prof() {  # prof <tag> <bench args...>
   local tag=$1; shift
   cd /tmp
-  run 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$tag -- python3 $R/bench.py --cpu-baseline-updates 0 "$@" > $O/${tag}_under_rocprof.json 2> $O/${tag}_rocprof.err
+  run 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$tag -- python3 $R/bench.py --full --cpu-baseline-updates 0 "$@" > $O/${tag}_under_rocprof.json 2> $O/${tag}_rocprof.err
   cp $(ls $O/stats_$tag/*/*kernel_stats.csv | head -1) $O/${tag}_kernel_stats.csv
   rm -rf $O/stats_$tag
   cd $R
 }
 if part 1; then
-run 600 python3 bench.py > $O/bench.json 2> $O/bench.err
+run 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.json; echo
 prof bench --shard-envs-per-gpu 0
 prof bench_shard --envs-per-gpu 512 --shard-envs-per-gpu 0
@@ -50,7 +50,7 @@ prof bench_wide_3x64 --hidden-dim 64 --num-layers 3 --steps 30
 prof bench_wide_2x128 --hidden-dim 128 --num-layers 2 --steps 30
 for shape in "128 3" "64 3" "128 2"; do
   set -- $shape
-  run 600 python3 $R/bench.py --hidden-dim $1 --num-layers $2 --steps 30 --cpu-baseline-updates 1 > $O/bench_wide_$2x$1.json 2> $O/bench_wide_$2x$1.err
+  run 600 python3 $R/bench.py --full --hidden-dim $1 --num-layers $2 --steps 30 --cpu-baseline-updates 1 > $O/bench_wide_$2x$1.json 2> $O/bench_wide_$2x$1.err
 done
 run 600 python3 $R/tools/bench_wide.py > $O/wide_bench.json 2> $O/wide_bench.err
 fi
@@ -95,8 +95,8 @@ run 300 python3 $R/tools/bench_wgrad.py --batch 4096 --size 84 --equiv > $O/wgra
 run 200 python3 $R/tools/bench_wgrad.py --linear > $O/wgrad_bench_linear.json 2> /dev/null
 run 900 bash tools/pmc_mfma.sh k12 k_conv3x3_wgrad 0 tools/bench_wgrad.py --batch 2048 > /dev/null 2>&1
 cp gpurun_out/k12_mfma_pmc.json $O/conv_wgrad_k12_mfma_pmc.json
-run 600 python3 $R/bench.py --workload robot3 --steps 5 --warmup 3 > $O/bench_robot3.json 2> $O/bench_robot3.err
-run 900 python3 $R/bench.py --workload robot5 > $O/bench_robot5.json 2> $O/bench_robot5.err
+run 600 python3 $R/bench.py --full --workload robot3 --steps 5 --warmup 3 > $O/bench_robot3.json 2> $O/bench_robot3.err
+run 900 python3 $R/bench.py --full --workload robot5 > $O/bench_robot5.json 2> $O/bench_robot5.err
 run 900 python3 $R/tools/bench_robot.py --config 5 --equivariant --updates 2 --kernel-table > $O/equiv5_k11_k12.json 2> $O/equiv5.err
 rm -f $O/.step.txt
 fi

@@ -3,8 +3,8 @@
 setting=$1; rounds=${2:-3}
 for r in $(seq $rounds); do
   for which in base with; do
-    if [ $which = with ]; then line=$(env $setting timeout -k 10 300 python bench.py --steps 60 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
-    else line=$(timeout -k 10 300 python bench.py --steps 60 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1); fi
+    if [ $which = with ]; then line=$(env $setting timeout -k 10 300 python bench.py --full --steps 60 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1)
+    else line=$(timeout -k 10 300 python bench.py --full --steps 60 --warmup 5 --cpu-baseline-updates 0 2>/dev/null | tail -1); fi
     python - "$which" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2]); r = d["roofline"]; ss = r["side_stream"]
