@@ -253,7 +253,7 @@ __device__ __forceinline__ void store_plain1(char* img, int rowb, int planeb, in
     *reinterpret_cast<unsigned short*>(img + 2 * planeb + o) = (unsigned short)p2;
 }
 
-// ---- weights as B operands streamed from global memory in operand order (k_mlp3_prep / k_adam_chain lay them out):
+// ---- weights as B operands streamed from global memory in operand order (wop3_prepare / k_adam_chain lay them out):
 // block (role wi = net * 2 + cb, matrix mt, k-step ks, plane p) = 64 lanes x 8 bf16; lane l, element j holds
 //   mt 0 (W1, forward):  W1[cb*32 + (l & 31)][16 ks + 8 (l >> 5) + j]      (zero beyond D)
 //   mt 1 (W2, forward):  W2[cb*32 + (l & 31)][16 ks + 8 (l >> 5) + j]
@@ -278,6 +278,28 @@ __device__ __host__ __forceinline__ int wop3_places(int net, int is_w2, int row,
         idx[1] = wop3_index(net * 2 + cb, 2, ks, 0, c + 32 * h, j);
     }
     return 2;
+}
+
+// The copies of both nets' W1 (offsets w1[net], rows of D) and W2 (w2[net], 64 x 64) built from the weights, destination-first so
+// that the padding (state columns >= D) is zero without a clearing pass: thread `first` of `step` takes elements first, first + step,
+// ...  (the workgroups of k_adv_stats_idx past its statistics ones)
+__device__ __forceinline__ void wop3_prepare(const float* __restrict__ params, const int (&w1)[2], const int (&w2)[2], int D,
+                                             unsigned short* __restrict__ wop3, int first, int step) {
+    for (int e = first; e < 4 * kWopMats * kWopKs * 64 * 8; e += step) {
+        const int j = e & 7, lane = (e >> 3) & 63, ks = (e >> 9) & 3, mt = (e >> 11) % kWopMats, wi = (e >> 11) / kWopMats;
+        const int net = wi >> 1, cb = wi & 1;
+        const int k = 16 * ks + 8 * (lane >> 5) + j, c = cb * 32 + (lane & 31);
+        float v;
+        if (mt == 0) v = k < D ? params[w1[net] + c * D + k] : 0.0f;          // W1[o = c][d = k]
+        else if (mt == 1) v = params[w2[net] + c * 64 + k];                     // W2[o = c][i = k]
+        else v = params[w2[net] + k * 64 + c];                                  // W2[o2 = k][i = c]
+        unsigned p0, p1, p2;
+        split3(v, 0.0f, p0, p1, p2);
+        const int at = wop3_index(wi, mt, ks, 0, lane, j);
+        wop3[at] = (unsigned short)p0;
+        wop3[at + kWopBlock] = (unsigned short)p1;
+        wop3[at + 2 * kWopBlock] = (unsigned short)p2;
+    }
 }
 
 }  // namespace bf3

@@ -24,25 +24,31 @@ using namespace aurppo_mlp;
 
 namespace {
 
-// Also lays out W1 of both nets in the B-operand order of k_mlp_step2's layer-1 MFMA chain (w1op != nullptr):
+// Also lays out W1 of both nets in the B-operand order of k_mlp_step2's layer-1 MFMA chain (w1op != nullptr, variant 2):
 // w1op[(w * 32 + m) * 64 + lane] = W1[net = w >> 1][(w & 1) * 32 + (lane & 31)][2m + (lane >> 5)], zero beyond D, so
-// that wave w reads its slice with 32 fully coalesced loads per tile instead of holding it in registers.
+// that wave w reads its slice with 32 fully coalesced loads per tile instead of holding it in registers.  The workgroups past
+// the first n_stat build k_mlp_step3's bf16-plane copies of W1 / W2 instead (variant 3; this was a launch of its own).
 __global__ __launch_bounds__(256) void k_adv_stats_idx(const float4* __restrict__ rec, int rec_stride,
                                                        const int32_t* __restrict__ idx,
                                                        int M, double (*__restrict__ stats)[2], const float* __restrict__ params,
-                                                       int w1_actor, int w1_critic, int D, float* __restrict__ w1op,
+                                                       MlpLayout L, int D, float* __restrict__ w1op,
+                                                       unsigned short* __restrict__ wop3, int n_stat,
                                                        unsigned* __restrict__ tile_counter) {
+    if ((int)blockIdx.x >= n_stat) {
+        bf3::wop3_prepare(params, L.w1, L.w2, D, wop3, (blockIdx.x - n_stat) * kThreads + threadIdx.x, (gridDim.x - n_stat) * kThreads);
+        return;
+    }
     __shared__ double sc[2][kThreads / kWave];
+    if (blockIdx.x == 0 && threadIdx.x < 2) tile_counter[threadIdx.x] = 0u;
     if (w1op) {
-        if (blockIdx.x == 0 && threadIdx.x < 2) tile_counter[threadIdx.x] = 0u;
-        for (int e = blockIdx.x * kThreads + threadIdx.x; e < 4 * 32 * 64; e += gridDim.x * kThreads) {
+        for (int e = blockIdx.x * kThreads + threadIdx.x; e < 4 * 32 * 64; e += n_stat * kThreads) {
             const int lane = e & 63, m = (e >> 6) & 31, w = e >> 11;
             const int row = (w & 1) * 32 + (lane & 31), k = 2 * m + (lane >> 5);
-            w1op[e] = k < D ? params[((w >> 1) ? w1_critic : w1_actor) + row * D + k] : 0.0f;
+            w1op[e] = k < D ? params[L.w1[w >> 1] + row * D + k] : 0.0f;
         }
     }
     double s = 0.0, q = 0.0;
-    adv_partial_sums(rec, rec_stride, idx, M, blockIdx.x * kThreads + threadIdx.x, gridDim.x * kThreads, s, q);
+    adv_partial_sums(rec, rec_stride, idx, M, blockIdx.x * kThreads + threadIdx.x, n_stat * kThreads, s, q);
     const double bs = block_sum<kThreads / kWave>(s, sc[0]);
     const double bq = block_sum<kThreads / kWave>(q, sc[1]);
     if (threadIdx.x == 0) {
@@ -313,6 +319,130 @@ __global__ __launch_bounds__(1024) void k_mlp_reduce(const float* __restrict__ s
     }
 }
 
+// K7's slab reduce (slabs of slab_stride floats, n_slabs <= kMaxGrid): k_mlp_reduce<1>'s sums, bit for bit, on 16-byte loads.
+// A workgroup still owns 64 parameters and 16 slab groups, but a thread now holds FOUR consecutive parameters of its group's
+// 16 rows (16 x 16 B in flight per lane, one wave-instruction = four 256-B row segments) where it held one of them in
+// 4-byte loads: k_mlp_reduce<1> moved the 17 MB of slabs at a third of what the chip streams.  Per parameter the tree is
+// unchanged -- rows b = grp (mod 16), ((x0 + x4) + x8) + x12 per quarter, (a0 + a1) + (a2 + a3), the 16 groups folded
+// 0 -> 15 through LDS by wave 0 with lane = p mod 64 -- and so are the clip's partial sums, the step advance and the
+// loss-scalar fold (one wave per quantity, two quantities for the first two waves).
+__global__ __launch_bounds__(256) void k_mlp_reduce_x4(const float* __restrict__ slabs, const double* __restrict__ loss_part,
+                                                       int n_slabs, int n_params, PpoHyper h, float* __restrict__ grads,
+                                                       float* __restrict__ out_scalars, double* __restrict__ sq_part,
+                                                       float* __restrict__ step_dev, unsigned* __restrict__ tile_counter,
+                                                       double beta1, double beta2, double* __restrict__ bc_out) {
+    __shared__ __attribute__((aligned(16))) float s_part[kRedGroups][64];
+    const int qi = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const int p0 = blockIdx.x * 64 + 4 * qi;
+    const int ns = slab_stride(n_params);
+    const bool stepper = step_dev && threadIdx.x == 0 && blockIdx.x == 0;
+    static_assert(kMaxGrid <= 16 * kRedGroups, "k_mlp_reduce_x4: 16 rows per thread cover the grid");
+    float4 x[16];
+    if (p0 + 3 < n_params) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int b = grp + j * kRedGroups;
+            x[j] = b < n_slabs ? *reinterpret_cast<const float4*>(slabs + (size_t)b * ns + p0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    } else {   // the bucket's last, partial quad (or none): parameters past n_params read as zero, the stride's padding is not read
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int b = grp + j * kRedGroups;
+            const float* r = slabs + (size_t)b * ns + p0;
+            const bool ok = b < n_slabs;
+            x[j] = make_float4(ok && p0 + 0 < n_params ? r[0] : 0.f, ok && p0 + 1 < n_params ? r[1] : 0.f,
+                               ok && p0 + 2 < n_params ? r[2] : 0.f, ok && p0 + 3 < n_params ? r[3] : 0.f);
+        }
+    }
+    // workgroup 0 also folds the loss partials: they are fetched here, behind the slab rows, so that its fold costs no memory
+    // round trip of its own after the gradient's (waves 0 and 1 hold quantities w and w + 4, waves 2 and 3 quantity w; what
+    // lies past n_slabs or names no quantity is fetched from a valid row and not added)
+    static_assert(kMaxGrid <= 4 * kWave, "k_mlp_reduce_x4: four partials per lane cover the grid");
+    const int lw = threadIdx.x >> 6, ll = threadIdx.x & 63;
+    double lq[2][4];
+    double adv_mean = 0.0, adv_std = 0.0;
+    const bool folder = blockIdx.x == 0 && threadIdx.x == 0;
+    if (blockIdx.x == 0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int q = lw + 4 * u < 6 ? lw + 4 * u : 0, b = ll + k * kWave < n_slabs ? ll + k * kWave : 0;
+                lq[u][k] = loss_part[(size_t)b * 8 + q];
+            }
+        adv_mean = loss_part[6];
+        adv_std = loss_part[7];
+    }
+    const float t_new = stepper ? *step_dev + 1.0f : 0.0f;      // the Adam step this minibatch is
+    if (stepper && bc_out) {
+        // Adam's bias corrections for the optimizer launch that follows, while the slab rows are on their way
+        bc_out[0] = 1.0 - pow(beta1, (double)t_new);
+        bc_out[1] = 1.0 - pow(beta2, (double)t_new);
+    }
+    const auto tree = [&](auto c) {
+        float a4[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a4[k] = ((c(x[k]) + c(x[k + 4])) + c(x[k + 8])) + c(x[k + 12]);
+        return (a4[0] + a4[1]) + (a4[2] + a4[3]);
+    };
+    float4 acc;
+    acc.x = tree([](const float4& v) { return v.x; });
+    acc.y = tree([](const float4& v) { return v.y; });
+    acc.z = tree([](const float4& v) { return v.z; });
+    acc.w = tree([](const float4& v) { return v.w; });
+    // (k_mlp_reduce<1> leaves 0 for a parameter past n_params; here such a parameter's rows read as zero: the same)
+    *reinterpret_cast<float4*>(&s_part[grp][4 * qi]) = acc;
+    __syncthreads();
+    if (threadIdx.x < 64) {   // wave 0
+        const int pi = threadIdx.x, p = blockIdx.x * 64 + pi;
+        float t = 0.0f;
+        if (p < n_params) {
+#pragma unroll
+            for (int g = 0; g < kRedGroups; ++g) t += s_part[g][pi];
+            grads[p] = t;
+        }
+        if (sq_part) {
+            const double q = wave_sum((double)t * (double)t);
+            if (pi == 0) sq_part[blockIdx.x] = q;
+        }
+        if (stepper) {
+            *step_dev = t_new;   // the Adam kernel (a later launch) reads the new step count
+            tile_counter[0] = 0u;
+            tile_counter[1] = 0u;
+        }
+    }
+    __shared__ double r[6];
+    if (blockIdx.x == 0) {
+        // k_mlp_reduce<1>'s order per quantity: lane l adds rows l, l + 64, ... from 0, then the shuffle reduce
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int q = lw + 4 * u;
+            if (q < 6) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (ll + k * kWave < n_slabs) s += lq[u][k];
+                s = wave_sum(s);
+                if (ll == 0) r[q] = s;
+            }
+        }
+    }
+    __syncthreads();
+    if (folder) {
+        const double M = (double)h.M;
+        const float pg = (float)(r[0] / M), vl = 0.5f * (float)(r[1] / M), ent = (float)(r[2] / M);
+        out_scalars[AURPPO_S_PG] = pg;
+        out_scalars[AURPPO_S_VL] = vl;
+        out_scalars[AURPPO_S_ENT] = ent;
+        out_scalars[AURPPO_S_OLD_KL] = (float)(r[3] / M);
+        out_scalars[AURPPO_S_KL] = (float)(r[4] / M);
+        out_scalars[AURPPO_S_CLIPFRAC] = (float)(r[5] / M);
+        out_scalars[AURPPO_S_LOSS] = (pg - h.ent_coef * ent) + vl * h.vf_coef;
+        out_scalars[AURPPO_S_ADV_MEAN] = (float)adv_mean;
+        out_scalars[AURPPO_S_ADV_STD] = (float)adv_std;
+    }
+}
+
 // Where an updated weight is also kept in MFMA-operand order for the next K7 launch (W1 in k_mlp_step2's fp32 B-operand order;
 // W1 / W2 as bf16 planes for k_mlp_step3).  Offsets past the bucket switch a copy off.
 struct OperandCopies {
@@ -389,6 +519,15 @@ __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, 
     }
 }
 
+// Workgroups of k_adam_chain that update the bucket: one parameter per thread up to 128 workgroups.  The clip preamble is the
+// same in every workgroup, and what a thread does per parameter -- Adam, the operand-copy refresh with its run-time division,
+// bf16 split and scattered stores -- is one dependent chain: four per thread on 17 workgroups took 8.5 us per K7 minibatch,
+// one per thread on 67 takes 6.4.  The result does not depend on it (the update is per element).
+int adam_update_blocks(int n) {
+    const int nb = (n + kThreads - 1) / kThreads;
+    return nb < 128 ? nb : 128;
+}
+
 // Chained minibatch step, third launch: global-norm clip + Adam over the bucket (K6b's arithmetic); the W1
 // elements it has just updated are dropped into the operand-order copy the next K7 launch streams; and the
 // workgroups past `nb_upd` form the next minibatch's advantage partial sums -- so nothing is left to prepare
@@ -405,8 +544,8 @@ __global__ __launch_bounds__(kThreads) void k_adam_chain(float* __restrict__ p, 
     __shared__ float s_coef;
     if ((int)blockIdx.x < nb_upd) {
         __shared__ double s_own;
-        // a thread's first four elements are fetched before the clip preamble, whose partial sums, block reductions
-        // and pow() calls they then overlap
+        // a thread's first elements (up to four: one at the bucket sizes of K7, adam_update_blocks) are fetched before the
+        // clip preamble, whose partial sums, block reductions and pow() calls they then overlap
         constexpr int kPre = 4;
         float p0[kPre], g0[kPre], m0[kPre], v0[kPre];
 #pragma unroll
@@ -482,7 +621,7 @@ __global__ __launch_bounds__(kThreads) void k_adam_chain(float* __restrict__ p, 
 }  // namespace
 
 extern "C" size_t aurppo_mlp_workspace_bytes(int n_params) {
-    return sizeof(double) * 2 * kStatBlocks + sizeof(double) * 8 * kMaxGrid + sizeof(float) * (size_t)kMaxGrid * (size_t)n_params + 64 +
+    return sizeof(double) * 2 * kStatBlocks + sizeof(double) * 8 * kMaxGrid + sizeof(float) * (size_t)kMaxGrid * (size_t)slab_stride(n_params) + 64 +
            sizeof(unsigned long long) * 44 * kMaxGrid + sizeof(float) * 4 * 32 * 64 + 64 +
            ((sizeof(double) * (size_t)((n_params + 63) / 64) + 63) / 64) * 64 + 64 +
            mlp_step3_wop_bytes() + 64;
@@ -506,7 +645,7 @@ struct ChainArgs {   // the optimizer half of aurppo_mlp_ppo_minibatch_f32
 struct WsView {   // carve-up of the caller's workspace (aurppo_mlp_workspace_bytes)
     double* stats;               // (kStatBlocks, 2) advantage partial sums of the prepared minibatch
     double* loss_part;           // (kMaxGrid, 8)
-    float* slabs;                // (kMaxGrid, n_params)
+    float* slabs;                // (kMaxGrid, slab_stride(n_params)), 16-byte aligned
     unsigned long long* stamps;  // diagnostic build
     float* w1op;                 // W1 in B-operand order
     unsigned* tile_counter;
@@ -520,7 +659,7 @@ WsView ws_view(void* workspace, int n_params) {
     v.loss_part = v.stats + 2 * kStatBlocks;
     v.slabs = reinterpret_cast<float*>(v.loss_part + 8 * kMaxGrid);
     v.stamps = reinterpret_cast<unsigned long long*>(w + ((sizeof(double) * (2 * kStatBlocks + 8 * kMaxGrid) +
-                                                           sizeof(float) * (size_t)kMaxGrid * (size_t)n_params + 63) / 64) * 64);
+                                                           sizeof(float) * (size_t)kMaxGrid * (size_t)slab_stride(n_params) + 63) / 64) * 64);
     v.w1op = reinterpret_cast<float*>(v.stamps + 44 * kMaxGrid);
     v.tile_counter = reinterpret_cast<unsigned*>(v.w1op + 4 * 32 * 64);
     v.sq_part = reinterpret_cast<double*>(v.tile_counter + 16);
@@ -584,13 +723,12 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
     a.wop3 = wv.wop3;
     double* sq_part = wv.sq_part;
     if (!(chain && chain->chained)) {   // otherwise the previous chained call has prepared all of this
-        hipLaunchKernelGGL(k_adv_stats_idx, dim3(sb), dim3(kThreads), 0, s, a.rec, a.rec_stride, idx, M,
-                           reinterpret_cast<double (*)[2]>(stats), params, a.L.w1[0], a.L.w1[1], D, a.w1op, a.tile_counter);
+        // each variant's operand copies: W1 for k_mlp_step2 in the statistics workgroups, the bf16 planes for k_mlp_step3 in
+        // 24 more (4 elements per thread)
+        hipLaunchKernelGGL(k_adv_stats_idx, dim3(sb + (variant == 3 ? 24 : 0)), dim3(kThreads), 0, s, a.rec, a.rec_stride, idx, M,
+                           reinterpret_cast<double (*)[2]>(stats), params, a.L, D, variant == 2 ? a.w1op : nullptr, wv.wop3, sb,
+                           a.tile_counter);
         AURPPO_LAUNCH_CHECK("k_adv_stats_idx");
-        if (variant == 3) {
-            const int rc = launch_mlp3_prep(params, a.L, D, wv.wop3, s);
-            if (rc != AURPPO_OK) return rc;
-        }
     }
     const int n_tiles = (M + R - 1) / R;
     // One persistent workgroup per CU, minus one CU per XCD (AURPPO_MLP_SPARE_CUS, default 8; workgroups are dealt
@@ -623,15 +761,15 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
     const int n_red = (n_params + 63) / 64;
     // (words 8..11 of the counter block: Adam's two bias corrections, formed by the reduce for the optimizer launch behind it)
     double* const bc = (chain && !chain->grad_only) ? reinterpret_cast<double*>(a.tile_counter + 8) : nullptr;
-    hipLaunchKernelGGL(k_mlp_reduce<1>, dim3(n_red), dim3(1024), 0, s, a.slabs, a.loss_part, grid, n_params, a.h, grads,
+    hipLaunchKernelGGL(k_mlp_reduce_x4, dim3(n_red), dim3(256), 0, s, a.slabs, a.loss_part, grid, n_params, a.h, grads,
                        out_scalars, (chain && !chain->grad_only) ? sq_part : nullptr, chain ? chain->step_dev : nullptr,
                        a.tile_counter, bc ? chain->beta1 : 0.0, bc ? chain->beta2 : 0.0, bc);
-    AURPPO_LAUNCH_CHECK("k_mlp_reduce");
+    AURPPO_LAUNCH_CHECK("k_mlp_reduce_x4");
     if (chain && !chain->grad_only) {
-        int nb_upd = (n_params + kThreads * 4 - 1) / (kThreads * 4);
-        if (nb_upd > 64) nb_upd = 64;
+        const int nb_upd = adam_update_blocks(n_params);
         const int nsb = chain->next_idx ? stat_blocks_for(chain->next_M) : 0;
-        OperandCopies oc = {a.L.w1[0], a.L.w1[1], D, a.w1op, a.L.w2[0], a.L.w2[1],
+        // w1op is k_mlp_step2's operand; k_mlp_step3 never reads it, and the next non-chained call rebuilds it (k_adv_stats_idx)
+        OperandCopies oc = {a.L.w1[0], a.L.w1[1], D, variant == 2 ? a.w1op : nullptr, a.L.w2[0], a.L.w2[1],
                             variant == 3 ? wv.wop3 : (unsigned short*)nullptr, {}};
         oc.wide.wop = nullptr;
         hipLaunchKernelGGL(k_adam_chain, dim3(nb_upd + nsb), dim3(kThreads), 0, s, chain->params_rw, grads, chain->exp_avg,
@@ -672,8 +810,7 @@ int aurppo_mlp::launch_adam_tail(float* params, float* grads, float* exp_avg, fl
                                  double beta1, double beta2, double eps, float* out_norm, hipStream_t s, const WideCopies* wide,
                                  const float4* rec, int rec_stride, const int32_t* next_idx, int next_M, double* stats,
                                  const double* bc) {
-    int nb_upd = (n_params + kThreads * 4 - 1) / (kThreads * 4);
-    if (nb_upd > 64) nb_upd = 64;
+    const int nb_upd = adam_update_blocks(n_params);
     // no K7 operand copies (offsets past the bucket); K7w's if the caller names them; statistics of a next minibatch if it names one
     OperandCopies oc = no_operand_copies(n_params);
     if (wide) oc.wide = *wide;
@@ -749,8 +886,7 @@ static int mlp_apply_impl(float* params, float* grads, float* exp_avg, float* ex
     const WsView wv = ws_view(workspace, n_params);
     double* stats = wv.stats;
     float* w1op = wv.w1op;
-    int nb_upd = (n_params + kThreads * 4 - 1) / (kThreads * 4);
-    if (nb_upd > 64) nb_upd = 64;
+    const int nb_upd = adam_update_blocks(n_params);
     const int nsb = next_idx ? stat_blocks_for(next_M) : 0;
     OperandCopies oc_apply = {layout_h[0], layout_h[6], D, w1op, layout_h[2], layout_h[8],
                               aurppo_knobs().k7_variant == 3 ? wv.wop3 : (unsigned short*)nullptr, {}};

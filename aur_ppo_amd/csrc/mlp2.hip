@@ -700,7 +700,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
     }
     __syncthreads();
     if (set == 0) {
-        float* slab = a.slabs + (size_t)blockIdx.x * a.L.n_params;
+        float* slab = a.slabs + (size_t)blockIdx.x * slab_stride(a.L.n_params);
         const int col = cb * 32 + (le & 31);
 #pragma unroll
         for (int ob = 0; ob < 2; ++ob) {

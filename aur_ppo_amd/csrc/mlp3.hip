@@ -672,7 +672,7 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
     }
     __syncthreads();
     if (set == 0) {
-        float* slab = a.slabs + (size_t)blockIdx.x * a.L.n_params;
+        float* slab = a.slabs + (size_t)blockIdx.x * slab_stride(a.L.n_params);
         const int col = cb * 32 + (le & 31);
 #pragma unroll
         for (int ob = 0; ob < 2; ++ob) {
@@ -743,38 +743,12 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
 #endif
 }
 
-// wop3[...] = the bf16 planes of W1 / W2 of both nets in operand order (bf16x3.h), written destination-first so that the
-// padding (state columns >= D) is zero without a clearing pass
-__global__ __launch_bounds__(256) void k_mlp3_prep(const float* __restrict__ params, MlpLayout L, int D, unsigned short* __restrict__ wop3) {
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < 4 * kWopMats * kWopKs * 64 * 8; e += gridDim.x * 256) {
-        const int j = e & 7, lane = (e >> 3) & 63, ks = (e >> 9) & 3, mt = (e >> 11) % kWopMats, wi = (e >> 11) / kWopMats;
-        const int net = wi >> 1, cb = wi & 1;
-        const int k = 16 * ks + 8 * (lane >> 5) + j, c = cb * 32 + (lane & 31);
-        float v;
-        if (mt == 0) v = k < D ? params[L.w1[net] + c * D + k] : 0.0f;          // W1[o = c][d = k]
-        else if (mt == 1) v = params[L.w2[net] + c * H + k];                      // W2[o = c][i = k]
-        else v = params[L.w2[net] + k * H + c];                                   // W2[o2 = k][i = c]
-        unsigned p0, p1, p2;
-        split3(v, 0.0f, p0, p1, p2);
-        const int at = wop3_index(wi, mt, ks, 0, lane, j);
-        wop3[at] = (unsigned short)p0;
-        wop3[at + kWopBlock] = (unsigned short)p1;
-        wop3[at + 2 * kWopBlock] = (unsigned short)p2;
-    }
-}
-
 }  // namespace
 
 namespace aurppo_mlp {
 
 size_t mlp_step3_lds_bytes() { return (size_t)kDynBytes; }
 size_t mlp_step3_wop_bytes() { return sizeof(unsigned short) * (size_t)kWopElems; }
-
-int launch_mlp3_prep(const float* params, const MlpLayout& L, int D, void* wop3, hipStream_t s) {
-    hipLaunchKernelGGL(k_mlp3_prep, dim3(24), dim3(256), 0, s, params, L, D, reinterpret_cast<unsigned short*>(wop3));
-    AURPPO_LAUNCH_CHECK("k_mlp3_prep");
-    return AURPPO_OK;
-}
 
 int launch_mlp_step3(const MlpArgs& a, int grid, hipStream_t s) {
     static bool attr_set[kMaxDevices] = {false};

@@ -19,6 +19,11 @@ constexpr int kThreads = 256;
 constexpr int kMaxGrid = 256;
 constexpr int kStatBlocks = 256;
 
+// K7's gradient slabs: (kMaxGrid, slab_stride) floats, slab b's parameter p at b * slab_stride + p (bucket order).  The stride is
+// padded to 64 floats so that every slab row starts on a 256-B boundary: k_mlp_reduce then reads a row's 64 parameters of a
+// workgroup as 16 aligned 16-byte loads (two whole 128-B lines).  The padding is never written and never read.
+__host__ __device__ constexpr int slab_stride(int n_params) { return (n_params + 63) & ~63; }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct MlpLayout {  // float offsets into the flat parameter / gradient bucket
@@ -34,7 +39,7 @@ struct MlpArgs {
     int rec_stride;        // float4s per record: 1, or 4 in packed mode (actions == nullptr)
     const int32_t* idx;    // (M,) minibatch permutation slice
     const float* params;   // flat bucket
-    float* slabs;          // (grid, n_params) per-workgroup gradient slabs
+    float* slabs;          // (grid, slab_stride(n_params)) per-workgroup gradient slabs
     double* loss_part;     // (grid, 8)
     unsigned long long* stamps;  // diagnostic build: (grid, 16) cycle counters
     unsigned* tile_counter;  // next tile to hand out ([0]), zeroed by k_adv_stats_idx / k_mlp_reduce
@@ -176,10 +181,10 @@ __device__ __forceinline__ f32x16 zero16() {
 // mlp2.hip: the two-tile-set variant of K7 (8 waves per workgroup); same arguments, same slab / loss_part outputs.
 size_t mlp_step2_lds_bytes();
 int launch_mlp_step2(const MlpArgs& a, int grid, hipStream_t s);
-// mlp3.hip: the same step on bf16 MFMAs over three-way bf16 splits (AURPPO_K7_VARIANT=3); its operand-order weight copies
+// mlp3.hip: the same step on bf16 MFMAs over three-way bf16 splits (AURPPO_K7_VARIANT=3); its operand-order weight copies (bf16x3.h:
+// wop3_prepare, run by k_adv_stats_idx; refreshed by k_adam_chain)
 size_t mlp_step3_lds_bytes();
 size_t mlp_step3_wop_bytes();
-int launch_mlp3_prep(const float* params, const MlpLayout& L, int D, void* wop3, hipStream_t s);
 int launch_mlp_step3(const MlpArgs& a, int grid, hipStream_t s);
 // mlp.hip: k_mlp_reduce alone (grads[p] = fixed-order sum over n_slabs slabs, loss scalars folded) -- mlp_wide.hip's tail.
 // sq_part / step_dev != nullptr: also leave the clip's partial sums of squares (one per 64 parameters) and advance the

@@ -25,7 +25,7 @@ for _ in range(3):
     Hh.mlp_ppo_step(obs, None, rec64, idx, bucket.flat_param, lay, bucket.flat_grad, 0.2, 0.0, 0.5)
 torch.cuda.synchronize()
 ws = H._ws_cache[("mlp", torch.cuda.current_device())]
-off = ((8 * (2 * 256 + 8 * 256) + 4 * 256 * n + 63) // 64) * 64
+off = ((8 * (2 * 256 + 8 * 256) + 4 * 256 * ((n + 63) // 64 * 64) + 63) // 64) * 64   # slabs: (256, slab_stride(n)) floats
 if True:
     if os.environ.get("AURPPO_K7_VARIANT", "3") != "2":
         x = ws[off + 8 * 40 * 256:off + 8 * 44 * 256].view(torch.int64).view(256, 4).cpu().numpy().astype(np.float64)
