@@ -40,10 +40,36 @@ SHAPES = [  # hidden, layers, D, A, T, N, M
 ]
 
 
+def _select_variant(H, monkeypatch, variant, hidden, D):
+    """The builds of K7w, held to the SAME tolerances: AURPPO_K7W_VARIANT 3 (default) runs k_mlpw3_step (bf16 MFMA over three-way
+    splits, kernel id 3) for the shapes wider than 64, 2 keeps the fp32-MFMA k_mlpw_step<., false> (id 2); hidden <= 64 over D <= 64
+    is k_mlpw_step<., true> (id 1) under either.  Asserts which kernel the shape is dispatched to."""
+    monkeypatch.setenv("AURPPO_K7W_VARIANT", variant)
+    H.reload_knobs()
+    want = 1 if (hidden <= 64 and D <= 64) else int(variant)
+    assert H.k7w_kernel(hidden, D) == want, (H.k7w_kernel(hidden, D), want)
+    return want
+
+
+WIDER = [s for s in SHAPES if not (s[0] <= 64 and s[2] <= 64)]      # the shapes AURPPO_K7W_VARIANT chooses a kernel for
+
+
 @pytest.mark.parametrize("hidden,layers,D,A,T,N,M", SHAPES)
 @pytest.mark.parametrize("norm_adv,vmode,packed", [(True, 1, True), (False, 2, False), (True, 0, False)])
-def test_wide_step_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed):
+def test_wide_step_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed, monkeypatch):
+    _wide_step(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed, monkeypatch, "3")
+
+
+@pytest.mark.parametrize("hidden,layers,D,A,T,N,M", WIDER)
+@pytest.mark.parametrize("norm_adv,vmode,packed", [(True, 1, True), (False, 2, False), (True, 0, False)])
+def test_wide_step_fp32_mfma_build_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed, monkeypatch):
+    """AURPPO_K7W_VARIANT=2: k_mlpw_step<., false> (kernel id 2), same inputs, same tolerances."""
+    assert _wide_step(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed, monkeypatch, "2") == 2
+
+
+def _wide_step(hidden, layers, D, A, T, N, M, norm_adv, vmode, packed, monkeypatch, variant):
     H, pol, bucket, obs, act, rec = _setup(T, N, D, A, hidden, layers)
+    kid = _select_variant(H, monkeypatch, variant, hidden, D)
     idx = torch.randperm(T * N, device="cuda")[:M].int()
     lay = H.mlp_layout(pol, bucket)
     assert lay is not None and lay["wide"] and (lay["hidden"], lay["num_layers"], lay["D"], lay["A"]) == (hidden, layers, D, A)
@@ -73,13 +99,26 @@ def test_wide_step_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv
         # floor: a bias gradient is a sum of M terms that may cancel to far below the terms' own rounding error
         assert float((a - b).abs().max()) <= 5e-5 * s + 2e-6 * scale + 1e-9, (nm, float((a - b).abs().max()), s)
         off += k
+    return kid
 
 
 @pytest.mark.parametrize("hidden,layers,D,A,T,N,M", [(128, 2, 4, 2, 8, 64, 200), (64, 3, 64, 16, 16, 64, 1024), (128, 3, 6, 11, 8, 64, 333),
                                                     (48, 1, 5, 3, 8, 64, 200)])
 @pytest.mark.parametrize("norm_adv,vmode,ec", [(True, 1, 0.01), (False, 2, 0.05)])
-def test_wide_step_categorical_head_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec):
+def test_wide_step_categorical_head_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec, monkeypatch):
+    _wide_step_categorical(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec, monkeypatch, "3")
+
+
+@pytest.mark.parametrize("hidden,layers,D,A,T,N,M", [(128, 2, 4, 2, 8, 64, 200), (128, 3, 6, 11, 8, 64, 333)])
+@pytest.mark.parametrize("norm_adv,vmode,ec", [(True, 1, 0.01), (False, 2, 0.05)])
+def test_wide_step_categorical_head_fp32_mfma_build_matches_autograd_path(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec, monkeypatch):
+    """AURPPO_K7W_VARIANT=2 (kernel id 2) for the wider shapes of the test above."""
+    assert _wide_step_categorical(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec, monkeypatch, "2") == 2
+
+
+def _wide_step_categorical(hidden, layers, D, A, T, N, M, norm_adv, vmode, ec, monkeypatch, variant):
     H, pol, bucket, obs, act, rec = _setup(T, N, D, A, hidden, layers, seed=1, cont=False)
+    kid = _select_variant(H, monkeypatch, variant, hidden, D)
     idx = torch.randperm(T * N, device="cuda")[:M].int()
     lay = H.mlp_layout(pol, bucket)
     assert lay is not None and lay["wide"] and lay["continuous"] is False
@@ -104,6 +143,7 @@ def test_wide_step_categorical_head_matches_autograd_path(hidden, layers, D, A, 
         s_ = float(b.abs().max())
         assert float((a - b).abs().max()) <= 5e-5 * s_ + 2e-6 * gscale + 1e-9, (off, float((a - b).abs().max()), s_)
         off += k
+    return kid
 
 
 @pytest.mark.parametrize("hidden,layers,N,D,A,cont", [(128, 2, 4096, 64, 6, True), (128, 3, 77, 128, 2, False), (64, 3, 256, 16, 16, True),
@@ -219,6 +259,17 @@ def test_rollout_with_a_wide_policy_goes_through_k8w_and_trains():
 @pytest.mark.parametrize("handover", [False, True], ids=["prepare-each-call", "handed-over"])
 @pytest.mark.parametrize("hidden,layers,D", [(128, 3, 64), (64, 3, 24), (32, 1, 8), (96, 2, 100)])
 def test_wide_minibatch_matches_step_then_clip_adam(hidden, layers, D, handover, monkeypatch):
+    _wide_minibatch(hidden, layers, D, handover, monkeypatch, "3")
+
+
+@pytest.mark.parametrize("handover", [False, True], ids=["prepare-each-call", "handed-over"])
+@pytest.mark.parametrize("hidden,layers,D", [(128, 3, 64), (96, 2, 100)])
+def test_wide_minibatch_fp32_mfma_build_matches_step_then_clip_adam(hidden, layers, D, handover, monkeypatch):
+    """AURPPO_K7W_VARIANT=2 (kernel id 2) for the wider shapes of the test above."""
+    assert _wide_minibatch(hidden, layers, D, handover, monkeypatch, "2") == 2
+
+
+def _wide_minibatch(hidden, layers, D, handover, monkeypatch, variant):
     """aurppo_mlp_wide_ppo_minibatch_f32 over a run of minibatches == the same run as aurppo_mlp_wide_ppo_step_f32 +
     aurppo_clip_adam_f32 pairs: parameters, moments, loss scalars, norms and the Adam step count.  Tiles are dealt by
     static stride in both runs, so the two see the same summation order (tests/test_determinism.py) and the norms can be held
@@ -226,6 +277,7 @@ def test_wide_minibatch_matches_step_then_clip_adam(hidden, layers, D, handover,
     monkeypatch.setenv("AURPPO_STATIC_TILES", "1")
     T, N, A, M = 16, 64, 6, 300      # B = 1024: three full slices and a ragged tail
     H, pol, bucket, obs, act, rec = _setup(T, N, D, A, hidden, layers, seed=3)
+    kid = _select_variant(H, monkeypatch, variant, hidden, D)
     lay = H.mlp_layout(pol, bucket)
     nb = bucket.flat_param.numel()
     perm = torch.randperm(T * N, device="cuda").int()
@@ -264,3 +316,4 @@ def test_wide_minibatch_matches_step_then_clip_adam(hidden, layers, D, handover,
     for a_, b_ in zip(got[:3], ref[:3]):
         torch.testing.assert_close(a_, b_, rtol=1e-4, atol=1e-6)
     assert float((ref[0] - p0).abs().max()) > 1e-3
+    return kid
