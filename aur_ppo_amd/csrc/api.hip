@@ -73,6 +73,17 @@ extern "C" int aurppo_k7_variant(void) {
     return aurppo_knobs().k7_variant;
 }
 
+int aurppo_cu_count(int fallback) {
+    static int cus_of[kMaxDevices] = {0};
+    const int dslot = aurppo_device_slot();
+    if (!cus_of[dslot]) {
+        hipDeviceProp_t prop;
+        AURPPO_HIP_TRY(hipGetDeviceProperties(&prop, dslot));
+        cus_of[dslot] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : fallback;
+    }
+    return cus_of[dslot];
+}
+
 extern "C" int aurppo_device_count(void) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

@@ -120,37 +120,41 @@ __device__ __forceinline__ Frag3 x_cols(const char* img, int ks, int d0, int lan
     return f;
 }
 // A[m = f0 + 0..31][k = s] or B[k = s][n = f0 + 0..31] (32x32x16) from an F image, k-step ks (16 samples): row read
+template <int PL = kFPlane>
 __device__ __forceinline__ Frag3 f_rows(const char* img, int f0, int ks, int lane) {       // f0 a multiple of 16, ks < 2
     const int o = (foff(lane & 31, 8 * (lane >> 5)) ^ (ks << 5)) + f0 * kFRow;      // = foff(f0 + (lane & 31), 16 ks + 8 (lane >> 5))
     Frag3 f;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * kFPlane + o);
+    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * PL + o);
     return f;
 }
 // A[m = s][k = f] (32x32x16) from an F image, k-step ks (16 features): transposed read
+template <int PL = kFPlane>
 __device__ __forceinline__ Frag3 f_cols(const char* img, int ks, int lane) {
     const TrLane t = tr_lane32(lane);
     const int o0 = foff(t.kq, t.m0) + 16 * ks * kFRow, o1 = foff(t.kq + 4, t.m0) + 16 * ks * kFRow;      // = foff(16 ks + kq (+ 4), m0): kq + 4 < 16
     Frag3 r;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * kFPlane + o0), lds_tr(img + p * kFPlane + o1));
+    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * PL + o0), lds_tr(img + p * PL + o1));
     return r;
 }
 // 16x16x32: A[m = s0 + 0..15][k = f] from an F image, k-step ks (32 features): transposed read
+template <int PL = kFPlane>
 __device__ __forceinline__ Frag3 f_cols16(const char* img, int s0, int ks, int lane) {
     const TrLane t = tr_lane16(lane);
     const int o0 = foff(t.kq, s0 + t.m0) + 32 * ks * kFRow, o1 = foff(t.kq + 4, s0 + t.m0) + 32 * ks * kFRow;      // kq + 4 < 32
     Frag3 r;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * kFPlane + o0), lds_tr(img + p * kFPlane + o1));
+    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * PL + o0), lds_tr(img + p * PL + o1));
     return r;
 }
 // 16x16x32: B[k = s][n = f0 + 0..15] from an F image (all 32 samples = one k-step): row read
+template <int PL = kFPlane>
 __device__ __forceinline__ Frag3 f_rows16(const char* img, int f0, int lane) {
     const int o = foff(f0 + (lane & 15), 8 * (lane >> 4));
     Frag3 f;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * kFPlane + o);
+    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * PL + o);
     return f;
 }
 

@@ -44,6 +44,9 @@ static inline int aurppo_device_slot() {
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
     return d;
 }
+// CUs of the calling thread's current device (asked once per device; `fallback` if the runtime reports none), or a negative AURPPO_E*
+// code with the error set (api.hip)
+int aurppo_cu_count(int fallback);
 // Diagnostic knobs.  Every environment variable the library looks at is parsed in ONE place (api.hip) into this struct,
 // once per process -- or on every call when AURPPO_TEST_KNOBS=1 (tests/conftest.py), so that one test process can flip
 // them.  None of them changes results beyond summation order; the defaults are the product configuration.

@@ -69,11 +69,7 @@ __global__ __launch_bounds__(kThreads) void k_loss(const float* __restrict__ new
         const double ts = block_sum<kNW>(s, sc[0]);
         const double tq = block_sum<kNW>(q, sc[1]);
         if (threadIdx.x == 0) {
-            const double m = ts / (double)p.h.M;
-            double var = (tq - ts * m) / (double)(p.h.M - 1);  // M == 1 -> 0/0 = NaN, like torch.std
-            if (var < 0.0) var = 0.0;
-            s_mean = (float)m;
-            s_std = (float)sqrt(var);
+            adv_mean_std(ts, tq, p.h.M, s_mean, s_std);
         }
         __syncthreads();
     }

@@ -24,10 +24,9 @@ using namespace aurppo_mlp;
 
 namespace {
 
-// Also lays out W1 of both nets in the B-operand order of k_mlp_step2's layer-1 MFMA chain (w1op != nullptr, variant 2):
-// w1op[(w * 32 + m) * 64 + lane] = W1[net = w >> 1][(w & 1) * 32 + (lane & 31)][2m + (lane >> 5)], zero beyond D, so
-// that wave w reads its slice with 32 fully coalesced loads per tile instead of holding it in registers.  The workgroups past
-// the first n_stat build k_mlp_step3's bf16-plane copies of W1 / W2 instead (variant 3; this was a launch of its own).
+// Also lays out W1 of both nets in the B-operand order of k_mlp_step2's layer-1 MFMA chain (w1op != nullptr, variant 2; the layout:
+// mlp_common.h, w1op_index).  The workgroups past the first n_stat build k_mlp_step3's bf16-plane copies of W1 / W2 instead (variant
+// 3; this was a launch of its own).
 __global__ __launch_bounds__(256) void k_adv_stats_idx(const float4* __restrict__ rec, int rec_stride,
                                                        const int32_t* __restrict__ idx,
                                                        int M, double (*__restrict__ stats)[2], const float* __restrict__ params,
@@ -41,10 +40,9 @@ __global__ __launch_bounds__(256) void k_adv_stats_idx(const float4* __restrict_
     __shared__ double sc[2][kThreads / kWave];
     if (blockIdx.x == 0 && threadIdx.x < 2) tile_counter[threadIdx.x] = 0u;
     if (w1op) {
-        for (int e = blockIdx.x * kThreads + threadIdx.x; e < 4 * 32 * 64; e += n_stat * kThreads) {
-            const int lane = e & 63, m = (e >> 6) & 31, w = e >> 11;
-            const int row = (w & 1) * 32 + (lane & 31), k = 2 * m + (lane >> 5);
-            w1op[e] = k < D ? params[L.w1[w >> 1] + row * D + k] : 0.0f;
+        for (int e = blockIdx.x * kThreads + threadIdx.x; e < kW1opFloats; e += n_stat * kThreads) {
+            const W1opPlace q = w1op_place(e);
+            w1op[e] = q.col < D ? params[L.w1[q.net] + q.row * D + q.col] : 0.0f;
         }
     }
     double s = 0.0, q = 0.0;
@@ -233,6 +231,22 @@ constexpr size_t act_lds_bytes() {
     return sizeof(float) * (size_t)(R * LD + 2 * 2 * R * LD + 2 * 2 * H * LD + 2 * AP * LD + 2 * R * LDO + 4 * H + 2 * AP + 2 * AP);
 }
 
+// The nine scalars of a minibatch from its six loss sums (r: pg, vl, ent, old KL, KL, clip fraction) and advantage statistics
+__device__ __forceinline__ void write_loss_scalars(const double* r, const PpoHyper& h, double adv_mean, double adv_std,
+                                                   float* __restrict__ out_scalars) {
+    const double M = (double)h.M;
+    const float pg = (float)(r[0] / M), vl = 0.5f * (float)(r[1] / M), ent = (float)(r[2] / M);
+    out_scalars[AURPPO_S_PG] = pg;
+    out_scalars[AURPPO_S_VL] = vl;
+    out_scalars[AURPPO_S_ENT] = ent;
+    out_scalars[AURPPO_S_OLD_KL] = (float)(r[3] / M);
+    out_scalars[AURPPO_S_KL] = (float)(r[4] / M);
+    out_scalars[AURPPO_S_CLIPFRAC] = (float)(r[5] / M);
+    out_scalars[AURPPO_S_LOSS] = (pg - h.ent_coef * ent) + vl * h.vf_coef;
+    out_scalars[AURPPO_S_ADV_MEAN] = (float)adv_mean;
+    out_scalars[AURPPO_S_ADV_STD] = (float)adv_std;
+}
+
 // grads[p] = sum over slabs, fixed order (deterministic); block 0 also folds the loss scalars.
 // 64 parameters x 16 slab groups per 1024-thread workgroup: every wave-instruction reads one coalesced
 // 256-B slab row, 16 rows per parameter are in flight at once, groups are combined through LDS in order.
@@ -304,19 +318,7 @@ __global__ __launch_bounds__(1024) void k_mlp_reduce(const float* __restrict__ s
         if (l == 0) r[q] = s;
     }
     __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double M = (double)h.M;
-        const float pg = (float)(r[0] / M), vl = 0.5f * (float)(r[1] / M), ent = (float)(r[2] / M);
-        out_scalars[AURPPO_S_PG] = pg;
-        out_scalars[AURPPO_S_VL] = vl;
-        out_scalars[AURPPO_S_ENT] = ent;
-        out_scalars[AURPPO_S_OLD_KL] = (float)(r[3] / M);
-        out_scalars[AURPPO_S_KL] = (float)(r[4] / M);
-        out_scalars[AURPPO_S_CLIPFRAC] = (float)(r[5] / M);
-        out_scalars[AURPPO_S_LOSS] = (pg - h.ent_coef * ent) + vl * h.vf_coef;
-        out_scalars[AURPPO_S_ADV_MEAN] = (float)loss_part[6];
-        out_scalars[AURPPO_S_ADV_STD] = (float)loss_part[7];
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) write_loss_scalars(r, h, loss_part[6], loss_part[7], out_scalars);
 }
 
 // K7's slab reduce (slabs of slab_stride floats, n_slabs <= kMaxGrid): k_mlp_reduce<1>'s sums, bit for bit, on 16-byte loads.
@@ -428,19 +430,7 @@ __global__ __launch_bounds__(256) void k_mlp_reduce_x4(const float* __restrict__
         }
     }
     __syncthreads();
-    if (folder) {
-        const double M = (double)h.M;
-        const float pg = (float)(r[0] / M), vl = 0.5f * (float)(r[1] / M), ent = (float)(r[2] / M);
-        out_scalars[AURPPO_S_PG] = pg;
-        out_scalars[AURPPO_S_VL] = vl;
-        out_scalars[AURPPO_S_ENT] = ent;
-        out_scalars[AURPPO_S_OLD_KL] = (float)(r[3] / M);
-        out_scalars[AURPPO_S_KL] = (float)(r[4] / M);
-        out_scalars[AURPPO_S_CLIPFRAC] = (float)(r[5] / M);
-        out_scalars[AURPPO_S_LOSS] = (pg - h.ent_coef * ent) + vl * h.vf_coef;
-        out_scalars[AURPPO_S_ADV_MEAN] = (float)adv_mean;
-        out_scalars[AURPPO_S_ADV_STD] = (float)adv_std;
-    }
+    if (folder) write_loss_scalars(r, h, adv_mean, adv_std, out_scalars);
 }
 
 // Where an updated weight is also kept in MFMA-operand order for the next K7 launch (W1 in k_mlp_step2's fp32 B-operand order;
@@ -452,10 +442,21 @@ struct OperandCopies {
     unsigned short* wop3;
     aurppo_mlp::WideCopies wide;     // K7w's copies (wide.wop == nullptr: none)
 };
+// No copies at all (every offset past the bucket), K7's (L != nullptr: the two-layer nets at L; w1op / wop3 name the copies to refresh) or
+// K7w's (wide != nullptr).
+OperandCopies operand_copies(int n_params, const MlpLayout* L = nullptr, int D = 1, float* w1op = nullptr,
+                             unsigned short* wop3 = nullptr, const aurppo_mlp::WideCopies* wide = nullptr) {
+    OperandCopies oc = {L ? L->w1[0] : n_params, L ? L->w1[1] : n_params, D, w1op, L ? L->w2[0] : n_params, L ? L->w2[1] : n_params, wop3, {}};
+    oc.wide.wop = nullptr;
+    if (wide) oc.wide = *wide;
+    return oc;
+}
+// bucket element i has just become pn: drop it wherever the weight appears as an operand.  The addresses are mlp_common.h's w1op_index,
+// op_index and op3_index written out (= op3_at(slot, nn >> 5, kk >> 4, 0, (nn & 31) + 32 ((kk >> 3) & 1), kk & 7) ...): called as
+// functions they compile k_adam_chain to other instructions, which is held back until that build has been timed against this one.
 __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, int i, float pn) {
     if (oc.wide.wop) {
-        // K7w (k_mlpw_prep's layout, source-first): forward copy B[k][j] = W[j][k], backward copy (layers >= 1) B[k][j] = W[k][j];
-        // entry ((nl * 2 + dir) * 16 + blk) * 1024 + lane * 16 + m
+        // K7w: forward copy of every hidden layer, backward copy of layers >= 1
         const aurppo_mlp::WideCopies& wc = oc.wide;
         for (int n = 0; n < 2; ++n)
             for (int l = 0; l < wc.NL; ++l) {
@@ -463,22 +464,20 @@ __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, 
                 const int e = i - wc.w[n][l];
                 if (e < 0 || e >= wc.Hd * in_dim) continue;
                 const int row = e / in_dim, col = e - row * in_dim;
-                const int nl = n * 3 + l;
-                if (wc.wop3) {
-                    // k_mlpw3_step's copies (mlp_wide.hip, w3::wop_index): slot (net, layer, direction) x column block x k-step x
-                    // plane x lane x 8; forward B[k][n = out] = W[out][k], backward (layers >= 1) B[k = out][n = in] = W[out][in]
+                if (wc.wop3) {      // k_mlpw3_step's copies: the bf16 planes of the new value
                     unsigned p0, p1, p2;
                     bf3::split3(pn, 0.0f, p0, p1, p2);
                     for (int dir = 0; dir < (l > 0 ? 2 : 1); ++dir) {
                         const int nn = dir == 0 ? row : col, kk = dir == 0 ? col : row;
-                        const int at = (nl * 2 + dir) * (4 * 8 * 3 * 512) + (nn >> 5) * (8 * 3 * 512) +
+                        const int at = op3_slot(n, l, dir) * kOp3Slot + (nn >> 5) * kOp3Slice +
                                        (((kk >> 4) * 3) * 64 + (nn & 31) + 32 * ((kk >> 3) & 1)) * 8 + (kk & 7);
                         wc.wop3[at] = (unsigned short)p0;
-                        wc.wop3[at + 512] = (unsigned short)p1;
-                        wc.wop3[at + 1024] = (unsigned short)p2;
+                        wc.wop3[at + kOp3Plane] = (unsigned short)p1;
+                        wc.wop3[at + 2 * kOp3Plane] = (unsigned short)p2;
                     }
                     continue;
                 }
+                const int nl = n * MAXL + l;
                 {
                     const int blk = (row >> 5) * 4 + (col >> 5), lane = (row & 31) + 32 * (col & 1), m = (col & 31) >> 1;
                     wc.wop[(((nl * 2 + 0) * 16 + blk) * 64 + lane) * 16 + m] = pn;
@@ -620,13 +619,6 @@ __global__ __launch_bounds__(kThreads) void k_adam_chain(float* __restrict__ p, 
 
 }  // namespace
 
-extern "C" size_t aurppo_mlp_workspace_bytes(int n_params) {
-    return sizeof(double) * 2 * kStatBlocks + sizeof(double) * 8 * kMaxGrid + sizeof(float) * (size_t)kMaxGrid * (size_t)slab_stride(n_params) + 64 +
-           sizeof(unsigned long long) * 44 * kMaxGrid + sizeof(float) * 4 * 32 * 64 + 64 +
-           ((sizeof(double) * (size_t)((n_params + 63) / 64) + 63) / 64) * 64 + 64 +
-           mlp_step3_wop_bytes() + 64;
-}
-
 namespace {
 struct ChainArgs {   // the optimizer half of aurppo_mlp_ppo_minibatch_f32
     float* params_rw;
@@ -642,36 +634,50 @@ struct ChainArgs {   // the optimizer half of aurppo_mlp_ppo_minibatch_f32
     int chained;
     int grad_only;   // stop after k_mlp_reduce (the caller all-reduces the gradient, then calls the apply half)
 };
-struct WsView {   // carve-up of the caller's workspace (aurppo_mlp_workspace_bytes)
+struct WsView {   // carve-up of the caller's workspace
     double* stats;               // (kStatBlocks, 2) advantage partial sums of the prepared minibatch
     double* loss_part;           // (kMaxGrid, 8)
     float* slabs;                // (kMaxGrid, slab_stride(n_params)), 16-byte aligned
-    unsigned long long* stamps;  // diagnostic build
+    unsigned long long* stamps;  // diagnostic build: (kMaxGrid, 44)
     float* w1op;                 // W1 in B-operand order
-    unsigned* tile_counter;
+    unsigned* tile_counter;      // 16 words: the counters; words 8..11 carry Adam's bias corrections from the reduce to the optimizer launch
     double* sq_part;             // clip partial sums, one per k_mlp_reduce workgroup
     unsigned short* wop3;        // k_mlp_step3: bf16 planes of W1 / W2 in operand order
+    size_t bytes;                // aurppo_mlp_workspace_bytes
 };
 WsView ws_view(void* workspace, int n_params) {
+    WsCarver c(workspace);
     WsView v;
-    char* w = reinterpret_cast<char*>(workspace);
-    v.stats = reinterpret_cast<double*>(w);
-    v.loss_part = v.stats + 2 * kStatBlocks;
-    v.slabs = reinterpret_cast<float*>(v.loss_part + 8 * kMaxGrid);
-    v.stamps = reinterpret_cast<unsigned long long*>(w + ((sizeof(double) * (2 * kStatBlocks + 8 * kMaxGrid) +
-                                                           sizeof(float) * (size_t)kMaxGrid * (size_t)slab_stride(n_params) + 63) / 64) * 64);
-    v.w1op = reinterpret_cast<float*>(v.stamps + 44 * kMaxGrid);
-    v.tile_counter = reinterpret_cast<unsigned*>(v.w1op + 4 * 32 * 64);
-    v.sq_part = reinterpret_cast<double*>(v.tile_counter + 16);
-    v.wop3 = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(v.sq_part) +
-                                               ((sizeof(double) * (size_t)((n_params + 63) / 64) + 63) / 64) * 64);
+    v.stats = c.take<double>(sizeof(double) * 2 * kStatBlocks);
+    v.loss_part = c.take<double>(sizeof(double) * 8 * kMaxGrid);
+    v.slabs = c.take<float>(sizeof(float) * (size_t)kMaxGrid * (size_t)slab_stride(n_params), 64);
+    v.stamps = c.take<unsigned long long>(sizeof(unsigned long long) * 44 * kMaxGrid);
+    v.w1op = c.take<float>(sizeof(float) * kW1opFloats);
+    v.tile_counter = c.take<unsigned>(sizeof(unsigned) * 16);
+    v.sq_part = c.take<double>((sizeof(double) * (size_t)((n_params + 63) / 64) + 63) / 64 * 64, 64);
+    v.wop3 = c.take<unsigned short>(mlp_step3_wop_bytes(), 64);
+    v.bytes = c.bytes;
     return v;
 }
 int stat_blocks_for(int M) {
     int sb = (M + kThreads * 4 - 1) / (kThreads * 4);
     return sb > kStatBlocks ? kStatBlocks : sb;
 }
+// layout_h: w1a,b1a,w2a,b2a,w3a,b3a, w1c,b1c,w2c,b2c,w3c,b3c, logstd (read, and checked, only for a Gaussian head)
+int fill_layout(MlpLayout& L, const int* layout_h, int continuous, int n_params, const char* who) {
+    for (int n = 0; n < 2; ++n) {
+        L.w1[n] = layout_h[6 * n + 0]; L.b1[n] = layout_h[6 * n + 1]; L.w2[n] = layout_h[6 * n + 2];
+        L.b2[n] = layout_h[6 * n + 3]; L.w3[n] = layout_h[6 * n + 4]; L.b3[n] = layout_h[6 * n + 5];
+    }
+    L.logstd = continuous ? layout_h[12] : 0;
+    L.n_params = n_params;
+    for (int k = 0; k < (continuous ? 13 : 12); ++k)
+        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "%s: layout[%d]=%d", who, k, layout_h[k]);
+    return AURPPO_OK;
+}
 }  // namespace
+
+extern "C" size_t aurppo_mlp_workspace_bytes(int n_params) { return ws_view(nullptr, n_params).bytes; }
 
 static int mlp_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
                          int A, int continuous, int hidden, const float* params, const int* layout_h, int n_params, float* grads,
@@ -695,15 +701,7 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
     a.rec_stride = actions ? 1 : 4;
     a.D = D; a.A = A;
     a.continuous = continuous ? 1 : 0;
-    // layout_h: w1a,b1a,w2a,b2a,w3a,b3a, w1c,b1c,w2c,b2c,w3c,b3c, logstd
-    for (int n = 0; n < 2; ++n) {
-        a.L.w1[n] = layout_h[6 * n + 0]; a.L.b1[n] = layout_h[6 * n + 1]; a.L.w2[n] = layout_h[6 * n + 2];
-        a.L.b2[n] = layout_h[6 * n + 3]; a.L.w3[n] = layout_h[6 * n + 4]; a.L.b3[n] = layout_h[6 * n + 5];
-    }
-    a.L.logstd = continuous ? layout_h[12] : 0;
-    a.L.n_params = n_params;
-    for (int k = 0; k < (continuous ? 13 : 12); ++k)
-        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "aurppo_mlp_ppo_step_f32: layout[%d]=%d", k, layout_h[k]);
+    if (const int rc = fill_layout(a.L, layout_h, continuous, n_params, "aurppo_mlp_ppo_step_f32")) return rc;
     a.h = make_hyper(M, clip, ent_coef, vf_coef, norm_adv, vloss_mode);
     const WsView wv = ws_view(workspace, n_params);
     double* stats = wv.stats;
@@ -735,14 +733,8 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
     // round-robin over the 8 XCDs): the single-workgroup shuffle kernels of the side stream then have a CU of
     // their own.  The kernel hands tiles out dynamically, but it fills a CU's register file, so a workgroup whose CU
     // is taken starts late; 8 spare CUs measured 3.86-3.93 ms per update against 4.09-4.10 ms with none.
-    static int cus_of[kMaxDevices] = {0};
-    const int dslot = aurppo_device_slot();
-    if (!cus_of[dslot]) {
-        hipDeviceProp_t prop;
-        AURPPO_HIP_TRY(hipGetDeviceProperties(&prop, dslot));
-        cus_of[dslot] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : kMaxGrid;
-    }
-    const int cus = cus_of[dslot];
+    const int cus = aurppo_cu_count(kMaxGrid);
+    if (cus < 0) return cus;
     const int spare = knobs.k7_spare_cus >= 0 ? knobs.k7_spare_cus : 8;
     int grid = cus - spare;
     if (grid > kMaxGrid) grid = kMaxGrid;
@@ -769,9 +761,7 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
         const int nb_upd = adam_update_blocks(n_params);
         const int nsb = chain->next_idx ? stat_blocks_for(chain->next_M) : 0;
         // w1op is k_mlp_step2's operand; k_mlp_step3 never reads it, and the next non-chained call rebuilds it (k_adv_stats_idx)
-        OperandCopies oc = {a.L.w1[0], a.L.w1[1], D, variant == 2 ? a.w1op : nullptr, a.L.w2[0], a.L.w2[1],
-                            variant == 3 ? wv.wop3 : (unsigned short*)nullptr, {}};
-        oc.wide.wop = nullptr;
+        const OperandCopies oc = operand_copies(n_params, &a.L, D, variant == 2 ? a.w1op : nullptr, variant == 3 ? wv.wop3 : nullptr);
         hipLaunchKernelGGL(k_adam_chain, dim3(nb_upd + nsb), dim3(kThreads), 0, s, chain->params_rw, grads, chain->exp_avg,
                            chain->exp_avg_sq, n_params, sq_part, n_red, (float)chain->max_norm, chain->lr_dev,
                            chain->step_dev, chain->beta1, chain->beta2, chain->eps, chain->out_norm, 1.0f, nb_upd, oc,
@@ -780,14 +770,6 @@ static int mlp_step_impl(const float* obs, const float* actions, const float* re
     }
     return AURPPO_OK;
 }
-
-namespace {
-OperandCopies no_operand_copies(int n_params) {   // every offset past the bucket: no copy is refreshed
-    OperandCopies oc = {n_params, n_params, 1, nullptr, n_params, n_params, nullptr, {}};
-    oc.wide.wop = nullptr;
-    return oc;
-}
-}  // namespace
 
 int aurppo_mlp::launch_mlp_reduce(const float* slabs, const double* loss_part, int n_slabs, int n_params, const PpoHyper& h,
                                   float* grads, float* out_scalars, hipStream_t s, double* sq_part, float* step_dev,
@@ -812,8 +794,7 @@ int aurppo_mlp::launch_adam_tail(float* params, float* grads, float* exp_avg, fl
                                  const double* bc) {
     const int nb_upd = adam_update_blocks(n_params);
     // no K7 operand copies (offsets past the bucket); K7w's if the caller names them; statistics of a next minibatch if it names one
-    OperandCopies oc = no_operand_copies(n_params);
-    if (wide) oc.wide = *wide;
+    const OperandCopies oc = operand_copies(n_params, nullptr, 1, nullptr, nullptr, wide);
     const int nsb = (next_idx && stats) ? stat_blocks_for(next_M) : 0;
     hipLaunchKernelGGL(k_adam_chain, dim3(nb_upd + nsb), dim3(kThreads), 0, s, params, grads, exp_avg, exp_avg_sq, n_params, sq_part,
                        (n_params + 63) / 64, (float)max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm, 1.0f, nb_upd, oc, rec,
@@ -880,17 +861,15 @@ static int mlp_apply_impl(float* params, float* grads, float* exp_avg, float* ex
                    "aurppo_mlp_ppo_apply_f32: next_M=%d rec_floats=%d", next_M, rec_floats);
     AURPPO_REQUIRE(aligned_to(workspace, 16) && (!rec || aligned_to(rec, 16)), AURPPO_EINVAL,
                    "aurppo_mlp_ppo_apply_f32: workspace / rec not 16-byte aligned");
-    for (int k = 0; k < 12; ++k)
-        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "aurppo_mlp_ppo_apply_f32: layout[%d]=%d", k,
-                       layout_h[k]);
+    MlpLayout L;      // (the optimizer touches no log-std offset: the twelve weight / bias offsets are what is read and checked)
+    if (const int rc = fill_layout(L, layout_h, 0, n_params, "aurppo_mlp_ppo_apply_f32")) return rc;
     const WsView wv = ws_view(workspace, n_params);
     double* stats = wv.stats;
     float* w1op = wv.w1op;
     const int nb_upd = adam_update_blocks(n_params);
     const int nsb = next_idx ? stat_blocks_for(next_M) : 0;
-    OperandCopies oc_apply = {layout_h[0], layout_h[6], D, w1op, layout_h[2], layout_h[8],
-                              aurppo_knobs().k7_variant == 3 ? wv.wop3 : (unsigned short*)nullptr, {}};
-    oc_apply.wide.wop = nullptr;
+    // (w1op is refreshed whichever variant runs: the next call may be made under the other one)
+    const OperandCopies oc_apply = operand_copies(n_params, &L, D, w1op, aurppo_knobs().k7_variant == 3 ? wv.wop3 : nullptr);
     hipLaunchKernelGGL(k_adam_chain, dim3(nb_upd + nsb), dim3(kThreads), 0, (hipStream_t)stream, params, grads, exp_avg,
                        exp_avg_sq, n_params, sq_part, sq_part ? n_part : 0, (float)max_norm, lr_dev, step_dev, beta1, beta2, eps,
                        out_norm, (float)grad_scale, nb_upd, oc_apply,
@@ -964,14 +943,7 @@ extern "C" int aurppo_mlp_act_f32(const float* obs, const float* noise, int N, i
     ActArgs a;
     a.obs = obs; a.noise = noise; a.params = params; a.actions = actions; a.logp = logp; a.value = value;
     a.N = N; a.D = D; a.A = A; a.continuous = continuous ? 1 : 0;
-    for (int n = 0; n < 2; ++n) {
-        a.L.w1[n] = layout_h[6 * n + 0]; a.L.b1[n] = layout_h[6 * n + 1]; a.L.w2[n] = layout_h[6 * n + 2];
-        a.L.b2[n] = layout_h[6 * n + 3]; a.L.w3[n] = layout_h[6 * n + 4]; a.L.b3[n] = layout_h[6 * n + 5];
-    }
-    a.L.logstd = continuous ? layout_h[12] : 0;
-    a.L.n_params = n_params;
-    for (int k = 0; k < (continuous ? 13 : 12); ++k)
-        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "aurppo_mlp_act_f32: layout[%d]=%d", k, layout_h[k]);
+    if (const int rc = fill_layout(a.L, layout_h, continuous, n_params, "aurppo_mlp_act_f32")) return rc;
     static bool attr_set[kMaxDevices] = {false};
     const int dslot = aurppo_device_slot();
     if (!attr_set[dslot]) {

@@ -25,7 +25,7 @@
 // The library is built with -ffp-contract=off for K1's bit parity; nothing in this file is held to bit parity (K7 is
 // checked to 1e-5 against fp32 autograd), so its VALU code may fuse a*b+c: 1.4 % off the kernel (profiles/r02/ab_fp_contract.txt).
 #pragma clang fp contract(fast)
-#include "mlp_common.h"
+#include "mlp_twoset.h"
 
 using namespace aurppo_mlp;
 
@@ -59,9 +59,6 @@ constexpr int kChB = AURPPO_KCH_BIG;
 // three alternating runs; 150 us with single-accumulator dot products): what a tile waits for is not the matrix pipe.  Off.
 #define AURPPO_K7_CRITIC_VALU 0
 #endif
-#ifndef AURPPO_BAR_SLEEP
-#define AURPPO_BAR_SLEEP 1   // s_sleep argument of the software barriers' poll loops (A/B knob; 0 = poll back to back)
-#endif
 
 // LDS carve-up (floats).  Shared by both sets:
 constexpr int oW2 = 0;                       // [2][H][LD]
@@ -82,13 +79,7 @@ constexpr int pSrc = pRec + 4 * R;           // int[R]
 constexpr int pIdx = pSrc + R;               // int[2][R]
 constexpr int kSetFloats = pIdx + 2 * R;     // multiple of 4
 static_assert(kSharedFloats % 4 == 0 && pRec % 4 == 0 && kSetFloats % 4 == 0, "float4 alignment of sRec");
-constexpr int kAccRegs = 72;                 // gW1 (32) + gW2 (32) + gW3 (2 x 4) per lane
-static_assert(kSharedFloats + 2 * kSetFloats >= 4 * kAccRegs * kWave, "hand-over scratch must fit the dead tiles");
-
-// LDS accumulate without reading the result back (ds_add_f64)
-__device__ __forceinline__ void lds_add(double* p, double v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
+static_assert(kSharedFloats + 2 * kSetFloats >= 4 * kTwoSetAccRegs * kWave, "hand-over scratch must fit the dead tiles");
 
 __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -270,11 +261,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
         const double ts = block_sum<kThreads2 / kWave>(s, s_red[0]);
         const double tq = block_sum<kThreads2 / kWave>(q, s_red[1]);
         if (tid == 0) {
-            const double m = ts / (double)a.h.M;
-            double var = (tq - ts * m) / (double)(a.h.M - 1);
-            if (var < 0.0) var = 0.0;
-            s_mean = (float)m;
-            s_std = (float)sqrt(var);
+            adv_mean_std(ts, tq, a.h.M, s_mean, s_std);
         }
     }
     __syncthreads();
@@ -358,32 +345,10 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
     st_last = __builtin_readcyclecounter();
     const unsigned long long clk0 = st_last, rt0 = wall_clock64();   // shader cycles vs the 100 MHz wall clock
 #endif
-    // The two sets do not share barriers inside the tile loop.  A set's four waves meet at a counter in LDS (arrive =
-    // one ds_add by lane 0 once the wave's LDS writes have completed, wait = poll until 4 more arrivals than at the
-    // previous barrier), so neither set ever waits for the other's longer phase -- with workgroup-wide barriers 38 %
-    // of the loop was the tail of barrier intervals where one set finished its epilogue alone -- and a set whose
-    // queue is dry simply leaves.  s_barrier is only used before and after the loop.
-    int bar_gen = 0;
-    auto set_bar = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) (void)__hip_atomic_fetch_add(&s_bar[set], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        bar_gen += 4;
-        while (__hip_atomic_load(&s_bar[set], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - bar_gen < 0)
-            __builtin_amdgcn_s_sleep(AURPPO_BAR_SLEEP);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
-    // Between the layers of one net only that net's two waves exchange data (each writes its column half of H1 / H2 /
-    // dZ2 / dZ1, both read all of it): those four barriers involve two waves, not four, and the actor and critic pairs
-    // drift apart between the set-wide barriers around S and L.
-    int pbar_gen = 0;
-    auto pair_bar = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) (void)__hip_atomic_fetch_add(&s_pbar[set][net], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pbar_gen += 2;
-        while (__hip_atomic_load(&s_pbar[set][net], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - pbar_gen < 0)
-            __builtin_amdgcn_s_sleep(AURPPO_BAR_SLEEP);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
+    // the software barriers of the tile loop (mlp_twoset.h): a set's four waves, and the two waves of one net
+    int bar_gen = 0, pbar_gen = 0;
+    auto set_bar = [&]() { wave_group_bar<4>(&s_bar[set], bar_gen, lane); };
+    auto pair_bar = [&]() { wave_group_bar<2>(&s_pbar[set][net], pbar_gen, lane); };
     for (int it = 0; s_first[set] != 0; ++it) {
         // Opaque per-tile copies of the lane coordinates: every LDS address below is re-derived from them inside
         // the phase (one or two VALU ops) instead of being hoisted out of the loop as ~100 loop-invariant
@@ -666,7 +631,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
     int le = lane, se = st;   // fresh opaque copies: nothing lane-derived has to stay live across the tile loop
     asm volatile("" : "+v"(le), "+v"(se));
     // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab
-    float* park = lds + (size_t)wi * kAccRegs * kWave + le;   // [role][reg][le]: set 0's wave of the same role reads it
+    float* park = lds + (size_t)wi * kTwoSetAccRegs * kWave + le;   // [role][reg][le]: set 0's wave of the same role reads it
     // head-side column sums: fold the 8 rows a wave's loss lanes cover
     float hs[5] = {g_b3a[0], g_b3a[1], g_ls[0], g_ls[1], (se & 7) == 0 ? g_b3c : 0.0f};
 #pragma unroll

@@ -19,8 +19,8 @@
 #include <stdlib.h>
 
 #pragma clang fp contract(fast)
-#include "bf16x3.h"
-#include "mlp_common.h"
+#include "mlp_bf3.h"
+#include "mlp_twoset.h"
 
 using namespace aurppo_mlp;
 using namespace bf3;
@@ -52,9 +52,6 @@ namespace {
 
 constexpr int kThreads3 = 512;
 constexpr int kSetThreads = 256;
-#ifndef AURPPO_BAR_SLEEP
-#define AURPPO_BAR_SLEEP 1
-#endif
 
 // ---- dynamic LDS carve-up (bytes).  Shared by both sets:
 constexpr int kW3Row = 128, kW3Plane = AP * kW3Row, kW3Net = 3 * kW3Plane;       // W3 image [a 16][i 64] per net
@@ -78,59 +75,12 @@ constexpr int pIdx = pSrc + 4 * R;                   // int[2][R]
 constexpr int kSetBytes = pIdx + 4 * 2 * R;
 static_assert(kSharedBytes % 16 == 0 && pH1 % 16 == 0 && pH2 % 16 == 0 && pDo % 16 == 0 && pOut % 16 == 0 && pRec % 16 == 0 &&
               kSetBytes % 16 == 0, "16-byte alignment of the images");
-constexpr int kAccRegs = 72;                         // gW1 (32) + gW2 (32) + gW3 (2 x 4) per lane
 constexpr int kDynBytes = kSharedBytes + 2 * kSetBytes;
 // the hand-over at the end reuses the (dead) tile memory: parked accumulators, then the small column sums
-constexpr int kParkBytes = 4 * 4 * kAccRegs * kWave;
+constexpr int kParkBytes = 4 * 4 * kTwoSetAccRegs * kWave;
 constexpr int kSmallOff = kParkBytes;                // float [8 waves][8][5]
 constexpr int kGbOff = kSmallOff + 4 * 8 * 8 * 5;    // float [4 roles][2][32]
 static_assert(kGbOff + 4 * 4 * 2 * 32 <= kDynBytes, "hand-over scratch must fit the dead tiles");
-
-// Epilogues, four values (one 8-byte store per plane) at a time so that nothing but the accumulator is live across them.
-// tanh(acc + bias) of a 32x32 block into an F image:
-// om[e] = 1 - tanh^2 of the same element, kept in registers for the backward pass (dz_from_regs): re-read from the image's planes it
-// cost three unpacks and two adds per value to join and twelve LDS reads per block (the register file has had room for the 2 x 16
-// values since the fragment addresses stopped being re-derived, bf16x3.h)
-__device__ __forceinline__ void tanh_store(char* img, int f0, const f32x16& acc, float bias, int lane, float (&om)[16]) {
-    const int f = f0 + (lane & 31), h = lane >> 5;
-    const float bc = bias * kTanhC;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-        unsigned a0, a1, a2, b0, b1, b2;
-        const float t0 = tanh_fast_fma(acc[4 * gq + 0], bc), t1 = tanh_fast_fma(acc[4 * gq + 1], bc);
-        const float t2 = tanh_fast_fma(acc[4 * gq + 2], bc), t3 = tanh_fast_fma(acc[4 * gq + 3], bc);
-        om[4 * gq + 0] = 1.0f - t0 * t0; om[4 * gq + 1] = 1.0f - t1 * t1;
-        om[4 * gq + 2] = 1.0f - t2 * t2; om[4 * gq + 3] = 1.0f - t3 * t3;
-        split3(t0, t1, a0, a1, a2);
-        split3(t2, t3, b0, b1, b2);
-        const int o = foff(f, 4 * h) ^ (gq << 4);       // = foff(f, 8 gq + 4 h)
-        *reinterpret_cast<u32x2*>(img + 0 * kFPlane + o) = u32x2{a0, b0};
-        *reinterpret_cast<u32x2*>(img + 1 * kFPlane + o) = u32x2{a1, b1};
-        *reinterpret_cast<u32x2*>(img + 2 * kFPlane + o) = u32x2{a2, b2};
-    }
-}
-// dZ = dH * (1 - h^2), (1 - h^2) from the forward pass's registers, written over the block of h in the image; returns the lane's column sum
-__device__ __forceinline__ float dz_from_regs(char* img, int f0, const f32x16& dh, const float (&om)[16], int lane) {
-    const int f = f0 + (lane & 31), h = lane >> 5;
-    float colsum = 0.0f;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-        const float d0 = dh[4 * gq + 0] * om[4 * gq + 0], d1 = dh[4 * gq + 1] * om[4 * gq + 1];
-        const float d2 = dh[4 * gq + 2] * om[4 * gq + 2], d3 = dh[4 * gq + 3] * om[4 * gq + 3];
-        colsum += (d0 + d1) + (d2 + d3);
-        unsigned a0, a1, a2, b0, b1, b2;
-        split3(d0, d1, a0, a1, a2);
-        split3(d2, d3, b0, b1, b2);
-        const int o = foff(f, 4 * h) ^ (gq << 4);
-        *reinterpret_cast<u32x2*>(img + 0 * kFPlane + o) = u32x2{a0, b0};
-        *reinterpret_cast<u32x2*>(img + 1 * kFPlane + o) = u32x2{a1, b1};
-        *reinterpret_cast<u32x2*>(img + 2 * kFPlane + o) = u32x2{a2, b2};
-    }
-    return colsum;
-}
-__device__ __forceinline__ void lds_add(double* p, double v) {
-    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -368,11 +318,7 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
         const double ts = block_sum<kThreads3 / kWave>(st_s, s_red[0]);
         const double tq = block_sum<kThreads3 / kWave>(st_q, s_red[1]);
         if (tid == 0) {
-            const double m = ts / (double)a.h.M;
-            double var = (tq - ts * m) / (double)(a.h.M - 1);
-            if (var < 0.0) var = 0.0;
-            s_mean = (float)m;
-            s_std = (float)sqrt(var);
+            adv_mean_std(ts, tq, a.h.M, s_mean, s_std);
         }
     }
     __syncthreads();
@@ -395,24 +341,10 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
 
     __syncthreads();
 
-    int bar_gen = 0;
-    auto set_bar = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) (void)__hip_atomic_fetch_add(&s_bar[set], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        bar_gen += 4;
-        while (__hip_atomic_load(&s_bar[set], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - bar_gen < 0)
-            __builtin_amdgcn_s_sleep(AURPPO_BAR_SLEEP);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
-    int pbar_gen = 0;
-    auto pair_bar = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) (void)__hip_atomic_fetch_add(&s_pbar[set][net], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pbar_gen += 2;
-        while (__hip_atomic_load(&s_pbar[set][net], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - pbar_gen < 0)
-            __builtin_amdgcn_s_sleep(AURPPO_BAR_SLEEP);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    };
+    // the software barriers of the tile loop (mlp_twoset.h): a set's four waves, and the two waves of one net
+    int bar_gen = 0, pbar_gen = 0;
+    auto set_bar = [&]() { wave_group_bar<4>(&s_bar[set], bar_gen, lane); };
+    auto pair_bar = [&]() { wave_group_bar<2>(&s_pbar[set][net], pbar_gen, lane); };
     auto wfrag = [&](int ks) {
         Frag3 f;
         f.p[0] = wreg[3 * ks + 0];
@@ -638,7 +570,7 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
     asm volatile("" : "+v"(le), "+v"(se));
     // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab
     float* const fl = reinterpret_cast<float*>(lds);
-    float* park = fl + (size_t)wi * kAccRegs * kWave + le;
+    float* park = fl + (size_t)wi * kTwoSetAccRegs * kWave + le;
     float (*s_small)[8][5] = reinterpret_cast<float (*)[8][5]>(lds + kSmallOff);
     float (*s_gb)[2][32] = reinterpret_cast<float (*)[2][32]>(lds + kGbOff);
     float hs[5] = {g_b3a[0], g_b3a[1], g_ls[0], g_ls[1], (se & 7) == 0 ? g_b3c : 0.0f};

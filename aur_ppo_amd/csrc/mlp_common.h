@@ -178,6 +178,22 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
+// A caller's workspace as regions at multiples of 64 bytes from its start, taken in order, and the size the caller is told to provide:
+// the regions' sizes plus the slack each was given for the rounding behind it (>= 64 where the size is no multiple of 64).  A family's
+// carve-up is ONE list of take() calls: its pointers and its *_workspace_bytes both come from that list.
+struct WsCarver {
+    uintptr_t at;        // where the next region starts
+    size_t bytes = 0;    // what the *_workspace_bytes entry point reports
+    explicit WsCarver(void* workspace) : at(reinterpret_cast<uintptr_t>(workspace)) {}
+    template <class T>
+    T* take(size_t n_bytes, size_t slack = 0) {
+        T* const p = reinterpret_cast<T*>(at);
+        at += (n_bytes + 63) / 64 * 64;
+        bytes += n_bytes + slack;
+        return p;
+    }
+};
+
 // mlp2.hip: the two-tile-set variant of K7 (8 waves per workgroup); same arguments, same slab / loss_part outputs.
 size_t mlp_step2_lds_bytes();
 int launch_mlp_step2(const MlpArgs& a, int grid, hipStream_t s);
@@ -215,13 +231,83 @@ __device__ __forceinline__ void adv_partial_sums(const float4* __restrict__ rec,
     }
 }
 
-// K7w's operand-order copies of the hidden layers (mlp_wide.hip: [net][layer][fwd | bwd][4 x 4 blocks][lane][16 k-steps]): where the
-// optimizer launch drops an updated weight so that the next K7w launch needs no prepare pass.  wop == nullptr: nothing to refresh.
+// ---- Operand-order copies of the weights.  Each layout has ONE index function, here, with its inverse beside it (tied by the
+// static_assert below): the kernel that builds a copy walks its entries and asks the inverse what each holds, the optimizer launch
+// that refreshes a copy in place (mlp.hip: refresh_operand_copies) asks the index where a weight sits.
+// k_mlp_step2's w1op (built by k_adv_stats_idx): W1 of both nets as the B operand of the layer-1 chain, [4 roles][32 steps][64 lanes]:
+// role net * 2 + cb, step m, lane l hold W1[net][cb*32 + (l & 31)][2m + (l >> 5)], zero beyond D -- wave `role` reads its slice with 32
+// fully coalesced loads per tile.  (k_mlp_step3's bf16 planes of W1 / W2: bf3::wop3_places / wop3_prepare, bf16x3.h.)
+constexpr int kW1opFloats = 4 * 32 * kWave;
+__host__ __device__ constexpr int w1op_index(int net, int row, int col) {
+    return ((net * 2 + (row >> 5)) * 32 + (col >> 1)) * kWave + (row & 31) + 32 * (col & 1);
+}
+struct W1opPlace { int net, row, col; };
+__host__ __device__ constexpr W1opPlace w1op_place(int e) {     // entry e holds W1[net][row][col]
+    return {e >> 12, ((e >> 11) & 1) * 32 + (e & 31), 2 * ((e >> 6) & 31) + ((e >> 5) & 1)};
+}
+
+// K7w's fp32 copies of the hidden layers (k_mlpw_prep builds, k_mlpw_step / k_mlpw_act stream): [net][layer][fwd | bwd][4 x 4 blocks]
+// [lane][16 steps].  Copy (net, l, dir) is a B operand -- forward (dir 0) B[k][j] = W[j][k], backward (dir 1, layers >= 1) B[k][j] =
+// W[k][j] -- and entry (block (jb, kb), lane, m) holds B[kb*32 + 2m + (lane >> 5)][jb*32 + (lane & 31)], zero beyond the layer's widths.
+constexpr int MAXL = 3;             // hidden layers of a K7w net
+constexpr int kOpBlk = 64 * 16;     // floats of one 32x32 block in operand order: [lane][16 k-steps]
+constexpr int kOpLayer = 16 * kOpBlk;                 // 4 x 4 blocks
+constexpr int kOpFloats = 2 * MAXL * 2 * kOpLayer;    // [net][layer][fwd | bwd]
+__host__ __device__ constexpr size_t op_copy(int net, int l, int dir) { return (size_t)((net * MAXL + l) * 2 + dir) * kOpLayer; }
+__host__ __device__ constexpr int op_entry(int jb, int kb, int lane, int m) { return (jb * 4 + kb) * kOpBlk + lane * 16 + m; }
+__host__ __device__ constexpr size_t op_at(int net, int l, int dir, int jb, int kb, int lane, int m) { return op_copy(net, l, dir) + op_entry(jb, kb, lane, m); }
+__host__ __device__ constexpr size_t op_index(int net, int l, int dir, int row, int col) {   // where W[row][col] sits in copy (net, l, dir)
+    const int j = dir == 0 ? row : col, k = dir == 0 ? col : row;
+    return op_at(net, l, dir, j >> 5, k >> 5, (j & 31) + 32 * (k & 1), (k & 31) >> 1);
+}
+// ... and back: the B[k][j] that entry (block (jb, kb), lane, m) holds, for a builder that walks the entries
+__host__ __device__ constexpr int op_j(int jb, int lane) { return jb * 32 + (lane & 31); }
+__host__ __device__ constexpr int op_k(int kb, int lane, int m) { return kb * 32 + 2 * m + (lane >> 5); }
+
+// K7w's bf16-plane copies (built by k_mlpw3_prep, streamed by k_mlpw3_step): slot (net, layer, direction) x column block of 32 x
+// k-step of 16 x plane x lane x 8, the same B operands: entry (cb, ks, p, lane, j) holds plane p of B[16 ks + 8 (lane >> 5) + j][cb*32 +
+// (lane & 31)].  A value's three planes lie kOp3Plane apart.
+constexpr int kOp3Ks = 8;                          // k-steps of a weight slice (128 / 16)
+constexpr int kOp3Plane = 64 * 8;                  // bf16 elements of one plane of one k-step
+constexpr int kOp3Slice = kOp3Ks * 3 * kOp3Plane;  // one (slot, column block) slice
+constexpr int kOp3Slot = 4 * kOp3Slice;            // one (net, layer, direction)
+constexpr int kOp3Elems = 2 * MAXL * 2 * kOp3Slot;
+__host__ __device__ constexpr int op3_slot(int net, int l, int dir) { return (net * MAXL + l) * 2 + dir; }
+__host__ __device__ constexpr int op3_at(int slot, int cb, int ks, int p, int lane, int j) {
+    return slot * kOp3Slot + cb * kOp3Slice + ((ks * 3 + p) * 64 + lane) * 8 + j;
+}
+__host__ __device__ constexpr int op3_index(int net, int l, int dir, int row, int col) {     // plane 0 of W[row][col] in copy (net, l, dir)
+    const int n = dir == 0 ? row : col, k = dir == 0 ? col : row;
+    return op3_at(op3_slot(net, l, dir), n >> 5, k >> 4, 0, (n & 31) + 32 * ((k >> 3) & 1), k & 7);
+}
+// ... and back: the B[k][n] that entry (cb, ks, lane, j) holds, for a builder that walks the entries
+__host__ __device__ constexpr int op3_n(int cb, int lane) { return cb * 32 + (lane & 31); }
+__host__ __device__ constexpr int op3_k(int ks, int lane, int j) { return 16 * ks + 8 * (lane >> 5) + j; }
+
+constexpr bool operand_places_invert_indices() {      // (every third entry: each field of an entry still takes all its values)
+    for (int e = 0; e < kW1opFloats; e += 3) {
+        const W1opPlace p = w1op_place(e);
+        if (w1op_index(p.net, p.row, p.col) != e) return false;
+    }
+    for (int e = 0; e < kOpLayer; e += 3) {
+        const int m = e & 15, lane = (e >> 4) & 63, kb = (e >> 10) & 3, jb = e >> 12, j = op_j(jb, lane), k = op_k(kb, lane, m);
+        if (op_index(1, 2, 0, j, k) != op_at(1, 2, 0, jb, kb, lane, m) || op_index(1, 2, 1, k, j) != op_at(1, 2, 1, jb, kb, lane, m)) return false;
+    }
+    for (int e = 0; e < 4 * kOp3Ks * 64 * 8; e += 3) {
+        const int j = e & 7, lane = (e >> 3) & 63, ks = (e >> 9) & 7, cb = e >> 12, n = op3_n(cb, lane), k = op3_k(ks, lane, j);
+        if (op3_index(1, 2, 0, n, k) != op3_at(op3_slot(1, 2, 0), cb, ks, 0, lane, j) || op3_index(1, 2, 1, k, n) != op3_at(op3_slot(1, 2, 1), cb, ks, 0, lane, j)) return false;
+    }
+    return true;
+}
+static_assert(operand_places_invert_indices(), "an operand copy's inverse map must undo its index");
+
+// What the optimizer launch needs to refresh K7w's copies: where it drops an updated weight so that the next K7w launch needs no
+// prepare pass.  wop == nullptr: nothing to refresh.
 struct WideCopies {
-    int w[2][3];       // float offsets of the hidden layers' weights in the bucket
+    int w[2][MAXL];    // float offsets of the hidden layers' weights in the bucket
     int NL, Hd, D;
     float* wop;
-    unsigned short* wop3;   // != nullptr: k_mlpw3_step's bf16-plane copies are the ones to refresh (mlp_wide.hip: w3::wop_index)
+    unsigned short* wop3;   // != nullptr: k_mlpw3_step's bf16-plane copies are the ones to refresh
 };
 // next_idx != nullptr: the launch also forms the next minibatch's advantage partial sums (stats: (kStatBlocks, 2) doubles).
 int launch_adam_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int n_params, const double* sq_part,

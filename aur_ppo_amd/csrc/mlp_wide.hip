@@ -22,8 +22,7 @@
 #include <stdlib.h>
 
 #pragma clang fp contract(fast)
-#include "bf16x3.h"
-#include "mlp_common.h"
+#include "mlp_bf3.h"
 
 using namespace aurppo_mlp;
 
@@ -31,10 +30,6 @@ namespace {
 
 constexpr int HPW = 128;            // widest (padded) layer
 constexpr int LDW = HPW + 1;        // LDS row stride of an activation matrix (odd: conflict-free row- and column-wise)
-constexpr int MAXL = 3;             // hidden layers
-constexpr int kOpBlk = 64 * 16;     // floats of one 32x32 block in operand order: [lane][16 k-steps]
-constexpr int kOpLayer = 16 * kOpBlk;                 // 4 x 4 blocks
-constexpr int kOpFloats = 2 * MAXL * 2 * kOpLayer;    // [net][layer][fwd | bwd]
 constexpr int kMaxSlabs = 2 * kMaxGrid;               // k_mlp_reduce folds up to 512
 
 struct WideLayout {   // float offsets into the flat parameter / gradient bucket; layer NL is the head
@@ -69,8 +64,7 @@ struct WideArgs {
 };
 
 // stats[b] = partial (sum, sum of squares) of the minibatch's advantages; wop = every hidden layer of both nets in
-// operand order.  Forward copy, block (ob, kb): lane l, step m holds W[ob*32 + (l & 31)][kb*32 + 2m + (l >> 5)]
-// (B[k][j] = W[j][k]); backward copy, block (jb, kb): W[kb*32 + 2m + (l >> 5)][jb*32 + (l & 31)] (B[k][j] = W[k][j]).
+// operand order (mlp_common.h: op_at / op_index), walked entry by entry so that the padding is zero without a clearing pass.
 __global__ __launch_bounds__(256) void k_mlpw_prep(const float* __restrict__ params, WideLayout L, int NL, int D, int Hd,
                                                    float* __restrict__ wop, const float4* __restrict__ rec, int rec_stride,
                                                    const int32_t* __restrict__ idx, int M, double (*__restrict__ stats)[2],
@@ -90,6 +84,7 @@ __global__ __launch_bounds__(256) void k_mlpw_prep(const float* __restrict__ par
     }
     const int b = blockIdx.x - n_stat_blocks, nb = gridDim.x - n_stat_blocks;
     for (int e = b * 256 + threadIdx.x; e < kOpFloats; e += nb * 256) {
+        // (the entry number's own fields: e = op_at(n, l, dir, hi, kb, lane, m))
         const int m = e & 15, lane = (e >> 4) & 63, blk = (e >> 10) & 15, dir = (e >> 14) & 1, nl = e >> 15;
         const int n = nl / MAXL, l = nl - n * MAXL;
         if (l >= NL || (dir == 1 && l == 0)) continue;
@@ -98,18 +93,23 @@ __global__ __launch_bounds__(256) void k_mlpw_prep(const float* __restrict__ par
         const int hi = blk >> 2, kb = blk & 3;
         int row, col;
         if (dir == 0) {
-            row = hi * 32 + (lane & 31);
-            col = kb * 32 + 2 * m + (lane >> 5);
+            row = op_j(hi, lane);
+            col = op_k(kb, lane, m);
         } else {
-            row = kb * 32 + 2 * m + (lane >> 5);
-            col = hi * 32 + (lane & 31);
+            row = op_k(kb, lane, m);
+            col = op_j(hi, lane);
         }
         wop[e] = (row < Hd && col < in_dim) ? W[row * in_dim + col] : 0.0f;
     }
 }
+static_assert(op_at(0, 0, 0, 0, 0, 0, 1) == 1 && op_at(0, 0, 0, 0, 0, 1, 0) == 16 && op_at(0, 0, 0, 0, 1, 0, 0) == (1 << 10) &&
+              op_at(0, 0, 0, 1, 0, 0, 0) == (4 << 10) && op_at(0, 0, 1, 0, 0, 0, 0) == (1 << 14) && op_at(0, 1, 0, 0, 0, 0, 0) == (1 << 15) &&
+              op_at(1, 0, 0, 0, 0, 0, 0) == (MAXL << 15), "k_mlpw_prep reads an entry's fields out of its number");
 
+// this lane's 16 steps of block (hi, kb) of copy (net, l, dir) = wop + op_at(net, l, dir, hi, kb, lane, 0), taken in three pointer steps:
+// the step kernels' address code was tuned in this form, and one combined offset compiles to other instructions in all of them
 __device__ __forceinline__ const float* op_block(const float* wop, int net, int l, int dir, int hi, int kb, int lane) {
-    return wop + (size_t)((net * MAXL + l) * 2 + dir) * kOpLayer + (hi * 4 + kb) * kOpBlk + lane * 16;
+    return wop + op_copy(net, l, dir) + op_entry(hi, kb, 0, 0) + op_entry(0, 0, lane, 0);
 }
 
 __device__ __forceinline__ void load_b(float (&b)[16], const float* p) {
@@ -313,11 +313,7 @@ __global__ __launch_bounds__(256, DUAL ? 2 : 1) void k_mlpw_step(const WideArgs 
         const double ts = block_sum<kThreads / kWave>(sm, s_red[0]);
         const double tq = block_sum<kThreads / kWave>(q, s_red[1]);
         if (tid == 0) {
-            const double m = ts / (double)a.h.M;
-            double var = (tq - ts * m) / (double)(a.h.M - 1);
-            if (var < 0.0) var = 0.0;
-            s_mean = (float)m;
-            s_std = (float)sqrt(var);
+            adv_mean_std(ts, tq, a.h.M, s_mean, s_std);
         }
     }
     __syncthreads();
@@ -675,15 +671,6 @@ constexpr int kFPlaneW = HPW * kFRow;            // F image of 128 features: byt
 constexpr int kXHalf = 3 * kXPlane;              // one 64-column X image (three planes)
 constexpr int kW3RowW = 2 * HPW, kW3PlaneW = AP * kW3RowW;       // W3 image [a 16][i 128]
 constexpr int kDoRowW = 64, kDoPlaneW = AP * kDoRowW;            // dOut image [a 16][s 32]
-constexpr int kWopKs = 8;                        // k-steps of a weight slice (128 / 16)
-constexpr int kWopSlice = kWopKs * 3 * 512;      // bf16 elements of one (slot, column block) slice
-constexpr int kWopSlot = 4 * kWopSlice;          // one (net, layer, direction)
-constexpr int kWopElems = 2 * MAXL * 2 * kWopSlot;
-__device__ __host__ __forceinline__ int wop_slot(int net, int l, int dir) { return (net * MAXL + l) * 2 + dir; }
-// element (slot, column block cb, k-step ks, plane p, lane, j)
-__device__ __host__ __forceinline__ int wop_index(int slot, int cb, int ks, int p, int lane, int j) {
-    return slot * kWopSlot + cb * kWopSlice + ((ks * 3 + p) * 64 + lane) * 8 + j;
-}
 
 // byte offsets of the workgroup's LDS
 constexpr int oX = 0;                                  // [2 halves][3 planes][4 KB]
@@ -706,40 +693,6 @@ constexpr int kBytes = oStageA + 4 * R * 16;
 static_assert(oH % 16 == 0 && oW3 % 16 == 0 && oDo % 16 == 0 && oOut % 16 == 0 && oRec % 16 == 0, "16-byte alignment of the images");
 static_assert(kBytes <= 160 * 1024, "one workgroup per CU");
 
-template <int PL>
-__device__ __forceinline__ Frag3 f_rows_p(const char* img, int f0, int ks, int lane) {      // (addresses as in bf16x3.h: lane part + k-step constant)
-    const int o = (foff(lane & 31, 8 * (lane >> 5)) ^ (ks << 5)) + f0 * kFRow;
-    Frag3 f;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * PL + o);
-    return f;
-}
-template <int PL>
-__device__ __forceinline__ Frag3 f_cols_p(const char* img, int ks, int lane) {
-    const TrLane t = tr_lane32(lane);
-    const int o0 = foff(t.kq, t.m0) + 16 * ks * kFRow, o1 = foff(t.kq + 4, t.m0) + 16 * ks * kFRow;
-    Frag3 r;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * PL + o0), lds_tr(img + p * PL + o1));
-    return r;
-}
-template <int PL>
-__device__ __forceinline__ Frag3 f_cols16_p(const char* img, int s0, int ks, int lane) {
-    const TrLane t = tr_lane16(lane);
-    const int o0 = foff(t.kq, s0 + t.m0) + 32 * ks * kFRow, o1 = foff(t.kq + 4, s0 + t.m0) + 32 * ks * kFRow;
-    Frag3 r;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) r.p[p] = join_tr(lds_tr(img + p * PL + o0), lds_tr(img + p * PL + o1));
-    return r;
-}
-template <int PL>
-__device__ __forceinline__ Frag3 f_rows16_p(const char* img, int f0, int lane) {
-    const int o = foff(f0 + (lane & 15), 8 * (lane >> 4));
-    Frag3 f;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) f.p[p] = lds_b128(img + p * PL + o);
-    return f;
-}
 // LDS-DMA: 16 / 4 bytes per lane from global memory straight into LDS at dst + lane * 16 / 4 (wave-uniform dst), no registers
 __device__ __forceinline__ void dma16(const void* src, void* dst_wave_uniform) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -760,51 +713,9 @@ __device__ __forceinline__ float row16_max(float v) {
     for (int m = 8; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 16));
     return v;
 }
-// tanh(acc + bias) of a 32x32 block into an F image, four values (one 8-byte store per plane) at a time
-// (om[e] = 1 - tanh^2 of the same element stays in registers for the backward pass, as in k_mlp_step3: joined again from the image's
-// planes it cost three unpacks and two adds per value and twelve LDS reads per block)
-template <int PL>
-__device__ __forceinline__ void tanh_store_p(char* img, int f0, const f32x16& acc, float bias, int lane, float (&om)[16]) {
-    const int f = f0 + (lane & 31), h = lane >> 5;
-    const float bc = bias * kTanhC;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-        unsigned a0, a1, a2, b0, b1, b2;
-        const float t0 = tanh_fast_fma(acc[4 * gq + 0], bc), t1 = tanh_fast_fma(acc[4 * gq + 1], bc);
-        const float t2 = tanh_fast_fma(acc[4 * gq + 2], bc), t3 = tanh_fast_fma(acc[4 * gq + 3], bc);
-        om[4 * gq + 0] = 1.0f - t0 * t0; om[4 * gq + 1] = 1.0f - t1 * t1;
-        om[4 * gq + 2] = 1.0f - t2 * t2; om[4 * gq + 3] = 1.0f - t3 * t3;
-        split3(t0, t1, a0, a1, a2);
-        split3(t2, t3, b0, b1, b2);
-        const int o = foff(f, 4 * h) ^ (gq << 4);       // = foff(f, 8 gq + 4 h)
-        *reinterpret_cast<u32x2*>(img + 0 * PL + o) = u32x2{a0, b0};
-        *reinterpret_cast<u32x2*>(img + 1 * PL + o) = u32x2{a1, b1};
-        *reinterpret_cast<u32x2*>(img + 2 * PL + o) = u32x2{a2, b2};
-    }
-}
-// dZ = dH * (1 - h^2), (1 - h^2) from the forward pass's registers, written over the block of h in the image; returns the lane's column sum
-template <int PL>
-__device__ __forceinline__ float dz_from_regs_p(char* img, int f0, const f32x16& dh, const float (&om)[16], int lane) {
-    const int f = f0 + (lane & 31), h = lane >> 5;
-    float colsum = 0.0f;
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-        const float d0 = dh[4 * gq + 0] * om[4 * gq + 0], d1 = dh[4 * gq + 1] * om[4 * gq + 1];
-        const float d2 = dh[4 * gq + 2] * om[4 * gq + 2], d3 = dh[4 * gq + 3] * om[4 * gq + 3];
-        colsum += (d0 + d1) + (d2 + d3);
-        unsigned a0, a1, a2, b0, b1, b2;
-        split3(d0, d1, a0, a1, a2);
-        split3(d2, d3, b0, b1, b2);
-        const int o = foff(f, 4 * h) ^ (gq << 4);       // = foff(f, 8 gq + 4 h)
-        *reinterpret_cast<u32x2*>(img + 0 * PL + o) = u32x2{a0, b0};
-        *reinterpret_cast<u32x2*>(img + 1 * PL + o) = u32x2{a1, b1};
-        *reinterpret_cast<u32x2*>(img + 2 * PL + o) = u32x2{a2, b2};
-    }
-    return colsum;
-}
 }  // namespace w3
 
-// wop3 = the bf16 planes of every hidden layer of both nets in operand order (w3::wop_index), written destination-first so
+// wop3 = the bf16 planes of every hidden layer of both nets in operand order (mlp_common.h: op3_at / op3_index), written destination-first so
 // that the padding (rows >= Hd, columns >= the layer's input width) is zero without a clearing pass.  The first n_stat_blocks
 // workgroups form the advantage partial sums instead (as k_mlpw_prep).
 __global__ __launch_bounds__(256) void k_mlpw3_prep(const float* __restrict__ params, WideLayout L, int NL, int D, int Hd,
@@ -825,23 +736,22 @@ __global__ __launch_bounds__(256) void k_mlpw3_prep(const float* __restrict__ pa
         return;
     }
     const int b = blockIdx.x - n_stat_blocks, nb = gridDim.x - n_stat_blocks;
-    constexpr int per_slot = 4 * w3::kWopKs * 512;     // plane-0 elements of one slot
-    for (int e = b * 256 + threadIdx.x; e < 2 * MAXL * 2 * per_slot; e += nb * 256) {
+    for (int e = b * 256 + threadIdx.x; e < kOp3Elems / 3; e += nb * 256) {      // every (slot, cb, ks, lane, j)
         const int j = e & 7, lane = (e >> 3) & 63, ks = (e >> 9) & 7, cb = (e >> 12) & 3, slot = e >> 14;
         const int dir = slot & 1, nl = slot >> 1, n = nl / MAXL, l = nl - n * MAXL;
         if (l >= NL || (dir == 1 && l == 0)) continue;
         const int in_dim = l == 0 ? D : Hd;
         const float* W = params + L.w[n][l];
-        const int k = 16 * ks + 8 * (lane >> 5) + j, c = cb * 32 + (lane & 31);
+        const int k = op3_k(ks, lane, j), c = op3_n(cb, lane);
         // forward: B[k][n = out c] = W[c][k]; backward: B[k = out][n = in c] = W[k][c]
         const int row = dir == 0 ? c : k, col = dir == 0 ? k : c;
         const float v = (row < Hd && col < in_dim) ? W[row * in_dim + col] : 0.0f;
         unsigned p0, p1, p2;
         bf3::split3(v, 0.0f, p0, p1, p2);
-        const int at = w3::wop_index(slot, cb, ks, 0, lane, j);
+        const int at = op3_at(slot, cb, ks, 0, lane, j);
         wop3[at] = (unsigned short)p0;
-        wop3[at + 512] = (unsigned short)p1;
-        wop3[at + 1024] = (unsigned short)p2;
+        wop3[at + kOp3Plane] = (unsigned short)p1;
+        wop3[at + 2 * kOp3Plane] = (unsigned short)p2;
     }
 }
 
@@ -956,11 +866,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
         const double ts = block_sum<kThreads / kWave>(sm, s_red[0]);
         const double tq = block_sum<kThreads / kWave>(q, s_red[1]);
         if (tid == 0) {
-            const double m = ts / (double)a.h.M;
-            double var = (tq - ts * m) / (double)(a.h.M - 1);
-            if (var < 0.0) var = 0.0;
-            s_mean = (float)m;
-            s_std = (float)sqrt(var);
+            adv_mean_std(ts, tq, a.h.M, s_mean, s_std);
         }
     }
     __syncthreads();
@@ -990,13 +896,13 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
     // (a wave-uniform base in scalar registers + the lane's 32-bit byte offset + an immediate per fragment; written as 64-bit
     // vector addresses they are formed once, hoisted out of the tile loop and spilled -- every load then waits behind a scratch
     // reload: k_mlp_step3's lesson)
-    const char* const wbase0 = reinterpret_cast<const char*>(a.wop3) + 2 * (size_t)(cb * kWopSlice);
+    const char* const wbase0 = reinterpret_cast<const char*>(a.wop3) + 2 * (size_t)(cb * kOp3Slice);
     const char* wbase = wbase0;
     int lane16 = lane * 16;
     // (in two halves: k-steps 0..3 are requested one phase ahead and stay live across the epilogue and the barrier in between;
     // k-steps 4..7 are requested at the top of the phase that uses them, behind the first half's 24 matrix instructions -- held
     // whole, the 96 registers of a slice pushed the kernel's vector registers into scratch)
-    bf16x8 wreg[3 * kWopKs];
+    bf16x8 wreg[3 * kOp3Ks];
 #ifdef K7W_EXP_NO_WLOAD
     int n_loaded = 0, n_loaded_hi = 0;
 #endif
@@ -1006,12 +912,12 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
 #endif
         int wz = 0;
         asm volatile("" : "+s"(wz));          // (an opaque zero per request: the loads stay where they are asked for)
-        const char* m = wbase + wz + 2 * (size_t)(wop_slot(net, l, dir) * kWopSlot);
+        const char* m = wbase + wz + 2 * (size_t)(op3_slot(net, l, dir) * kOp3Slot);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
             if (ks < nks) {
 #pragma unroll
-                for (int p = 0; p < 3; ++p) wreg[3 * ks + p] = *reinterpret_cast<const bf16x8*>(m + (ks * 3 + p) * 1024 + lane16);
+                for (int p = 0; p < 3; ++p) wreg[3 * ks + p] = *reinterpret_cast<const bf16x8*>(m + (ks * 3 + p) * (2 * kOp3Plane) + lane16);
             }
     };
     auto load_w_hi = [&](int l, int dir, int nks) {       // second half
@@ -1020,12 +926,12 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
 #endif
         int wz = 0;
         asm volatile("" : "+s"(wz));
-        const char* m = wbase + wz + 2 * (size_t)(wop_slot(net, l, dir) * kWopSlot);
+        const char* m = wbase + wz + 2 * (size_t)(op3_slot(net, l, dir) * kOp3Slot);
 #pragma unroll
-        for (int ks = 4; ks < kWopKs; ++ks)
+        for (int ks = 4; ks < kOp3Ks; ++ks)
             if (ks < nks) {
 #pragma unroll
-                for (int p = 0; p < 3; ++p) wreg[3 * ks + p] = *reinterpret_cast<const bf16x8*>(m + (ks * 3 + p) * 1024 + lane16);
+                for (int p = 0; p < 3; ++p) wreg[3 * ks + p] = *reinterpret_cast<const bf16x8*>(m + (ks * 3 + p) * (2 * kOp3Plane) + lane16);
             }
     };
     auto wfrag = [&](int ks) {
@@ -1207,7 +1113,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                     load_w_hi(0, 0, nksD);
                     Frag3 f0 = x_rows(sX, 0, lc), f1 = f0;          // two fragment sets take turns (no copies between them)
 #pragma unroll
-                    for (int ks = 0; ks < kWopKs; ks += 2) {
+                    for (int ks = 0; ks < kOp3Ks; ks += 2) {
                         if (DK > 0 ? ks + 1 < DK : ks + 1 < nksD) f1 = x_rows(sX + ((ks + 1) >> 2) * kXHalf, (ks + 1) & 3, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (DK > 0 ? ks < DK : ks < nksD) acc = mma32x3(f0, wfrag(ks), acc);
@@ -1219,14 +1125,14 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                     }
                 } else {
                     load_w_hi(l, 0, nksH);
-                    Frag3 f0 = f_cols_p<kFPlaneW>(sH(l - 1), 0, lc), f1 = f0;
+                    Frag3 f0 = f_cols<kFPlaneW>(sH(l - 1), 0, lc), f1 = f0;
 #pragma unroll
-                    for (int ks = 0; ks < kWopKs; ks += 2) {
-                        if (FULL ? ks + 1 < HK : ks + 1 < nksH) f1 = f_cols_p<kFPlaneW>(sH(l - 1), ks + 1, lc);
+                    for (int ks = 0; ks < kOp3Ks; ks += 2) {
+                        if (FULL ? ks + 1 < HK : ks + 1 < nksH) f1 = f_cols<kFPlaneW>(sH(l - 1), ks + 1, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? ks < HK : ks < nksH) acc = mma32x3(f0, wfrag(ks), acc);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (FULL ? ks + 2 < HK : ks + 2 < nksH) f0 = f_cols_p<kFPlaneW>(sH(l - 1), ks + 2, lc);
+                        if (FULL ? ks + 2 < HK : ks + 2 < nksH) f0 = f_cols<kFPlaneW>(sH(l - 1), ks + 2, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? ks + 1 < HK : ks + 1 < nksH) acc = mma32x3(f1, wfrag(ks + 1), acc);
                         __builtin_amdgcn_sched_barrier(0);
@@ -1250,7 +1156,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 // the slice used next: the following layer's forward copy, or (behind the last layer) the top layer's backward copy
                 if (l + 1 < NL) load_w(l + 1, 0, nksH);
                 else if (NL > 1) load_w(NL - 1, 1, nksH);
-                tanh_store_p<kFPlaneW>(sH(l), cb * 32, acc, sB[l * HPW + cb * 32 + (ln & 31)], ln, om[l]);
+                tanh_store<kFPlaneW>(sH(l), cb * 32, acc, sB[l * HPW + cb * 32 + (ln & 31)], ln, om[l]);
             }
             WSUB(l == 0 ? 26 : 29);
             WBAR(1 + l);
@@ -1260,7 +1166,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
                 if (ks < nks2H)
-                    acc = mma16x3(f_cols16_p<kFPlaneW>(sH(NL - 1), 16 * cb, ks, ln),
+                    acc = mma16x3(f_cols16<kFPlaneW>(sH(NL - 1), 16 * cb, ks, ln),
                                   plain_rows(sW3, kW3RowW, kW3PlaneW, ln & 15, 32 * ks + 8 * (ln >> 4)), acc);
             const int col = ln & 15;
             const float bias = sB3[col];
@@ -1339,9 +1245,9 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
             {
                 const Frag3 da = plain_rows(sDo, kDoRowW, kDoPlaneW, ln & 15, 8 * (ln >> 4));
 #pragma unroll
-                for (int q = 0; q < 2; ++q) gW3[q] = mma16x3(da, f_rows16_p<kFPlaneW>(HL, cb * 32 + 16 * q, ln), gW3[q]);
+                for (int q = 0; q < 2; ++q) gW3[q] = mma16x3(da, f_rows16<kFPlaneW>(HL, cb * 32 + 16 * q, ln), gW3[q]);
             }
-            float colsum = dz_from_regs_p<kFPlaneW>(HL, cb * 32, acc, om[NL - 1], ln);
+            float colsum = dz_from_regs<kFPlaneW>(HL, cb * 32, acc, om[NL - 1], ln);
             colsum += __shfl_xor(colsum, 32, kWave);
             gb[NL - 1] += colsum;
         }
@@ -1356,16 +1262,16 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 int lc = ln;
                 asm volatile("" : "+v"(lc));
                 {   // dW_l: eight (k-step, out-block) products, the next one's dZ fragment (and the next k-step's H fragment) asked for first
-                    Frag3 hb0 = f_rows_p<kFPlaneW>(Hp, cb * 32, 0, lc), hb1 = hb0;
-                    Frag3 d0 = f_rows_p<kFPlaneW>(dZ, 0, 0, lc), d1 = d0;
+                    Frag3 hb0 = f_rows<kFPlaneW>(Hp, cb * 32, 0, lc), hb1 = hb0;
+                    Frag3 d0 = f_rows<kFPlaneW>(dZ, 0, 0, lc), d1 = d0;
 #pragma unroll
                     for (int q = 0; q < 8; q += 2) {            // q = 4 ks + ob
-                        if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) d1 = f_rows_p<kFPlaneW>(dZ, ((q + 1) & 3) * 32, (q + 1) >> 2, lc);
-                        if (q == 2) hb1 = f_rows_p<kFPlaneW>(Hp, cb * 32, 1, lc);
+                        if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) d1 = f_rows<kFPlaneW>(dZ, ((q + 1) & 3) * 32, (q + 1) >> 2, lc);
+                        if (q == 2) hb1 = f_rows<kFPlaneW>(Hp, cb * 32, 1, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? (q & 3) < HBK : (q & 3) < HB) gW[l][q & 3] = mma32x3(d0, q < 4 ? hb0 : hb1, gW[l][q & 3]);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (q + 2 < 8 && (FULL ? ((q + 2) & 3) < HBK : ((q + 2) & 3) < HB)) d0 = f_rows_p<kFPlaneW>(dZ, ((q + 2) & 3) * 32, (q + 2) >> 2, lc);
+                        if (q + 2 < 8 && (FULL ? ((q + 2) & 3) < HBK : ((q + 2) & 3) < HB)) d0 = f_rows<kFPlaneW>(dZ, ((q + 2) & 3) * 32, (q + 2) >> 2, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) gW[l][(q + 1) & 3] = mma32x3(d1, q < 4 ? hb0 : hb1, gW[l][(q + 1) & 3]);
                         __builtin_amdgcn_sched_barrier(0);
@@ -1373,14 +1279,14 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 }
                 f32x16 acc = zero16();
                 {
-                    Frag3 f0 = f_cols_p<kFPlaneW>(dZ, 0, lc), f1 = f0;
+                    Frag3 f0 = f_cols<kFPlaneW>(dZ, 0, lc), f1 = f0;
 #pragma unroll
-                    for (int ks = 0; ks < kWopKs; ks += 2) {
-                        if (FULL ? ks + 1 < HK : ks + 1 < nksH) f1 = f_cols_p<kFPlaneW>(dZ, ks + 1, lc);
+                    for (int ks = 0; ks < kOp3Ks; ks += 2) {
+                        if (FULL ? ks + 1 < HK : ks + 1 < nksH) f1 = f_cols<kFPlaneW>(dZ, ks + 1, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? ks < HK : ks < nksH) acc = mma32x3(f0, wfrag(ks), acc);
                         __builtin_amdgcn_sched_barrier(0);
-                        if (FULL ? ks + 2 < HK : ks + 2 < nksH) f0 = f_cols_p<kFPlaneW>(dZ, ks + 2, lc);
+                        if (FULL ? ks + 2 < HK : ks + 2 < nksH) f0 = f_cols<kFPlaneW>(dZ, ks + 2, lc);
                         __builtin_amdgcn_sched_barrier(0);
                         if (FULL ? ks + 1 < HK : ks + 1 < nksH) acc = mma32x3(f1, wfrag(ks + 1), acc);
                         __builtin_amdgcn_sched_barrier(0);
@@ -1388,7 +1294,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 }
                 if (l - 1 >= 1) load_w(l - 1, 1, nksH);
                 else load_w(0, 0, nksD);                    // layer 1's forward slice for the next tile
-                float colsum = dz_from_regs_p<kFPlaneW>(Hp, cb * 32, acc, om[l - 1], ln);
+                float colsum = dz_from_regs<kFPlaneW>(Hp, cb * 32, acc, om[l - 1], ln);
                 colsum += __shfl_xor(colsum, 32, kWave);
                 gb[l - 1] += colsum;
             }
@@ -1400,15 +1306,15 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
             int lc = ln;
             asm volatile("" : "+v"(lc));
             Frag3 xb0 = x_cols(sX + (cb >> 1) * kXHalf, 0, (cb & 1) * 32, lc), xb1 = xb0;
-            Frag3 d0 = f_rows_p<kFPlaneW>(dZ, 0, 0, lc), d1 = d0;
+            Frag3 d0 = f_rows<kFPlaneW>(dZ, 0, 0, lc), d1 = d0;
 #pragma unroll
             for (int q = 0; q < 8; q += 2) {
-                if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) d1 = f_rows_p<kFPlaneW>(dZ, ((q + 1) & 3) * 32, (q + 1) >> 2, lc);
+                if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) d1 = f_rows<kFPlaneW>(dZ, ((q + 1) & 3) * 32, (q + 1) >> 2, lc);
                 if (q == 2) xb1 = x_cols(sX + (cb >> 1) * kXHalf, 1, (cb & 1) * 32, lc);
                 __builtin_amdgcn_sched_barrier(0);
                 if (FULL ? (q & 3) < HBK : (q & 3) < HB) gW[0][q & 3] = mma32x3(d0, q < 4 ? xb0 : xb1, gW[0][q & 3]);
                 __builtin_amdgcn_sched_barrier(0);
-                if (q + 2 < 8 && (FULL ? ((q + 2) & 3) < HBK : ((q + 2) & 3) < HB)) d0 = f_rows_p<kFPlaneW>(dZ, ((q + 2) & 3) * 32, (q + 2) >> 2, lc);
+                if (q + 2 < 8 && (FULL ? ((q + 2) & 3) < HBK : ((q + 2) & 3) < HB)) d0 = f_rows<kFPlaneW>(dZ, ((q + 2) & 3) * 32, (q + 2) >> 2, lc);
                 __builtin_amdgcn_sched_barrier(0);
                 if (FULL ? ((q + 1) & 3) < HBK : ((q + 1) & 3) < HB) gW[0][(q + 1) & 3] = mma32x3(d1, q < 4 ? xb0 : xb1, gW[0][(q + 1) & 3]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1553,21 +1459,22 @@ struct WideWs {
     unsigned* tile_counter;   // [2] (+ padding to 64 B)
     float* slabs;        // (kMaxSlabs, n_params)
     double* sq_part;     // (ceil(n_params / 64)) clip partial sums left by k_mlp_reduce
-    unsigned short* wop3;   // k_mlpw3_step's bf16-plane operand copies (w3::kWopElems), behind everything else
+    unsigned short* wop3;   // k_mlpw3_step's bf16-plane operand copies (kOp3Elems), behind everything else
+    size_t bytes;           // aurppo_mlp_wide_workspace_bytes
 };
 // slabs a launch can write: two both-net workgroups per CU for the narrow shapes (small n_params), one pair per two CUs otherwise
 int wide_slab_cap(int hidden, int D) { return (hidden <= 64 && D <= 64) ? kMaxSlabs : kMaxGrid / 2; }
 WideWs wide_ws(void* workspace, int n_params, int slab_cap) {
+    WsCarver c(workspace);
     WideWs v;
-    char* p = reinterpret_cast<char*>(workspace);
-    v.stats = reinterpret_cast<double*>(p);
-    v.loss_part = v.stats + 2 * kStatBlocks;
-    v.wop = reinterpret_cast<float*>(v.loss_part + 8 * kMaxSlabs);
-    v.tile_counter = reinterpret_cast<unsigned*>(v.wop + kOpFloats);
-    v.slabs = reinterpret_cast<float*>(v.tile_counter + 16);
-    v.sq_part = reinterpret_cast<double*>(v.slabs + (((size_t)slab_cap * (size_t)n_params + 15) / 16) * 16);
-    v.wop3 = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(v.sq_part) +
-                                               ((sizeof(double) * (size_t)((n_params + 63) / 64) + 63) / 64) * 64);
+    v.stats = c.take<double>(sizeof(double) * 2 * kStatBlocks);
+    v.loss_part = c.take<double>(sizeof(double) * 8 * kMaxSlabs);
+    v.wop = c.take<float>(sizeof(float) * kOpFloats);
+    v.tile_counter = c.take<unsigned>(sizeof(unsigned) * 16);
+    v.slabs = c.take<float>(sizeof(float) * (size_t)slab_cap * (size_t)n_params, 64);
+    v.sq_part = c.take<double>(sizeof(double) * (size_t)((n_params + 63) / 64), 128);
+    v.wop3 = c.take<unsigned short>(sizeof(unsigned short) * (size_t)kOp3Elems, 64);
+    v.bytes = c.bytes;
     return v;
 }
 
@@ -1611,10 +1518,7 @@ int launch_wide(K kernel, bool* attr_done, int grid, size_t lds_bytes, hipStream
 extern "C" size_t aurppo_mlp_wide_workspace_bytes(int n_params, int hidden, int state_dim) {
     // the slab region is sized from the shape (512 slabs of a narrow policy's few parameters, 128 of a wide one's many: 52 MB
     // instead of 207 MB at 3 x 128 over 128 state floats); n_params = 0: the operand copies alone, all K8w needs
-    const size_t slabs = (size_t)wide_slab_cap(hidden, state_dim) * (size_t)(n_params > 0 ? n_params : 0);
-    return sizeof(double) * (2 * kStatBlocks + 8 * kMaxSlabs) + sizeof(float) * (size_t)kOpFloats + 64 +
-           sizeof(float) * slabs + 64 + sizeof(double) * (size_t)((n_params + 63) / 64) + 128 +
-           sizeof(unsigned short) * (size_t)w3::kWopElems + 64;
+    return wide_ws(nullptr, n_params > 0 ? n_params : 0, wide_slab_cap(hidden, state_dim)).bytes;
 }
 
 // Which kernel aurppo_mlp_wide_ppo_*_f32 launches for a net shape: 1 = k_mlpw_step<., true> (both nets per workgroup, fp32 MFMA:
@@ -1682,18 +1586,13 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
                                a.rec_stride, idx, M, reinterpret_cast<double (*)[2]>(wv.stats), sb, wv.tile_counter);
         AURPPO_LAUNCH_CHECK("k_mlpw_prep");
     }
-    static int cus_of[kMaxDevices] = {0};
-    const int dslot = aurppo_device_slot();
-    if (!cus_of[dslot]) {
-        hipDeviceProp_t prop;
-        AURPPO_HIP_TRY(hipGetDeviceProperties(&prop, dslot));
-        cus_of[dslot] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : kMaxGrid;
-    }
+    const int cus = aurppo_cu_count(kMaxGrid), dslot = aurppo_device_slot();
+    if (cus < 0) return cus;
     const int n_tiles = (M + R - 1) / R;
     // 8 CUs left to the side stream's shuffle kernels, as K7; a both-net workgroup is built to share its CU with a second one
     a.static_tiles = knobs.static_tiles ? 1 : 0;
     const int spare = knobs.k7_spare_cus >= 0 ? knobs.k7_spare_cus : 8;
-    int pairs = dual ? 2 * (cus_of[dslot] - spare) : (cus_of[dslot] - spare) / 2;
+    int pairs = dual ? 2 * (cus - spare) : (cus - spare) / 2;
     if (pairs > (dual ? kMaxSlabs : kMaxGrid / 2)) pairs = dual ? kMaxSlabs : kMaxGrid / 2;
     if (pairs > n_tiles) pairs = n_tiles;
     if (pairs < 1) pairs = 1;
@@ -1741,7 +1640,7 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
     if (rc != AURPPO_OK) return rc;
     WideCopies wc;
     for (int n = 0; n < 2; ++n)
-        for (int l = 0; l < 3; ++l) wc.w[n][l] = l < num_layers ? a.L.w[n][l] : n_params;
+        for (int l = 0; l < MAXL; ++l) wc.w[n][l] = l < num_layers ? a.L.w[n][l] : n_params;
     wc.NL = num_layers; wc.Hd = hidden; wc.D = D; wc.wop = wv.wop;
     wc.wop3 = bf3k ? wv.wop3 : nullptr;
     return launch_adam_tail(tail->params_rw, grads, tail->exp_avg, tail->exp_avg_sq, n_params, wv.sq_part, tail->max_norm,

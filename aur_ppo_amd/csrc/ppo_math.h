@@ -54,6 +54,16 @@ __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, fl
     return o;
 }
 
+// Mean and standard deviation (torch.std: over M - 1; M == 1 -> 0/0 = NaN, as there) of a minibatch's advantages from their sum and
+// sum of squares, formed in double: every kernel that normalises advantages folds the same partial sums with this.
+__device__ __forceinline__ void adv_mean_std(double ts, double tq, int M, float& mean, float& std) {
+    const double m = ts / (double)M;
+    double var = (tq - ts * m) / (double)(M - 1);
+    if (var < 0.0) var = 0.0;
+    mean = (float)m;
+    std = (float)sqrt(var);
+}
+
 static inline PpoHyper make_hyper(int M, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode) {
     PpoHyper p;
     p.M = M;

@@ -1,0 +1,107 @@
+"""Do two builds of the library compute the same BITS in the fused MLP kernels (K7, K7w, K8, K8w, their reduce / optimizer launches)?
+    AURPPO_LIB=<build> python tools/build_bitdiff.py run OUT.npz     (once per build, each in a process of its own)
+    python tools/build_bitdiff.py cmp A.npz B.npz                    (raw bytes of every array; exit 1 + the first that differs)
+`run` drives every build of the step (K7 ids 3, 2; K7w ids 1, 3, 2) with AURPPO_STATIC_TILES=1 (a fixed summation order; the
+counter-dealt order is not reproducible by construction) over the smallest shapes that reach every path, at M = 1, 65 and 70001, and
+stores gradient, scalars and the whole workspace after mlp_ppo_step; parameters, moments, norms, step count and workspace after two
+chained mlp_ppo_minibatch calls (the first names next_idx) and after mlp_ppo_grad + mlp_ppo_apply (K7); the mlp_act outputs.  The
+workspace is zero-filled before each sequence, so that bytes no kernel writes are equal across processes."""
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+# (layers, hidden, D, A, Gaussian head, packed records)
+K7_SHAPES = [(2, 64, 64, 6, True, False), (2, 64, 17, 3, True, False), (2, 64, 64, 12, True, True), (2, 64, 32, 5, False, False)]
+K7W_SHAPES = [(1, 64, 64, 6, True, False), (3, 64, 64, 6, True, False), (3, 128, 64, 6, True, False), (2, 128, 128, 16, True, False),
+              (1, 96, 64, 4, False, False)]
+MS, B = (1, 65, 70001), 71000
+
+
+def run(out_path):
+    os.environ["AURPPO_TEST_KNOBS"] = "1"       # the library re-reads its knobs on every call: one process runs every build
+    os.environ["AURPPO_STATIC_TILES"] = "1"
+    import torch
+    from aur_ppo_amd import _lib
+    if os.environ.get("AURPPO_LIB"):
+        _lib.LIB_PATH = os.environ["AURPPO_LIB"]
+    from aur_ppo_amd import hip_ops as H
+    from aur_ppo_amd.actor_critic import actor_critic
+    from aur_ppo_amd.flat import FlatBucket
+    lib, dev, out = _lib.load(), torch.device("cuda:0"), {}
+
+    def keep(key, **tensors):
+        torch.cuda.synchronize()
+        for name, t in tensors.items():
+            out[key + name] = t.detach().cpu().contiguous().view(-1).numpy().view(np.uint8).copy()
+
+    def case(tag, NL, Hd, D, A, cont, packed):
+        torch.manual_seed(1000 * NL + Hd + D + A)                       # CPU generator: the same inputs in every process
+        pol = actor_critic(D, (A,) if cont else A, Hd, NL, 0.0, cont)
+        with torch.no_grad():
+            for p in pol.parameters():
+                p.add_(0.05 * torch.randn_like(p))
+        bucket = FlatBucket(pol.to(dev).parameters())
+        lay = H.mlp_layout(pol, bucket)
+        assert lay is not None and lay["wide"] == tag.startswith("k7w"), (tag, lay)
+        n, nb, flat = lay["n_params"], bucket.flat_param.numel(), bucket.flat_param
+        obs = torch.randn(B, D).to(dev)
+        act = (torch.randn(B, A) if cont else torch.randint(0, A, (B,)).float()).to(dev)
+        rec = torch.stack([-1.0 + 0.3 * torch.randn(B), 2 * torch.randn(B), torch.randn(B), torch.randn(B)], 1).contiguous().to(dev)
+        perm, p0 = torch.randperm(B).int().to(dev), flat.clone()
+        if packed:
+            act, rec = None, H.pack_records(rec, act)
+        ws_bytes = lib.aurppo_mlp_wide_workspace_bytes(n, Hd, D) if lay["wide"] else lib.aurppo_mlp_workspace_bytes(n)
+        ws = H._workspace("mlp_wide" if lay["wide"] else "mlp", ws_bytes, dev)
+
+        def fresh():
+            flat.copy_(p0)
+            ws.zero_()
+            return (torch.zeros(nb, device=dev), torch.zeros(nb, device=dev), torch.zeros(nb, device=dev),
+                    torch.full((1,), 3e-3, device=dev), torch.zeros(1, device=dev), torch.zeros(2, 9, device=dev), torch.zeros(2, device=dev))
+
+        for M in MS:
+            key, pairs = f"{tag}/M{M}/", ((perm[:M].contiguous(), perm[M:2 * M].contiguous()), (perm[M:2 * M].contiguous(), None))
+            g, m, v, lr, t, sc, norms = fresh()
+            H.mlp_ppo_step(obs, act, rec, pairs[0][0], flat, lay, g, 0.2, 0.01, 0.5, True, 1, sc[0])
+            keep(key + "step/", grad=g, scalars=sc, ws=ws[:ws_bytes])
+            g, m, v, lr, t, sc, norms = fresh()
+            for k, (idx, nxt) in enumerate(pairs):
+                H.mlp_ppo_minibatch(obs, act, rec, idx, flat, lay, g, 0.2, 0.01, 0.5, True, 1, sc[k], m, v, lr, t, 0.5, (0.9, 0.999), 1e-5,
+                                    norms[k:k + 1], next_idx=nxt, chained=k > 0)
+            keep(key + "minibatch/", params=flat, exp_avg=m, exp_avg_sq=v, norms=norms, step=t, scalars=sc, ws=ws[:ws_bytes])
+            if not lay["wide"]:
+                g, m, v, lr, t, sc, norms = fresh()
+                for k, (idx, nxt) in enumerate(pairs):
+                    H.mlp_ppo_grad(obs, act, rec, idx, flat, lay, g, 0.2, 0.01, 0.5, True, 1, sc[k], t, chained=k > 0)
+                    H.mlp_ppo_apply(flat, g, m, v, lay, lr, t, 0.5, (0.9, 0.999), 1e-5, norms[k:k + 1], rec=rec, next_idx=nxt)
+                keep(key + "grad_apply/", params=flat, exp_avg=m, exp_avg_sq=v, norms=norms, step=t, scalars=sc, ws=ws[:ws_bytes])
+            fresh()
+            a_, lp_, v_ = H.mlp_act(obs[:M].contiguous(), (torch.randn(M, A) if cont else torch.rand(M)).to(dev), flat, lay)
+            keep(key + "act/", actions=a_, logp=lp_, value=v_)
+
+    for knob, shapes in (("AURPPO_K7_VARIANT", K7_SHAPES), ("AURPPO_K7W_VARIANT", K7W_SHAPES)):
+        for s in shapes:
+            dual = knob == "AURPPO_K7W_VARIANT" and lib.aurppo_k7w_kernel(s[1], s[2]) == 1     # K7w id 1: the knob does not matter
+            for variant in ("1",) if dual else ("3", "2"):
+                os.environ[knob] = variant
+                case(f"{'k7w' if 'K7W' in knob else 'k7'}-{variant}/{s[0]}x{s[1]}-D{s[2]}-A{s[3]}{'' if s[4] else 'c'}", *s)
+    np.savez(out_path, **out)
+    print(f"{len(out)} arrays, {sum(a.nbytes for a in out.values()) / 1e6:.0f} MB -> {out_path}")
+
+
+def cmp(path_a, path_b):
+    a, b = np.load(path_a), np.load(path_b)
+    if sorted(a.files) != sorted(b.files):
+        print("the two runs hold different arrays:", sorted(set(a.files) ^ set(b.files))[:5])
+        return 1
+    for k in a.files:
+        if not np.array_equal(a[k], b[k]):
+            bad = np.flatnonzero(a[k] != b[k]) if a[k].shape == b[k].shape else []
+            print(f"DIFFERENT: {k}: {len(bad)} of {a[k].size} bytes, the first at byte {bad[0] if len(bad) else '-'}")
+            return 1
+    print(f"identical: {len(a.files)} arrays")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(run(sys.argv[2]) if sys.argv[1] == "run" else cmp(sys.argv[2], sys.argv[3]))
