@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void k_loss(const float* __restrict__ new
             R = ret[i];
             vo = oldv[i];
         }
-        const PpoSample t = ppo_sample(newlogp[i], ol_, a_raw, newv[i], vo, R, mean, denom, invM, p.h);
+        const PpoSample t = ppo_sample<true>(newlogp[i], ol_, a_raw, newv[i], vo, R, mean, denom, invM, p.h);
         a_okl += (double)t.okl;
         a_kl += (double)t.kl;
         a_cf += (double)t.cf;

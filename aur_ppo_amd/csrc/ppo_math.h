@@ -1,6 +1,12 @@
 // Per-sample PPO loss terms and their gradients (src/ppo.py:225-264), shared by the stand-alone loss
 // kernel (loss.hip) and the fused MLP step (mlp.hip).  torch autograd conventions: max() ties split
 // 0.5/0.5, clamp passes gradient on the closed interval.
+//
+// Non-finite inputs.  fmaxf / fminf return the operand that is not NaN, torch.max / torch.clamp return NaN, and torch's
+// clamp backward SELECTS zero outside the interval where a product by 0 turns an infinite term into NaN.  ppo_sample<true>
+// (the per-op loss kernel, whose inputs come from any caller) follows torch in all three; on finite inputs it gives the
+// same bits as ppo_sample<false>.  The fused steps keep ppo_sample<false>: their log-prob and value are computed inside the
+// kernel from the parameters, so a NaN there means NaN parameters, which turn every output NaN anyway.
 #pragma once
 #include "common.h"
 
@@ -16,6 +22,12 @@ struct PpoSample {
     float pg, vl, okl, kl, cf;  // this sample's contribution to the (un-normalised) sums
 };
 
+// torch.max / torch.clamp on a NaN operand, and torch's clamp backward (a select, not a product by 0) -- ppo_sample<true> only
+__device__ __forceinline__ float ppo_nan_max(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+__device__ __forceinline__ float ppo_nan_clamp(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+__device__ __forceinline__ float ppo_select(float t, float in) { return in != 0.0f ? t : copysignf(0.0f, t); }
+
+template <bool NANPROP = false>
 __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, float a_raw, float v, float vo, float R,
                                                 float mean, float denom, float invM, const PpoHyper& p) {
     PpoSample o;
@@ -25,26 +37,28 @@ __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, fl
     o.okl = -lr;
     o.kl = (ratio - 1.0f) - lr;
     o.cf = (fabsf(ratio - 1.0f) > p.clip) ? 1.0f : 0.0f;
-    const float rc = fminf(fmaxf(ratio, p.lo), p.hi);
+    const float rc = NANPROP ? ppo_nan_clamp(ratio, p.lo, p.hi) : fminf(fmaxf(ratio, p.lo), p.hi);
     const float l1 = -an * ratio;
     const float l2 = -an * rc;
-    o.pg = fmaxf(l1, l2);
+    o.pg = NANPROP ? ppo_nan_max(l1, l2) : fmaxf(l1, l2);
     const float w1 = l1 > l2 ? 1.0f : (l1 == l2 ? 0.5f : 0.0f);
     const float inr = (ratio >= p.lo && ratio <= p.hi) ? 1.0f : 0.0f;
-    const float dpg = (w1 * (-an) + (1.0f - w1) * (-an) * inr) * invM;
+    const float dpg = NANPROP ? (w1 * (-an) + ppo_select((1.0f - w1) * (-an), inr)) * invM
+                              : (w1 * (-an) + (1.0f - w1) * (-an) * inr) * invM;
     o.g_logp = dpg * ratio;
     float dvl;
     if (p.vloss_mode == AURPPO_VLOSS_CLIPPED) {
         const float du = v - R;
         const float vu = du * du;
         const float dv = v - vo;
-        const float dcl = fminf(fmaxf(dv, -p.clip), p.clip);
+        const float dcl = NANPROP ? ppo_nan_clamp(dv, -p.clip, p.clip) : fminf(fmaxf(dv, -p.clip), p.clip);
         const float dc = (vo + dcl) - R;
         const float vc = dc * dc;
-        o.vl = fmaxf(vu, vc);
+        o.vl = NANPROP ? ppo_nan_max(vu, vc) : fmaxf(vu, vc);
         const float u1 = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
         const float inv = (dv >= -p.clip && dv <= p.clip) ? 1.0f : 0.0f;
-        dvl = (u1 * (2.0f * du) + (1.0f - u1) * (2.0f * dc) * inv) * (0.5f * invM);
+        dvl = NANPROP ? (u1 * (2.0f * du) + ppo_select((1.0f - u1) * (2.0f * dc), inv)) * (0.5f * invM)
+                      : (u1 * (2.0f * du) + (1.0f - u1) * (2.0f * dc) * inv) * (0.5f * invM);
     } else {
         const float du = v - (p.vloss_mode == AURPPO_VLOSS_RETURNS ? R : vo);
         o.vl = du * du;

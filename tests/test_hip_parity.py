@@ -260,6 +260,98 @@ def test_gather_full_size_permutation_roundtrip(H):
     assert torch.equal(g.sum(dim=1).sort().values, src.sum(dim=1).sort().values)
 
 
+# K3 under guards.  Every destination is a view into a larger buffer filled with a sentinel bit pattern, with at least 64 floats of guard
+# before the view and after row M - 1; both guards must come back bit-unchanged.  Indices lie in [0, B), with repeats, 0 and B - 1.
+_SENTINEL, _GUARD = 0x7FA5C3E1, 64
+
+
+def _gather_idx(rs, M, B):
+    idx = rs.randint(0, B, size=M).astype(np.int32)
+    if M >= 1:
+        idx[M - 1] = B - 1
+    if M >= 2:
+        idx[0] = 0
+    if M >= 4:
+        idx[M // 2] = idx[M // 2 - 1]                     # a repeat
+    assert M == 0 or (idx.min() >= 0 and idx.max() < B)
+    return idx
+
+
+def _guarded_gather(H, M, rows, src_off=None, dst_off=None, B=None):
+    """One ``H.gather`` of streams with ``rows`` floats per sample into guarded destinations.  ``src_off`` / ``dst_off``: per stream, how many
+    floats past a 16-byte boundary the source / destination starts (0: 16-byte aligned, 2: 8-byte, 1: 4-byte)."""
+    n = len(rows)
+    src_off, dst_off = src_off or [0] * n, dst_off or [0] * n
+    B = B or max(2 * M, 64)
+    rs = np.random.RandomState(M * 131 + sum(rows) + n)
+    srcs, bufs, outs = [], [], []
+    for r, so, do in zip(rows, src_off, dst_off):
+        base = dev(rs.standard_normal(B * r + 4).astype(np.float32))
+        s = base[so:so + B * r]
+        srcs.append(s.view(B, r) if r > 1 else s)
+        assert srcs[-1].data_ptr() % 16 == 4 * so
+        buf = torch.full((2 * _GUARD + 4 + M * r,), _SENTINEL, dtype=torch.int32, device="cuda")
+        o = buf[_GUARD + do:_GUARD + do + M * r].view(torch.float32)
+        outs.append(o.view(M, r) if r > 1 else o)
+        assert M == 0 or outs[-1].data_ptr() % 16 == 4 * do
+        bufs.append((buf, _GUARD + do, _GUARD + do + M * r))
+    idx_np = _gather_idx(rs, M, B)
+    idx = dev(idx_np) if M else torch.zeros(1, dtype=torch.int32, device="cuda")[:0]
+    return srcs, outs, bufs, idx
+
+
+def _check_guarded(srcs, outs, bufs, idx):
+    torch.cuda.synchronize()
+    for k, (s, o, (buf, lo, hi)) in enumerate(zip(srcs, outs, bufs)):
+        assert bool((buf[:lo] == _SENTINEL).all()), f"stream {k}: the guard before the view was written"
+        assert bool((buf[hi:] == _SENTINEL).all()), f"stream {k}: the guard after row M - 1 was written"
+        assert torch.equal(o.view(torch.int32), s[idx.long()].view(torch.int32)), f"stream {k}"
+
+
+@pytest.mark.parametrize("M,rows", [
+    # four to eight row streams: a second and a third launch; scalars ride the first launch only, one sits between the launch groups
+    (257, [64, 6, 3, 5]), (1000, [4, 2, 3, 8, 12, 16, 5, 7]), (33, [64, 1, 6, 3, 1, 5, 2]), (16384, [6, 3, 5, 2, 1, 1]),
+    # scalars only: k_gather<U, 0>
+    *[(M, rows) for M in (1, 255, 256, 257, 100000) for rows in ([1], [1, 1, 1, 1], [1] * 8)],
+    # rows wider than 64 chunks (the chunk loop, unroll 4 past 256 floats), M no multiple of the tile
+    (1, [128 * 128]), (5, [128 * 128]), (67, [128 * 128]), (37, [3 * 84 * 84, 1, 1]), (131, [1028]), (131, [1030]),
+    # around the tile-halving rule (M + rows - 1) / rows < 512
+    *[(M, [64, 6, 1, 1, 1, 1]) for M in (15, 16, 17, 8191, 8192, 8193)],
+])
+def test_gather_guarded_bit_exact(H, M, rows):
+    srcs, outs, bufs, idx = _guarded_gather(H, M, rows)
+    H.gather(idx, srcs, outs=outs)
+    _check_guarded(srcs, outs, bufs, idx)
+
+
+@pytest.mark.parametrize("rows,src_off,dst_off", [
+    ([64, 6, 8], [0, 0, 0], [2, 2, 2]),          # source 16-byte aligned, destination 8-byte: float4 rows go as float2
+    ([64, 6, 8], [2, 2, 2], [0, 0, 0]),          # the other way round
+    ([64, 6, 8], [0, 2, 0], [0, 0, 2]),          # a different chunk width per stream in one launch
+    ([6], [1], [0]),                             # rows of 6 from a 4-byte-aligned source: the float path
+    ([6, 64, 4, 2], [1, 0, 0, 0], [0, 1, 2, 0]),
+])
+@pytest.mark.parametrize("M", [1, 300])
+def test_gather_guarded_alignment_changes_the_chunk_width(H, M, rows, src_off, dst_off):
+    srcs, outs, bufs, idx = _guarded_gather(H, M, rows, src_off, dst_off)
+    H.gather(idx, srcs, outs=outs)
+    _check_guarded(srcs, outs, bufs, idx)
+
+
+def test_gather_of_zero_rows_touches_nothing(H):
+    """M = 0 through the C ABI with every pointer valid: returns without a launch, destinations and guards bit-unchanged."""
+    import ctypes as C
+    srcs, outs, bufs, _ = _guarded_gather(H, 4, [64, 1, 6])
+    idx = torch.zeros(4, dtype=torch.int32, device="cuda")
+    VP = C.c_void_p * 3
+    rc = H._lib.load().aurppo_gather_f32(C.c_void_p(idx.data_ptr()), 0, VP(*[s.data_ptr() for s in srcs]), VP(*[o.data_ptr() for o in outs]),
+                                         (C.c_int * 3)(64, 1, 6), 3, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    torch.cuda.synchronize()
+    for buf, _lo, _hi in bufs:
+        assert bool((buf == _SENTINEL).all())
+
+
 # ---------------------------------------------------------------------------------- K4 + K5
 def test_loss_golden_vs_reference_autograd(H):
     z = load("loss.npz")
