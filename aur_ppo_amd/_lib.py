@@ -20,7 +20,8 @@ SYMBOLS = (
     "aurppo_first_block_fwd_f32", "aurppo_first_block_bwd_f32", "aurppo_conv3x3_wop_bytes", "aurppo_conv3x3_f32", "aurppo_linear_f32", "aurppo_linear_bias_act_f32",
     "aurppo_linear_wgrad_ws_bytes", "aurppo_linear_wgrad_f32", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_f32",
     "aurppo_mlp_wide_workspace_bytes", "aurppo_mlp_wide_ppo_step_f32", "aurppo_mlp_wide_ppo_minibatch_f32",
-    "aurppo_mlp_wide_act_f32",
+    "aurppo_mlp_wide_act_f32", "aurppo_linear_rows_bias_act_f32", "aurppo_linear_wgrad_rows_f32", "aurppo_linear_dx_tanh_f32",
+    "aurppo_head_ppo_workspace_bytes", "aurppo_head_ppo_f32",
 )
 
 _lib = None
@@ -104,17 +105,26 @@ def load() -> C.CDLL:
     lib.aurppo_linear_wgrad_ws_bytes.argtypes = [C.c_longlong, i32, i32]
     lib.aurppo_linear_wgrad_ws_bytes.restype = C.c_size_t
     lib.aurppo_linear_wgrad_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
+    lib.aurppo_linear_rows_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, vp, vp]
+    lib.aurppo_linear_wgrad_rows_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
+    lib.aurppo_linear_dx_tanh_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
+    lib.aurppo_head_ppo_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.aurppo_head_ppo_f32.argtypes = ([vp] * 7 + [i32] * 4 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32, vp, vp, vp])
     lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
     lib.aurppo_conv3x3_wgrad_ws_bytes.restype = C.c_size_t
     lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + [vp, vp]
     lib.aurppo_clip_workspace_bytes.argtypes = [C.c_int64]
     lib.aurppo_clip_workspace_bytes.restype = C.c_size_t
     lib.aurppo_grad_norm_clip_f32.argtypes = [vp, C.c_int64, f64, vp, vp, vp]
+    # everything returns int except the error string and the size_t workspace plans (tests/test_abi_layered.py holds this list to the header)
+    sized = ("aurppo_loss_workspace_bytes", "aurppo_clip_workspace_bytes", "aurppo_mlp_workspace_bytes", "aurppo_conv3x3_wop_bytes",
+             "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
+             "aurppo_head_ppo_workspace_bytes")
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("aurppo_last_error", "aurppo_loss_workspace_bytes", "aurppo_clip_workspace_bytes",
-                        "aurppo_mlp_workspace_bytes", "aurppo_conv3x3_wop_bytes", "aurppo_linear_wgrad_ws_bytes",
-                        "aurppo_conv3x3_wgrad_ws_bytes"):
+        if name in sized:
+            fn.restype = C.c_size_t
+        elif name != "aurppo_last_error":
             fn.restype = i32
     _lib = lib
     return lib

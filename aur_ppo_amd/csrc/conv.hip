@@ -250,9 +250,14 @@ struct LinArgs {
     long long M;
     int K, N, n_mb;
     int act;                         // 0: none, 1: tanh (1 - 2 / (e^{2x} + 1), as the fused MLP steps form it)
+                                     // 2 (GATE builds): y = acc * (1 - h * h), tanh' of the layer below from its output h
+    const int32_t* rows;             // ROWS builds: (M,) lane row m reads x row rows[m] (the minibatch index); y stays in minibatch order
+    const float* h;                  // GATE builds: (M, N), read at the address the store uses
 };
 
-template <int NB>
+// ROWS (layer 0 of the layered PPO step, hip_ops.mlp_layered_step: x through the minibatch index) and GATE (its input gradients:
+// tanh' of the layer below in the epilogue) are template parameters, so the plain instantiations keep their instruction streams
+template <int NB, bool ROWS = false, bool GATE = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
     constexpr int kChunkBytes = kKC * NB * 3 * 1024;
     __shared__ __attribute__((aligned(16))) char s_b[2 * kChunkBytes];
@@ -269,7 +274,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
         m0[mb] = (((long long)mbq * 4 + w) * kMB + mb) * 32;
         const long long m = m0[mb] + (lane & 31);
         valid[mb] = m < a.M;
-        row[mb] = a.x + (size_t)(valid[mb] ? m : 0) * a.K + 8 * h;
+        if (ROWS) row[mb] = a.x + (size_t)(valid[mb] ? a.rows[m] : 0) * a.K + 8 * h;
+        else row[mb] = a.x + (size_t)(valid[mb] ? m : 0) * a.K + 8 * h;
     }
     const char* const wgrp = reinterpret_cast<const char*>(a.wop) + (size_t)(ng * NB) * KS * 3 * 1024;
     auto stage = [&](int kc, int buf) {
@@ -349,6 +355,13 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
                 for (int e = 0; e < 16; ++e) {
                     const long long r = m0[mb] + acc_row_c(e, lane);
                     float v = acc[mb][nb][e] + bv;
+                    if (GATE) {
+                        if (r < a.M) {
+                            const float hv = a.h[(size_t)r * a.N + col];
+                            a.y[(size_t)r * a.N + col] = v * (1.0f - hv * hv);
+                        }
+                        continue;
+                    }
                     if (a.act == 1) v = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * v) + 1.0f);
                     if (r < a.M) a.y[(size_t)r * a.N + col] = v;
                 }
@@ -368,8 +381,10 @@ struct WgradArgs {
     float* part;                     // (S, N, K)
     long long M;
     int N, K, rows_per_slice, n_tiles_n, n_tiles_k;
+    const int32_t* rows;             // ROWS builds: (M,) row m of the product reads x row rows[m]; dy stays in minibatch order
 };
 
+template <bool ROWS = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) char s_img[2 * 2 * 3 * kXPlane];      // [dY | X][64-column half][3 planes][32 rows x 128 B]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -401,7 +416,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArg
             const bool okr = r < m_hi;
             const bool oka = okr && n0 + c4 < a.N, okb = okr && k0 + c4 < a.K;      // (N and K are multiples of 4)
             const float4 va = *reinterpret_cast<const float4*>(a.dy + (oka ? (size_t)r * a.N + n0 + c4 : (size_t)0));
-            const float4 vb = *reinterpret_cast<const float4*>(a.x + (okb ? (size_t)r * a.K + k0 + c4 : (size_t)0));
+            const size_t xr = ROWS ? (size_t)(okb ? a.rows[r] : 0) : (size_t)r;
+            const float4 vb = *reinterpret_cast<const float4*>(a.x + (okb ? xr * a.K + k0 + c4 : (size_t)0));
             pa[u][0] = va.x; pa[u][1] = va.y; pa[u][2] = va.z; pa[u][3] = va.w;
             pb[u][0] = vb.x; pb[u][1] = vb.y; pb[u][2] = vb.z; pb[u][3] = vb.w;
             pok |= (oka ? 1u : 0u) << u;
@@ -752,7 +768,7 @@ extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int 
 // mode 1: y (M, K_w) = x (M, N_w) . w (N_w, K_w)         -- the gradient with respect to the input (x is dY); N_w a multiple of 16
 // wop_ws: aurppo_conv3x3_wop_bytes(product's K, product's N) / 9 bytes suffice; the same function's size is accepted.
 static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream);
+                       void* wop_ws, void* stream, const int32_t* rows = nullptr, const float* h = nullptr);
 
 extern "C" int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,
                                  void* stream) {
@@ -767,8 +783,24 @@ extern "C" int aurppo_linear_bias_act_f32(const float* x, const float* w, const 
     return linear_impl(x, w, bias, act, y, M, K_w, N_w, 0, wop_ws, stream);
 }
 
+// The same with lane row m reading x row rows[m] (rows == NULL: aurppo_linear_bias_act_f32): the K3 gather of the minibatch's
+// observations (src/ppo.py:219-220) rides in the first layer's product.  Every rows[m] must name a row of x.
+extern "C" int aurppo_linear_rows_bias_act_f32(const float* x, const int32_t* rows, const float* w, const float* bias, float* y,
+                                               long long M, int K_w, int N_w, int act, void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_rows_bias_act_f32: act %d", act);
+    return linear_impl(x, w, bias, act, y, M, K_w, N_w, 0, wop_ws, stream, rows);
+}
+
+// out (M, K_w) = (gz (M, N_w) . w (N_w, K_w)) * (1 - h * h), h (M, K_w): the input gradient of a hidden layer with tanh' of the
+// layer below in the epilogue (what autograd's mm + tanh_backward leave); out may be h itself.
+extern "C" int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const float* h, float* out, long long M, int K_w, int N_w,
+                                         void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(h, AURPPO_EINVAL, "aurppo_linear_dx_tanh_f32: null pointer");
+    return linear_impl(gz, w, nullptr, 2, out, M, K_w, N_w, 1, wop_ws, stream, nullptr, h);
+}
+
 static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream) {
+                       void* wop_ws, void* stream, const int32_t* rows, const float* h) {
     AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
     AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
     const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
@@ -782,7 +814,7 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     AURPPO_LAUNCH_CHECK("k_conv_prep");
     LinArgs a;
     a.x = x; a.wop = wop; a.y = y; a.M = M; a.K = K; a.N = N;
-    a.bias = bias; a.act = act;
+    a.bias = bias; a.act = act; a.rows = rows; a.h = h;
     const long long n_mb = (M + 32 * 4 * kMB - 1) / (32 * 4 * kMB);
     const int nblk = (N + 31) / 32;
     const int NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
@@ -790,7 +822,15 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     AURPPO_REQUIRE(n_mb * n_ng < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_f32: grid too large");
     a.n_mb = (int)n_mb;
     const dim3 g((unsigned)(n_mb * n_ng)), blk(kConvThreads);
-    if (NB == 4) hipLaunchKernelGGL(k_linear<4>, g, blk, 0, s, a);
+    if (h) {
+        if (NB == 4) hipLaunchKernelGGL((k_linear<4, false, true>), g, blk, 0, s, a);
+        else if (NB == 2) hipLaunchKernelGGL((k_linear<2, false, true>), g, blk, 0, s, a);
+        else hipLaunchKernelGGL((k_linear<1, false, true>), g, blk, 0, s, a);
+    } else if (rows) {
+        if (NB == 4) hipLaunchKernelGGL((k_linear<4, true, false>), g, blk, 0, s, a);
+        else if (NB == 2) hipLaunchKernelGGL((k_linear<2, true, false>), g, blk, 0, s, a);
+        else hipLaunchKernelGGL((k_linear<1, true, false>), g, blk, 0, s, a);
+    } else if (NB == 4) hipLaunchKernelGGL(k_linear<4>, g, blk, 0, s, a);
     else if (NB == 2) hipLaunchKernelGGL(k_linear<2>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(k_linear<1>, g, blk, 0, s, a);
     AURPPO_LAUNCH_CHECK("k_linear");
@@ -828,6 +868,11 @@ extern "C" size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K) {
 }
 // dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N and K multiples of 4, 16-byte aligned operands)
 extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream) {
+    return aurppo_linear_wgrad_rows_f32(dy, x, nullptr, dw, M, N, K, ws, stream);
+}
+// the same with row m of the product reading x row rows[m] (rows == NULL: the plain call); same slice rule, same workspace
+extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K,
+                                            void* ws, void* stream) {
     AURPPO_REQUIRE(dy && x && dw && ws, AURPPO_EINVAL, "aurppo_linear_wgrad_f32: null pointer");
     AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, AURPPO_ESHAPE,
                    "aurppo_linear_wgrad_f32: M=%lld N=%d K=%d (N, K multiples of 4)", M, N, K);
@@ -835,7 +880,7 @@ extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* d
                    "aurppo_linear_wgrad_f32: operands / workspace not 16-byte aligned");
     const int S0 = linear_wgrad_slices(M, N, K);
     WgradArgs a;
-    a.dy = dy; a.x = x; a.part = reinterpret_cast<float*>(ws); a.M = M; a.N = N; a.K = K;
+    a.dy = dy; a.x = x; a.part = reinterpret_cast<float*>(ws); a.M = M; a.N = N; a.K = K; a.rows = rows;
     const long long rps = ((M + S0 - 1) / S0 + 31) / 32 * 32;           // whole 32-row chunks per slice
     const long long S = (M + rps - 1) / rps;
     AURPPO_REQUIRE(S >= 1 && S <= S0 && rps < (1ll << 30), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: slice size");
@@ -845,7 +890,8 @@ extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* d
     const long long grid = (long long)a.n_tiles_n * a.n_tiles_k * S;
     AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_linear_wgrad, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+    if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+    else hipLaunchKernelGGL(k_linear_wgrad<false>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
     AURPPO_LAUNCH_CHECK("k_linear_wgrad");
     const long long n = (long long)N * K;
     hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, (int)S, n, dw);

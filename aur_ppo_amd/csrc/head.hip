@@ -1,0 +1,521 @@
+// K13: the heads of the MLP actor-critic, the action distribution, the PPO loss and their backward pass in one kernel -- the
+// part of a minibatch step (src/ppo.py:219-266) that sits between the last hidden layer of src/nets/nets.py:19-53 and the
+// loss, for the policies the fused steps K7 / K7w do not cover (hidden_dim > 128 or more than 128 state floats), whose
+// hidden layers run a layer at a time on k_linear / k_linear_wgrad (conv.hip).  It replaces, per minibatch: the two head
+// GEMMs (A and 1 columns), the Normal / Categorical log-prob and entropy (a dozen element-wise kernels), K4 + K5, and
+// autograd's backward of all of them down to the pre-activation of the last hidden layer.
+//
+// Memory bound (0.5 GB for 1.4 GFLOP at H = 256, M = 131 072), so: plain fp32 FMAs, no matrix pipe.
+//   * a row's H activations lie along TPR = pow2(H / 4) threads, 4 columns (one 16-byte load) each; a workgroup of 256 threads
+//     works on 256 / TPR rows at a time.  The (A + 1) x H head weights sit in LDS.  The A + 1 dot products of a row finish with
+//     a butterfly over the row's lanes (and, for TPR > 64, a fixed-order sum over its waves through LDS), which leaves the same
+//     bits in every lane: each lane then forms the row's loss terms itself (ppo_sample, ppo_math.h) -- no broadcast.
+//   * log-prob as torch forms it: -(z * z) / (2 * std * std) - logstd - log sqrt(2 pi), one division per element; the
+//     Categorical head through max-subtracted exponentials.
+//   * backward: gz = (d head . W) * (1 - h * h) is stored (gz may alias h: a thread reads its four h before it writes them);
+//     head weight / bias / logstd gradients and the column sums of gz (the last hidden layer's bias gradients) accumulate in
+//     registers over the rows of a thread, are summed over the workgroup's row groups in group order, and leave as one slab
+//     per workgroup.  k_head_fold sums the slabs in workgroup order (fp64 accumulator, rounded once) into the bucket's
+//     gradient and folds the nine scalars.  The grid depends on (M, H) only: two launches on the same inputs give the same bits.
+#include "mlp_common.h"
+
+namespace {
+
+constexpr int kHT = 256;             // threads per workgroup
+constexpr int kHeadMaxGrid = 512;
+constexpr int kHeadStat = 64;        // statistics workgroups (at most)
+constexpr int kSmall = 48;           // slab tail: d b_actor [16], d logstd [16], d b_critic [1] + padding
+constexpr float kHalfLog2Pi = 0.9189385332046727f;
+
+struct HeadArgs {
+    const float* hA;                 // (M, H) last hidden activations, minibatch order
+    const float* hC;
+    float* gzA;                      // (M, H) d loss / d pre-activation of the last hidden layer (may be hA / hC)
+    float* gzC;
+    const float* actions;            // (B, aw) or nullptr (packed records)
+    const float4* rec;               // (B, 4) {old_logp, adv, ret, old_v}; packed: (B, 16), the action row in floats 4..15
+    int rec_stride;                  // float4s per record: 1 or 4
+    int aw;                          // action floats per sample
+    const int32_t* idx;              // (M,)
+    const float* params;
+    int off_wa, off_ba, off_wc, off_bc, off_ls, off_bla, off_blc;
+    double (*stats)[2];              // (n_stat, 2)
+    int n_stat;
+    float* slabs;                    // (grid, slab_stride)
+    double* loss_part;               // (grid, 8)
+    int slab_stride;
+    int M, H, A, continuous, n_iter;
+    PpoHyper h;
+};
+
+__host__ __device__ constexpr int head_slab_floats(int H, int A) { return (A + 3) * H + kSmall; }
+
+__global__ __launch_bounds__(kHT) void k_head_stats(const float4* __restrict__ rec, int rec_stride, const int32_t* __restrict__ idx, int M,
+                                                    double (*__restrict__ stats)[2]) {
+    __shared__ double sc[2][kHT / kWave];
+    double s = 0.0, q = 0.0;
+    aurppo_mlp::adv_partial_sums(rec, rec_stride, idx, M, blockIdx.x * kHT + threadIdx.x, gridDim.x * kHT, s, q);
+    const double bs = block_sum<kHT / kWave>(s, sc[0]);
+    const double bq = block_sum<kHT / kWave>(q, sc[1]);
+    if (threadIdx.x == 0) {
+        stats[blockIdx.x][0] = bs;
+        stats[blockIdx.x][1] = bq;
+    }
+}
+
+// mean / std of the minibatch's advantages from the partial sums: the same order, so the same bits, in every workgroup of both kernels
+__device__ __forceinline__ void head_fold_stats(const double (*stats)[2], int n_stat, int M, double (*sc)[kHT / kWave], float* s_ms) {
+    double s = 0.0, q = 0.0;
+    for (int b = threadIdx.x; b < n_stat; b += kHT) {
+        s += stats[b][0];
+        q += stats[b][1];
+    }
+    const double ts = block_sum<kHT / kWave>(s, sc[0]);
+    const double tq = block_sum<kHT / kWave>(q, sc[1]);
+    if (threadIdx.x == 0) adv_mean_std(ts, tq, M, s_ms[0], s_ms[1]);
+    __syncthreads();
+}
+
+__device__ __forceinline__ float dot4(const float4 a, const float4 b) {
+    return __builtin_fmaf(a.w, b.w, __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x)));
+}
+__device__ __forceinline__ void fma4(float4& acc, float s, const float4 v) {
+    acc.x = __builtin_fmaf(s, v.x, acc.x);
+    acc.y = __builtin_fmaf(s, v.y, acc.y);
+    acc.z = __builtin_fmaf(s, v.z, acc.z);
+    acc.w = __builtin_fmaf(s, v.w, acc.w);
+}
+
+template <int TPR>      // threads per row: the power of two >= H / 4, 8 ... 256
+__global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
+    constexpr int GPW = kHT / TPR;                     // rows a workgroup works on at a time
+    constexpr int NWG = TPR > kWave ? TPR / kWave : 1;   // waves per row
+    constexpr int LW = TPR > kWave ? kWave : TPR;      // lanes of a wave on one row
+    extern __shared__ __attribute__((aligned(16))) float sW[];       // (A + 1, H): actor head rows, then the critic's
+    __shared__ __attribute__((aligned(16))) float s_red[kHT * 4];
+    __shared__ float s_small[kSmall];                  // b_actor [16], logstd [16], std * std [16]
+    __shared__ float s_part[2][kHT / kWave][20];
+    __shared__ float s_sm[32][kSmall];
+    __shared__ double s_loss[32][6];
+    __shared__ double s_dred[2][kHT / kWave];
+    __shared__ float s_ms[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = a.H, A = a.A;
+    head_fold_stats(a.stats, a.n_stat, a.h.M, s_dred, s_ms);
+    for (int e = tid; e < (A + 1) * H; e += kHT) sW[e] = e < A * H ? a.params[a.off_wa + e] : a.params[a.off_wc + (e - A * H)];
+    if (tid < 16) {
+        s_small[tid] = tid < A ? a.params[a.off_ba + tid] : 0.0f;
+        const float ls = (a.continuous && tid < A) ? a.params[a.off_ls + tid] : 0.0f;
+        const float sd = expf(ls);
+        s_small[16 + tid] = ls;
+        s_small[32 + tid] = sd * sd;
+    }
+    __syncthreads();
+    const float mean = s_ms[0], denom = s_ms[1] + 1e-8f;
+    const float invM = 1.0f / (float)a.h.M;
+    const float g_ent = -a.h.ent_coef * invM;
+    const float bc = a.params[a.off_bc];
+
+    const int g = tid / TPR, t = tid % TPR;
+    const int c0 = 4 * t;
+    const bool colok = c0 < H;
+    const int cw = colok ? c0 : 0;
+    const int G = (int)gridDim.x * GPW, gg = (int)blockIdx.x * GPW + g;
+    const float4 wc = *reinterpret_cast<const float4*>(sW + A * H + cw);
+    const float4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    float4 dWa[16], dWc = zero4, dblA = zero4, dblC = zero4;
+    float dba[16], dls[16], dbc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        dWa[k] = zero4;
+        dba[k] = dls[k] = 0.0f;
+    }
+    double l_pg = 0.0, l_vl = 0.0, l_ent = 0.0, l_okl = 0.0, l_kl = 0.0, l_cf = 0.0;
+
+    float4 na = zero4, nc = zero4;
+    int nsrc = 0;
+    auto fetch = [&](long long row) {
+        na = nc = zero4;
+        nsrc = 0;
+        if (row < a.M) {
+            nsrc = a.idx[row];
+            if (colok) {
+                na = *reinterpret_cast<const float4*>(a.hA + (size_t)row * H + c0);
+                nc = *reinterpret_cast<const float4*>(a.hC + (size_t)row * H + c0);
+            }
+        }
+    };
+    fetch(gg);
+    for (int it = 0; it < a.n_iter; ++it) {
+        const long long row = (long long)it * G + gg;
+        const bool valid = row < a.M;
+        const float4 ha = na, hc = nc;
+        const int src = nsrc;
+        // this row's record and action row: asked for here, used behind the dot products
+        float4 rc = zero4;
+        float actv[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) actv[k] = 0.0f;
+        if (valid) {
+            rc = a.rec[(size_t)src * a.rec_stride];
+            const float* ap = a.actions ? a.actions + (size_t)src * a.aw : reinterpret_cast<const float*>(a.rec) + (size_t)src * 16 + 4;
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < a.aw) actv[k] = ap[k];
+        }
+        fetch(row + G);
+
+        float p[17];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            p[k] = 0.0f;
+            if (k < A) p[k] = dot4(ha, *reinterpret_cast<const float4*>(sW + k * H + cw));
+        }
+        p[16] = dot4(hc, wc);
+#pragma unroll
+        for (int k = 0; k < 17; ++k) {
+            if (k < A || k == 16) {
+#pragma unroll
+                for (int off = LW / 2; off > 0; off >>= 1) p[k] += __shfl_xor(p[k], off, kWave);
+            }
+        }
+        if (NWG > 1) {
+            float* const mine = s_part[it & 1][wave];
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 17; ++k)
+                    if (k < A || k == 16) mine[k] = p[k];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 17; ++k) {
+                if (k < A || k == 16) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < NWG; ++w) s += s_part[it & 1][g * NWG + w][k];
+                    p[k] = s;
+                }
+            }
+        }
+        // ---- the row's loss terms (every lane of the row forms the same bits); p[k] becomes d loss / d head output k
+        float dv = 0.0f;
+        float dlr[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) dlr[k] = 0.0f;
+        if (valid) {
+            const float v_new = p[16] + bc;
+            PpoSample ts;
+            if (a.continuous) {
+                float logp = 0.0f, ent = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (k < A) {
+                        const float ls = s_small[16 + k], var = s_small[32 + k];
+                        const float z = actv[k] - (p[k] + s_small[k]);
+                        logp += (-(z * z) / (2.0f * var) - ls) - kHalfLog2Pi;
+                        ent += (0.5f + kHalfLog2Pi) + ls;
+                    }
+                }
+                ts = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (k < A) {
+                        const float var = s_small[32 + k];
+                        const float z = actv[k] - (p[k] + s_small[k]);
+                        p[k] = ts.g_logp * (z / var);
+                        dlr[k] = ts.g_logp * ((z * z) / var - 1.0f) + g_ent;
+                    }
+                }
+                l_ent += (double)ent;
+            } else {
+                float mx = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (k < A) {
+                        p[k] += s_small[k];
+                        mx = fmaxf(mx, p[k]);
+                    }
+                }
+                float se = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (k < A) se += expf(p[k] - mx);
+                const float lse = mx + logf(se);
+                const int ai = (int)actv[0];
+                float logp = 0.0f, ent = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (k < A) {
+                        const float lpk = p[k] - lse;
+                        ent -= expf(lpk) * lpk;
+                        if (k == ai) logp = lpk;
+                    }
+                }
+                ts = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    if (k < A) {
+                        const float lpk = p[k] - lse;
+                        const float pk = expf(lpk);
+                        p[k] = ts.g_logp * ((k == ai ? 1.0f : 0.0f) - pk) + g_ent * (-pk * (lpk + ent));
+                    }
+                }
+                l_ent += (double)ent;
+            }
+            dv = ts.g_v;
+            l_pg += (double)ts.pg;
+            l_vl += (double)ts.vl;
+            l_okl += (double)ts.okl;
+            l_kl += (double)ts.kl;
+            l_cf += (double)ts.cf;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) p[k] = 0.0f;
+        }
+        // ---- backward: gz of both nets for this thread's four columns, the register accumulators
+        float4 ga = zero4;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k < A) {
+                fma4(ga, p[k], *reinterpret_cast<const float4*>(sW + k * H + cw));
+                fma4(dWa[k], p[k], ha);
+                dba[k] += p[k];
+                dls[k] += dlr[k];
+            }
+        }
+        const float4 gza = {ga.x * (1.0f - ha.x * ha.x), ga.y * (1.0f - ha.y * ha.y), ga.z * (1.0f - ha.z * ha.z), ga.w * (1.0f - ha.w * ha.w)};
+        const float4 gzc = {(dv * wc.x) * (1.0f - hc.x * hc.x), (dv * wc.y) * (1.0f - hc.y * hc.y), (dv * wc.z) * (1.0f - hc.z * hc.z),
+                            (dv * wc.w) * (1.0f - hc.w * hc.w)};
+        if (valid && colok) {
+            *reinterpret_cast<float4*>(a.gzA + (size_t)row * H + c0) = gza;
+            *reinterpret_cast<float4*>(a.gzC + (size_t)row * H + c0) = gzc;
+            fma4(dWc, dv, hc);
+            dblA.x += gza.x; dblA.y += gza.y; dblA.z += gza.z; dblA.w += gza.w;
+            dblC.x += gzc.x; dblC.y += gzc.y; dblC.z += gzc.z; dblC.w += gzc.w;
+        }
+        dbc += dv;
+    }
+
+    // ---- hand over: the workgroup's row groups summed in group order, one slab per workgroup
+    float* const slab = a.slabs + (size_t)blockIdx.x * a.slab_stride;
+    auto emit = [&](const float4 v, int slab_off) {
+        __syncthreads();
+        reinterpret_cast<float4*>(s_red)[tid] = v;
+        __syncthreads();
+        if (g == 0 && colok) {
+            float4 s = reinterpret_cast<const float4*>(s_red)[t];
+#pragma unroll
+            for (int q = 1; q < GPW; ++q) {
+                const float4 o = reinterpret_cast<const float4*>(s_red)[q * TPR + t];
+                s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
+            }
+            *reinterpret_cast<float4*>(slab + slab_off + c0) = s;
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < A) emit(dWa[k], k * H);
+    emit(dWc, A * H);
+    emit(dblA, (A + 1) * H);
+    emit(dblC, (A + 2) * H);
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            s_sm[g][k] = dba[k];
+            s_sm[g][16 + k] = dls[k];
+            s_sm[g][32 + k] = k == 0 ? dbc : 0.0f;
+        }
+        s_loss[g][0] = l_pg; s_loss[g][1] = l_vl; s_loss[g][2] = l_ent; s_loss[g][3] = l_okl; s_loss[g][4] = l_kl; s_loss[g][5] = l_cf;
+    }
+    __syncthreads();
+    if (tid < kSmall) {
+        float s = 0.0f;
+        for (int q = 0; q < GPW; ++q) s += s_sm[q][tid];
+        slab[(A + 3) * H + tid] = s;
+    }
+    if (tid >= 64 && tid < 70) {
+        double s = 0.0;
+        for (int q = 0; q < GPW; ++q) s += s_loss[q][tid - 64];
+        a.loss_part[(size_t)blockIdx.x * 8 + (tid - 64)] = s;
+    }
+}
+
+// grads[...] = the slabs summed in workgroup order (eight runs of consecutive slabs, each summed in order in fp64, then the eight
+// in order; rounded once); the workgroup past the last folds the loss sums into the nine scalars (k_loss_final's arithmetic).
+__global__ __launch_bounds__(kHT) void k_head_fold(const HeadArgs a, int n_slabs, float* __restrict__ grads, float* __restrict__ out) {
+    __shared__ double s_run[8][32];
+    __shared__ double sc[6][kHT / kWave];
+    __shared__ float s_ms[2];
+    const int tid = threadIdx.x;
+    const int H = a.H, A = a.A;
+    const int n = head_slab_floats(H, A);
+    if (blockIdx.x == gridDim.x - 1) {
+        head_fold_stats(a.stats, a.n_stat, a.h.M, sc, s_ms);
+        double acc[6] = {0, 0, 0, 0, 0, 0};
+        for (int b = tid; b < n_slabs; b += kHT) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) acc[k] += a.loss_part[(size_t)b * 8 + k];
+        }
+        double r[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r[k] = block_sum<kHT / kWave>(acc[k], sc[k]);
+        if (tid == 0) {
+            const double M = (double)a.h.M;
+            const float pg = (float)(r[0] / M);
+            const float vl = 0.5f * (float)(r[1] / M);
+            const float ent = (float)(r[2] / M);
+            out[AURPPO_S_PG] = pg;
+            out[AURPPO_S_VL] = vl;
+            out[AURPPO_S_ENT] = ent;
+            out[AURPPO_S_OLD_KL] = (float)(r[3] / M);
+            out[AURPPO_S_KL] = (float)(r[4] / M);
+            out[AURPPO_S_CLIPFRAC] = (float)(r[5] / M);
+            out[AURPPO_S_LOSS] = (pg - a.h.ent_coef * ent) + vl * a.h.vf_coef;
+            out[AURPPO_S_ADV_MEAN] = s_ms[0];
+            out[AURPPO_S_ADV_STD] = s_ms[1];
+        }
+        return;
+    }
+    const int el = tid & 31, run = tid >> 5;
+    const int e = (int)blockIdx.x * 32 + el;
+    const int per = (n_slabs + 7) / 8;
+    const int lo = run * per, hi = lo + per < n_slabs ? lo + per : n_slabs;
+    double tsum = 0.0;
+    if (e < n) {
+        int s = lo;
+        for (; s + 4 <= hi; s += 4) {
+            float x[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = a.slabs[(size_t)(s + k) * a.slab_stride + e];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) tsum += (double)x[k];
+        }
+        for (; s < hi; ++s) tsum += (double)a.slabs[(size_t)s * a.slab_stride + e];
+    }
+    s_run[run][el] = tsum;
+    __syncthreads();
+    if (run != 0 || e >= n) return;
+    double total = 0.0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) total += s_run[q][el];
+    int dst = -1;
+    if (e < A * H) dst = a.off_wa + e;
+    else if (e < (A + 1) * H) dst = a.off_wc + (e - A * H);
+    else if (e < (A + 2) * H) dst = a.off_bla + (e - (A + 1) * H);
+    else if (e < (A + 3) * H) dst = a.off_blc + (e - (A + 2) * H);
+    else {
+        const int j = e - (A + 3) * H;
+        if (j < 16) dst = j < A ? a.off_ba + j : -1;
+        else if (j < 32) dst = (a.continuous && j - 16 < A) ? a.off_ls + (j - 16) : -1;
+        else if (j == 32) dst = a.off_bc;
+    }
+    if (dst >= 0) grads[dst] = (float)total;
+}
+
+int head_tpr(int H) {
+    int tpr = 8;
+    while (tpr * 4 < H) tpr *= 2;
+    return tpr;
+}
+// workgroups: eight rows per row group where the minibatch has them, at most kHeadMaxGrid -- a function of (M, H) only
+int head_grid(int M, int H) {
+    const int gpw = kHT / head_tpr(H);
+    long long g = ((long long)M + gpw * 8 - 1) / (gpw * 8);
+    if (g < 1) g = 1;
+    if (g > kHeadMaxGrid) g = kHeadMaxGrid;
+    return (int)g;
+}
+int head_slab_stride(int H, int A) { return (head_slab_floats(H, A) + 63) & ~63; }
+
+struct HeadWs {
+    double (*stats)[2];
+    double* loss_part;
+    float* slabs;
+    size_t bytes;
+};
+HeadWs head_carve(void* workspace, int M, int H, int A) {
+    aurppo_mlp::WsCarver c(workspace);
+    HeadWs w;
+    const int grid = head_grid(M, H);
+    w.stats = c.take<double[2]>(kHeadStat * 2 * sizeof(double));
+    w.loss_part = c.take<double>((size_t)grid * 8 * sizeof(double));
+    w.slabs = c.take<float>((size_t)grid * head_slab_stride(H, A) * sizeof(float), 64);
+    w.bytes = c.bytes;
+    return w;
+}
+bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
+
+}  // namespace
+
+extern "C" size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A) {
+    if (M <= 0 || !head_shape_ok(H, A, 1)) return 0;
+    return head_carve(nullptr, M, H, A).bytes;
+}
+
+extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                                   const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
+                                   int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                   int vloss_mode, float* out_scalars, void* workspace, void* stream) {
+    AURPPO_REQUIRE(hA && hC && gzA && gzC && rec && idx && params && layout_h && grads && out_scalars && workspace, AURPPO_EINVAL,
+                   "aurppo_head_ppo_f32: null pointer");
+    AURPPO_REQUIRE(M > 0, AURPPO_ESHAPE, "aurppo_head_ppo_f32: M=%d", M);
+    AURPPO_REQUIRE(head_shape_ok(H, A, continuous), AURPPO_ESHAPE,
+                   "aurppo_head_ppo_f32: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", H, A);
+    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "aurppo_head_ppo_f32: vloss_mode %d", vloss_mode);
+    const int aw = continuous ? A : 1;
+    AURPPO_REQUIRE(actions || aw <= 12, AURPPO_ESHAPE, "aurppo_head_ppo_f32: packed records hold at most 12 action floats (A=%d)", A);
+    AURPPO_REQUIRE(aligned_to(hA, 16) && aligned_to(hC, 16) && aligned_to(gzA, 16) && aligned_to(gzC, 16) && aligned_to(rec, 16) &&
+                       aligned_to(workspace, 64),
+                   AURPPO_EINVAL, "aurppo_head_ppo_f32: operands not 16-byte / workspace not 64-byte aligned");
+    HeadArgs a;
+    a.off_wa = layout_h[0]; a.off_ba = layout_h[1]; a.off_wc = layout_h[2]; a.off_bc = layout_h[3]; a.off_ls = layout_h[4];
+    a.off_bla = layout_h[5]; a.off_blc = layout_h[6];
+    const long long need[7] = {(long long)A * H, A, H, 1, continuous ? A : 0, H, H};
+    for (int i = 0; i < 7; ++i)
+        AURPPO_REQUIRE(layout_h[i] >= 0 && (long long)layout_h[i] + need[i] <= (long long)n_params, AURPPO_EINVAL,
+                       "aurppo_head_ppo_f32: layout offset %d (%d) outside the bucket of %d", i, layout_h[i], n_params);
+    const HeadWs w = head_carve(workspace, M, H, A);
+    a.hA = hA; a.hC = hC; a.gzA = gzA; a.gzC = gzC;
+    a.actions = actions; a.rec = reinterpret_cast<const float4*>(rec); a.rec_stride = actions ? 1 : 4; a.aw = aw;
+    a.idx = idx; a.params = params;
+    a.stats = w.stats; a.slabs = w.slabs; a.loss_part = w.loss_part;
+    a.slab_stride = head_slab_stride(H, A);
+    a.M = M; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0;
+    a.h = make_hyper(M, clip, ent_coef, vf_coef, norm_adv, vloss_mode);
+    const int tpr = head_tpr(H), gpw = kHT / tpr, grid = head_grid(M, H);
+    a.n_iter = (int)(((long long)M + (long long)grid * gpw - 1) / ((long long)grid * gpw));
+    int n_stat = (M + kHT * 4 - 1) / (kHT * 4);
+    if (n_stat > kHeadStat) n_stat = kHeadStat;
+    a.n_stat = n_stat;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_head_stats, dim3(n_stat), dim3(kHT), 0, s, a.rec, a.rec_stride, idx, M, w.stats);
+    AURPPO_LAUNCH_CHECK("k_head_stats");
+    const size_t lds = (size_t)(A + 1) * H * sizeof(float);
+    constexpr size_t kMaxLds = (size_t)17 * 1024 * sizeof(float);
+    static bool attr_set[kMaxDevices][6] = {};
+    const int dslot = aurppo_device_slot();
+#define AURPPO_HEAD_LAUNCH(T, SLOT)                                                                                              \
+    do {                                                                                                                         \
+        if (!attr_set[dslot][SLOT]) {                                                                                            \
+            AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_ppo<T>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                               (int)kMaxLds));                                                                   \
+            attr_set[dslot][SLOT] = true;                                                                                        \
+        }                                                                                                                        \
+        hipLaunchKernelGGL(k_head_ppo<T>, dim3(grid), dim3(kHT), lds, s, a);                                                     \
+    } while (0)
+    switch (tpr) {
+        case 8: AURPPO_HEAD_LAUNCH(8, 0); break;
+        case 16: AURPPO_HEAD_LAUNCH(16, 1); break;
+        case 32: AURPPO_HEAD_LAUNCH(32, 2); break;
+        case 64: AURPPO_HEAD_LAUNCH(64, 3); break;
+        case 128: AURPPO_HEAD_LAUNCH(128, 4); break;
+        default: AURPPO_HEAD_LAUNCH(256, 5); break;
+    }
+#undef AURPPO_HEAD_LAUNCH
+    AURPPO_LAUNCH_CHECK("k_head_ppo");
+    const int n = head_slab_floats(H, A);
+    hipLaunchKernelGGL(k_head_fold, dim3((n + 31) / 32 + 1), dim3(kHT), 0, s, a, grid, grads, out_scalars);
+    AURPPO_LAUNCH_CHECK("k_head_fold");
+    return AURPPO_OK;
+}

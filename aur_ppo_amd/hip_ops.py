@@ -286,17 +286,12 @@ MLP_HIDDEN, MLP_MAX_D, MLP_MAX_A = 64, 64, 16
 MLP_WIDE_MAX_HIDDEN, MLP_WIDE_MAX_D, MLP_WIDE_MAX_LAYERS = 128, 128, 3
 
 
-def mlp_layout(policy, bucket):
-    """Float offsets of ``policy`` (an ``actor_critic``: ``num_layers`` Tanh layers of ``hidden_dim``, src/nets/nets.py:19-53)
-    inside ``bucket``'s flat buffers, or None if no fused kernel is built for its shape.
-
-    The default shape (two layers of 64, D <= 64) gets K7/K8's layout {w1,b1,w2,b2,w3,b3} x {actor, critic} + actor_logstd;
-    every other shape up to three layers of 128 over D <= 128 gets K7w/K8w's (``wide=True``: {w_l, b_l} for l = 0..L per
-    net, then actor_logstd)."""
+def _mlp_structure(policy, bucket):
+    """(offsets, n_params, D, A, continuous, num_layers, hidden) of the reference's tanh actor-critic inside ``bucket``'s flat
+    buffers -- for the actor, then the critic: {w_l, b_l} for l = 0..L (layer L is the head), then actor_logstd -- or None if
+    ``policy`` is not that structure."""
     NL, Hd = getattr(policy, "num_layers", None), getattr(policy, "hidden_dim", None)
-    if not hasattr(policy, "continuous") or not isinstance(NL, int) or not isinstance(Hd, int):
-        return None
-    if not (1 <= NL <= MLP_WIDE_MAX_LAYERS and 1 <= Hd <= MLP_WIDE_MAX_HIDDEN):
+    if not hasattr(policy, "continuous") or not isinstance(NL, int) or not isinstance(Hd, int) or NL < 1 or Hd < 1:
         return None
     cont = bool(policy.continuous)
     off, pos = {}, 0
@@ -322,11 +317,46 @@ def mlp_layout(policy, bucket):
         return None
     if A > MLP_MAX_A or (not cont and A < 2):
         return None
+    return seq, pos, D, A, cont, NL, Hd
+
+
+def mlp_layout(policy, bucket):
+    """Float offsets of ``policy`` (an ``actor_critic``: ``num_layers`` Tanh layers of ``hidden_dim``, src/nets/nets.py:19-53)
+    inside ``bucket``'s flat buffers, or None if no fused kernel is built for its shape.
+
+    The default shape (two layers of 64, D <= 64) gets K7/K8's layout {w1,b1,w2,b2,w3,b3} x {actor, critic} + actor_logstd;
+    every other shape up to three layers of 128 over D <= 128 gets K7w/K8w's (``wide=True``: {w_l, b_l} for l = 0..L per
+    net, then actor_logstd)."""
+    st = _mlp_structure(policy, bucket)
+    if st is None:
+        return None
+    seq, pos, D, A, cont, NL, Hd = st
+    if not (1 <= NL <= MLP_WIDE_MAX_LAYERS and 1 <= Hd <= MLP_WIDE_MAX_HIDDEN):
+        return None
     # AURPPO_MLP_FORCE_WIDE=1 (diagnostic): the default shape through K7w too, for a same-box A/B of the two kernels
     fast = NL == 2 and Hd == MLP_HIDDEN and D <= MLP_MAX_D and os.environ.get("AURPPO_MLP_FORCE_WIDE") != "1"
     if not fast and D > MLP_WIDE_MAX_D:
         return None
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, wide=not fast)
+
+
+MLP_LAYERED_MAX_HIDDEN = 1024
+
+
+def mlp_layered_layout(policy, bucket):
+    """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
+    kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, a state of a
+    multiple of 16 floats, at most 16 actions.  Offsets as K7w's: {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no
+    device."""
+    if mlp_layout(policy, bucket) is not None:
+        return None
+    st = _mlp_structure(policy, bucket)
+    if st is None:
+        return None
+    seq, pos, D, A, cont, NL, Hd = st
+    if Hd % 32 != 0 or Hd > MLP_LAYERED_MAX_HIDDEN or D % 16 != 0:
+        return None
+    return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, layered=True)
 
 
 def k7_variant():
@@ -928,3 +958,149 @@ def first_block(obs, state, weight, bias):
     src/nets/base_cnns.py:28-31 on the input of src/models/robot_actor_critic.py:58-59 -- forward and backward without the
     full-resolution tensors.  ``weight``: (Co, Ci + 1, 3, 3), state plane last; Ci in 1..3, Co a multiple of 16."""
     return _FirstBlock.apply(obs, state, weight, bias)
+
+
+def linear_rows_bias_act(x, rows, w, bias, act=0):
+    """``act(x[rows] @ w.T + bias)`` without materialising ``x[rows]``: k_linear reads its rows through the int32 index."""
+    lib = _lib_or_raise()
+    x, w = x.contiguous(), w.contiguous()
+    M = rows.numel()
+    Nw, Kw = w.shape
+    y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
+    ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
+    _check(lib.aurppo_linear_rows_bias_act_f32(_ptr(x), _ptr(rows, torch.int32), _ptr(w), _optr(bias.contiguous() if bias is not None else None),
+                                               _ptr(y), M, Kw, Nw, int(act), C.c_void_p(ws.data_ptr()), _stream()),
+           "aurppo_linear_rows_bias_act_f32")
+    return y
+
+
+def linear_wgrad_rows(gy, x, rows):
+    """``gy.T @ x[rows]`` (k_linear_wgrad with its x operand read through the index)."""
+    lib = _lib_or_raise()
+    gy, x = gy.contiguous(), x.contiguous()
+    M, N = gy.shape
+    K = x.shape[1]
+    if rows.numel() != M:
+        raise ValueError("linear_wgrad_rows: one index per row of gy")
+    ws = _workspace("wgrad", lib.aurppo_linear_wgrad_ws_bytes(M, N, K), x.device)
+    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(gy), _ptr(x), _ptr(rows, torch.int32), _ptr(dw), M, N, K, C.c_void_p(ws.data_ptr()),
+                                            _stream()), "aurppo_linear_wgrad_rows_f32")
+    return dw
+
+
+def linear_dx_tanh(gz, w, h, out=None):
+    """``(gz @ w) * (1 - h * h)``: a hidden layer's input gradient with tanh' of the layer below in the product's epilogue.
+    ``out`` may be ``h``."""
+    lib = _lib_or_raise()
+    gz, w = gz.contiguous(), w.contiguous()
+    M = gz.shape[0]
+    Nw, Kw = w.shape
+    if out is None:
+        out = torch.empty((M, Kw), dtype=torch.float32, device=gz.device)
+    if h.shape != (M, Kw) or out.shape != (M, Kw) or gz.shape[1] != Nw:
+        raise ValueError("linear_dx_tanh: shape mismatch")
+    ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Nw, Kw), gz.device)
+    _check(lib.aurppo_linear_dx_tanh_f32(_ptr(gz), _ptr(w), _ptr(h), _ptr(out), M, Kw, Nw, C.c_void_p(ws.data_ptr()), _stream()),
+           "aurppo_linear_dx_tanh_f32")
+    return out
+
+
+# ------------------------------------------------------------------ K13 + the layered step
+def head_layout(layout):
+    """K13's seven offsets out of a layered (or K7w) layout: actor head w, b; critic head w, b; actor_logstd; the biases of the two last hidden layers."""
+    o, L = layout["offsets"], layout["num_layers"]
+    per = 2 * (L + 1)
+    return [o[2 * L], o[2 * L + 1], o[per + 2 * L], o[per + 2 * L + 1], o[2 * per], o[2 * L - 1], o[per + 2 * L - 1]]
+
+
+def head_ppo(hA, hC, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv=True,
+             vloss_mode=VLOSS_CLIPPED, out_scalars=None, gzA=None, gzC=None):
+    """K13: both heads, the action distribution, the PPO loss and their backward from the last hidden activations ``hA`` /
+    ``hC`` (M, H).  Writes ``gzA`` / ``gzC`` (default: in place of the activations), the heads', actor_logstd's and the last
+    hidden layers' bias gradients at their bucket offsets in ``flat_grad``, and returns the 9 scalars."""
+    lib = _lib_or_raise()
+    M, Hd = hA.shape
+    A, cont, n = layout["A"], layout.get("continuous", True), layout["n_params"]
+    gzA, gzC = hA if gzA is None else gzA, hC if gzC is None else gzC
+    if hC.shape != (M, Hd) or gzA.shape != (M, Hd) or gzC.shape != (M, Hd) or idx.numel() != M or Hd != layout["hidden"]:
+        raise ValueError("head_ppo: shape mismatch")
+    aw = A if cont else 1
+    B = rec.shape[0]
+    if (actions is None and rec.numel() != B * 16) or (actions is not None and (rec.numel() != B * 4 or actions.numel() != B * aw)):
+        raise ValueError("head_ppo: buffer shapes do not match the policy")
+    if min(flat_param.numel(), flat_grad.numel()) < n:
+        raise ValueError("head_ppo: the flat bucket is smaller than the policy")
+    if out_scalars is None:
+        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=hA.device)
+    nb = lib.aurppo_head_ppo_workspace_bytes(M, Hd, A)
+    if nb == 0:
+        raise RuntimeError("aur_ppo_amd: aurppo_head_ppo_f32 does not take this shape")
+    ws = _workspace("head", nb, hA.device)
+    lay = (C.c_int * 7)(*head_layout(layout))
+    _check(lib.aurppo_head_ppo_f32(_ptr(hA), _ptr(hC), _ptr(gzA), _ptr(gzC), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, Hd, A,
+                                   int(cont), _ptr(flat_param), lay, n, _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef),
+                                   int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars), C.c_void_p(ws.data_ptr()), _stream()),
+           "aurppo_head_ppo_f32")
+    return out_scalars
+
+
+_layered_cache = {}
+
+
+def _layered_buffers(M, layout, device):
+    """Activations of one minibatch, (M, hidden) per hidden layer and net, kept per (M, shape): a captured update replays into them."""
+    key = (M, layout["hidden"], layout["num_layers"], device.index if device.index is not None else torch.cuda.current_device())
+    buf = _layered_cache.get(key)
+    if buf is None:
+        buf = [[torch.empty((M, layout["hidden"]), dtype=torch.float32, device=device) for _ in range(layout["num_layers"])]
+               for _net in range(2)]
+        _layered_cache[key] = buf
+    return buf
+
+
+def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv=True,
+                     vloss_mode=VLOSS_CLIPPED, out_scalars=None):
+    """``mlp_ppo_step``'s contract for the MLP policies wider than the fused kernels (``mlp_layered_layout``): gather + evaluate +
+    loss + backward of one minibatch, overwriting ``flat_grad[:n_params]`` and returning the 9 scalars -- no autograd, no host
+    synchronisation.  Per net: layer 0 through the index (k_linear, bias + tanh in the epilogue), layers 1 .. L - 1, then K13
+    (heads, distribution, loss, their backward; its statistics and fold launches), then from the last layer down the weight
+    gradient (k_linear_wgrad, layer 0's x through the index), the input gradient with tanh' (k_linear) and the bias
+    gradient (a column sum)."""
+    lib = _lib_or_raise()
+    M, D, Hd, L, n = idx.numel(), layout["D"], layout["hidden"], layout["num_layers"], layout["n_params"]
+    if not layout.get("layered") or not _mlp_buffers_ok(obs, actions, rec, layout):
+        raise ValueError("mlp_layered_step: buffer shapes do not match the policy")
+    if min(flat_param.numel(), flat_grad.numel()) < n:
+        raise ValueError("mlp_layered_step: the flat bucket is smaller than the policy")
+    dev = obs.device
+    if out_scalars is None:
+        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=dev)
+    acts = _layered_buffers(M, layout, dev)
+    wop = C.c_void_p(_workspace("conv", lib.aurppo_conv3x3_wop_bytes(max(D, Hd), Hd), dev).data_ptr())
+    wgw = C.c_void_p(_workspace("wgrad", max(lib.aurppo_linear_wgrad_ws_bytes(M, Hd, D), lib.aurppo_linear_wgrad_ws_bytes(M, Hd, Hd)),
+                                dev).data_ptr())
+    st, off, per = _stream(), layout["offsets"], 2 * (L + 1)
+    p0, g0 = _ptr(flat_param).value, _ptr(flat_grad).value
+    obs_p, idx_p = _ptr(obs), _ptr(idx, torch.int32)
+
+    def at(base, o):
+        return C.c_void_p(base + 4 * o)
+    for net in range(2):
+        o, h = off[net * per:(net + 1) * per], acts[net]
+        _check(lib.aurppo_linear_rows_bias_act_f32(obs_p, idx_p, at(p0, o[0]), at(p0, o[1]), _ptr(h[0]), M, D, Hd, 1, wop, st),
+               "aurppo_linear_rows_bias_act_f32")
+        for l in range(1, L):
+            _check(lib.aurppo_linear_bias_act_f32(_ptr(h[l - 1]), at(p0, o[2 * l]), at(p0, o[2 * l + 1]), _ptr(h[l]), M, Hd, Hd, 1, wop, st),
+                   "aurppo_linear_bias_act_f32")
+    head_ppo(acts[0][L - 1], acts[1][L - 1], actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv,
+             vloss_mode, out_scalars)
+    for net in range(2):
+        o, h = off[net * per:(net + 1) * per], acts[net]        # h[l] now holds gz_l for l = L - 1; lower layers follow in place
+        for l in range(L - 1, 0, -1):
+            _check(lib.aurppo_linear_wgrad_f32(_ptr(h[l]), _ptr(h[l - 1]), at(g0, o[2 * l]), M, Hd, Hd, wgw, st), "aurppo_linear_wgrad_f32")
+            _check(lib.aurppo_linear_dx_tanh_f32(_ptr(h[l]), at(p0, o[2 * l]), _ptr(h[l - 1]), _ptr(h[l - 1]), M, Hd, Hd, wop, st),
+                   "aurppo_linear_dx_tanh_f32")
+            torch.sum(h[l - 1], 0, out=flat_grad[o[2 * l - 1]:o[2 * l - 1] + Hd])
+        _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(h[0]), obs_p, idx_p, at(g0, o[0]), M, Hd, D, wgw, st), "aurppo_linear_wgrad_rows_f32")
+    return out_scalars

@@ -58,6 +58,9 @@ class torch_buffer:
         return b_obs, b_logprobs, b_actions, b_advantages, b_returns, b_values
 
 
+LAYERED_STEP_DEFAULT = "0"      # AURPPO_LAYERED_STEP when the environment does not set it
+
+
 class ppo(FlatAdamMixin):
     """``ppo(params)`` as upstream (src/ppo.py:42-83).  Extra, optional ``params`` keys:
     ``obs_dim`` / ``act_dim`` / ``env_seed`` (Synthetic-* envs), ``log`` (False silences run logs),
@@ -142,6 +145,13 @@ class ppo(FlatAdamMixin):
         self._mlp = None
         if params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layout"):
             self._mlp = ops.mlp_layout(self.policy, self.bucket)
+        # MLP policies wider than the fused kernels: layer-at-a-time products + K13 in place of gather / evaluate / autograd in
+        # the update.  Opt-in (AURPPO_LAYERED_STEP=1) until it is timed against the per-op route on the bench shapes.
+        # ``_mlp`` stays None: rollout and bootstrap keep the torch modules.
+        self._mlp_layered = None
+        if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_layout")
+                and os.environ.get("AURPPO_LAYERED_STEP", LAYERED_STEP_DEFAULT) != "0"):
+            self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket)
         # the flat bucket holds the MLP policy and nothing else (up to alignment padding): K7 + clip + Adam can chain
         self._bucket_is_policy = self._mlp is not None and self.bucket.numel == self._mlp["n_params"]
         self._ro_state, self._ro_graph, self._ro_obs, self._ro_done, self._ro_out = 0, None, None, None, None   # captured rollout
@@ -476,6 +486,17 @@ class ppo(FlatAdamMixin):
                     ops.mlp_ppo_step(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp,
                                      self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
                                      self.norm_adv, vmode, self._scalars[step])
+                    D.allreduce_mean_(self.bucket.flat_grad, self.world, force=self._dp)
+                    if step == 0 and self.first_grad_probe is not None:
+                        self.first_grad_probe.append(self.bucket.flat_grad.detach().clone())
+                    self._clip_and_step(self._norms[step:step + 1])
+                    step += 1
+                    continue
+                if packed and self._mlp_layered is not None:
+                    # the layered step: rows through the permutation in the first product, the loss behind the last one
+                    ops.mlp_layered_step(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp_layered,
+                                         self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
+                                         self.norm_adv, vmode, self._scalars[step])
                     D.allreduce_mean_(self.bucket.flat_grad, self.world, force=self._dp)
                     if step == 0 and self.first_grad_probe is not None:
                         self.first_grad_probe.append(self.bucket.flat_grad.detach().clone())

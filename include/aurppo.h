@@ -273,6 +273,47 @@ int aurppo_linear_bias_act_f32(const float* x, const float* w, const float* bias
 size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K);
 int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream);
 
+/* The three products with what the layered PPO step (K13 below) needs riding in them.
+ *   aurppo_linear_rows_bias_act_f32: aurppo_linear_bias_act_f32 with lane row m reading x row rows[m] -- `b_obs[mb_inds]`
+ *     (src/ppo.py:219-220, the K3 gather) inside the first layer's product.  x (B, K_w), rows (M,) int32 with every entry in
+ *     [0, B); y (M, N_w) stays in minibatch order.  rows == NULL: exactly aurppo_linear_bias_act_f32.
+ *   aurppo_linear_wgrad_rows_f32: aurppo_linear_wgrad_f32 with the x operand read through the same index (dy is in minibatch
+ *     order already); same slice rule, same aurppo_linear_wgrad_ws_bytes(M, N, K).  rows == NULL: the plain call.
+ *   aurppo_linear_dx_tanh_f32: out (M, K_w) = (gz (M, N_w) . w (N_w, K_w)) * (1 - h * h), h (M, K_w) read at the address the
+ *     store uses (out may be h): autograd's `grad @ W` followed by tanh_backward of the layer below, src/nets/nets.py:21-27, in one
+ *     launch.  N_w a multiple of 16.
+ * Alignment, limits and wop_ws as aurppo_linear_f32. */
+int aurppo_linear_rows_bias_act_f32(const float* x, const int32_t* rows, const float* w, const float* bias, float* y, long long M,
+                                    int K_w, int N_w, int act, void* wop_ws, void* stream);
+int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K, void* ws,
+                                 void* stream);
+int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const float* h, float* out, long long M, int K_w, int N_w,
+                              void* wop_ws, void* stream);
+
+/* ---- K13: heads + distribution + PPO loss + their backward for the MLP policies the fused steps do not cover -------------
+ * For hidden_dim > 128 (or a state of more than 128 floats) the hidden layers of src/nets/nets.py:19-53 run a layer at a time
+ * on the products above; this call is everything between the last hidden activations and the loss of one minibatch
+ * (src/ppo.py:225-266): both heads' products, Normal(mean, exp(actor_logstd)) / Categorical(logits) log-prob and entropy
+ * (src/models/actor_critic.py:34-51), advantage normalisation, the clipped-surrogate / value / entropy loss, and the backward
+ * pass of all of it.  Three launches (advantage statistics, the kernel, a fixed-order fold); no floating-point atomics: two calls
+ * on the same inputs give the same bits.
+ *   hA, hC (M, H): the actor's / critic's last hidden activations (after tanh), minibatch order, 16-byte aligned.
+ *   gzA, gzC (M, H): d loss / d (pre-activation of the last hidden layer), tanh' folded in.  Each may be its h (in place).
+ *   actions / rec / idx: as aurppo_mlp_ppo_step_f32 -- (B, A) actions (Categorical: (B,) indices as floats) + (B, 4) records
+ *     {old_logp, adv, ret, old_v}, or actions == NULL and (B, 16) packed records (aurppo_pack_records_f32); both read
+ *     through idx (M,) int32.
+ *   params / grads: the flat bucket and its gradient (n_params floats); layout_h: 7 float offsets {actor head weight (A, H),
+ *     actor head bias, critic head weight (1, H), critic head bias, actor_logstd (ignored for the Categorical head), bias of the
+ *     actor's last hidden layer, bias of the critic's}.  Written in grads: both heads' weight and bias gradients, the
+ *     actor_logstd gradient, and the two last-hidden-layer bias gradients (the column sums of gz); nothing else.
+ *   out_scalars: the 9 floats of AURPPO_S_*.   workspace: aurppo_head_ppo_workspace_bytes(M, H, A) bytes, 64-byte aligned.
+ * Limits (AURPPO_ESHAPE otherwise): H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16; packed records A <= 12). */
+size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A);
+int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                        const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
+                        int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
+                        float* out_scalars, void* workspace, void* stream);
+
 /* K12 -- the weight gradient of the 3x3 convolution of aurppo_conv3x3_f32 (src/nets/base_cnns.py:32-45, src/nets/equiv.py:12-62;
  * what loss.backward() leaves in <conv>.weight.grad, src/robot_ppo.py:389): dw (Co, Ci, 3, 3) from x (B, Ci, H, W) and the
  * output gradient dy (B, Co, H + 2 pad - 2, W + 2 pad - 2), NCHW fp32, as a product over the batch's output pixels on bf16 MFMAs
