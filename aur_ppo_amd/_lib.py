@@ -1,4 +1,4 @@
-"""ctypes binding of libaurppo_hip.so (declarations mirror include/aurppo.h one to one)."""
+"""ctypes binding of libaurppo_hip.so: ``_declare`` mirrors include/aurppo.h one to one (tests/test_abi_signatures.py checks it)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,86 +45,98 @@ def load() -> C.CDLL:
     # inside one HIP runtime instance.
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, i32, f64 = C.c_void_p, C.c_int, C.c_double
-    lib.aurppo_version.restype = i32
-    lib.aurppo_last_error.restype = C.c_char_p
-    lib.aurppo_device_count.restype = i32
+    _declare(lib)
+    _lib = lib
+    return lib
+
+
+def _declare(lib):
+    """argtypes / restype of every symbol, in the header's order (tests/test_abi_signatures.py holds each one to its prototype in
+    include/aurppo.h).  The fused-step family shares long runs of same-typed arguments: each run is spelled once here, and
+    ``hip_ops`` builds the matching values with one helper per run (``_step_prefix``, ``_adam_tail``, ``_next_pair``, ``_rec_pair``)."""
+    vp, i32, i64, u32, f64, pi32 = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_double, C.POINTER(C.c_int)
+    ws_stream = [vp, vp]                                    # workspace, stream
+    loss_knobs = [f64, f64, f64, i32, i32]                  # clip, ent_coef, vf_coef, norm_adv, vloss_mode
+    adam_knobs = [f64, vp, vp, f64, f64, f64, vp]           # max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm
+    adam_tail = [vp, vp] + adam_knobs                       # exp_avg, exp_avg_sq, ...
+    next_pair = [vp, i32]                                   # next_idx, next_M
+    rec_pair = [vp, i32]                                    # rec, rec_floats
+
+    def step_prefix(shape_ints):
+        """obs, actions, rec, idx; M, D, A, continuous + hidden (1) or hidden, num_layers (2); params, layout_h, n_params; grads;
+        the loss knobs; out_scalars."""
+        return [vp] * 4 + [i32] * (4 + shape_ints) + [vp, pi32, i32, vp] + loss_knobs + [vp]
+
+    lib.aurppo_k7w_kernel.argtypes = [i32, i32]
+    # K1
     lib.aurppo_gae_f32.argtypes = [vp] * 7 + [i32, i32, f64, f64, i32, vp]
     lib.aurppo_gae_pack_f32.argtypes = [vp] * 9 + [i32, i32, f64, f64, i32, vp]
-    lib.aurppo_mt19937_create.argtypes = [C.POINTER(vp), C.c_uint32, i32, vp]
+    # K2
+    lib.aurppo_mt19937_create.argtypes = [C.POINTER(vp), u32, i32, vp]
     lib.aurppo_mt19937_destroy.argtypes = [vp]
-    lib.aurppo_mt19937_seed.argtypes = [vp, C.c_uint32, vp]
-    lib.aurppo_mt19937_get_state.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
-    lib.aurppo_mt19937_set_state.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32, vp]
+    lib.aurppo_mt19937_seed.argtypes = [vp, u32, vp]
+    lib.aurppo_mt19937_get_state.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_int32), vp]
+    lib.aurppo_mt19937_set_state.argtypes = [vp, C.POINTER(u32), C.c_int32, vp]
     lib.aurppo_mt19937_status_f32.argtypes = [vp, vp, vp]
     lib.aurppo_arange_i32.argtypes = [vp, i32, vp]
     lib.aurppo_shuffle_i32.argtypes = [vp, vp, i32, vp]
     lib.aurppo_shuffle_epochs_i32.argtypes = [vp, vp, i32, i32, vp]
-    lib.aurppo_gather_f32.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32, vp]
+    # K3
+    lib.aurppo_gather_f32.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), pi32, i32, vp]
+    # K4 + K5
     lib.aurppo_loss_workspace_bytes.argtypes = [i32]
-    lib.aurppo_loss_workspace_bytes.restype = C.c_size_t
-    lib.aurppo_loss_fwd_bwd_f32.argtypes = [vp] * 7 + [i32, f64, f64, f64, i32, i32] + [vp] * 6
-    lib.aurppo_loss_fwd_bwd_packed_f32.argtypes = [vp] * 4 + [i32, f64, f64, f64, i32, i32] + [vp] * 6
-    lib.aurppo_clip_adam_f32.argtypes = [vp] * 4 + [C.c_int64, C.c_int64, f64, vp, vp, f64, f64, f64, vp, vp, vp]
-    lib.aurppo_mlp_act_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.POINTER(i32), i32, vp, vp, vp, vp]
-    lib.aurppo_mlp_wide_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.aurppo_mlp_wide_workspace_bytes.restype = C.c_size_t
-    lib.aurppo_mlp_wide_ppo_step_f32.argtypes = ([vp] * 4 + [i32] * 6 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32] +
-                                                 [vp] * 5)
-    lib.aurppo_mlp_wide_ppo_minibatch_f32.argtypes = ([vp] * 4 + [i32] * 6 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32] +
-                                                      [vp, vp, vp, f64, vp, vp, f64, f64, f64, vp, vp, i32, i32, vp, vp])
-    lib.aurppo_mlp_wide_act_f32.argtypes = [vp, vp] + [i32] * 6 + [vp, C.POINTER(i32), i32] + [vp] * 5
+    lib.aurppo_loss_fwd_bwd_f32.argtypes = [vp] * 7 + [i32] + loss_knobs + [vp] * 4 + ws_stream
+    lib.aurppo_loss_fwd_bwd_packed_f32.argtypes = [vp] * 4 + [i32] + loss_knobs + [vp] * 4 + ws_stream
+    # K7 and its chained / two-halves forms
     lib.aurppo_mlp_workspace_bytes.argtypes = [i32]
-    lib.aurppo_mlp_workspace_bytes.restype = C.c_size_t
-    lib.aurppo_mlp_ppo_step_f32.argtypes = [vp] * 4 + [i32] * 5 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32, vp, vp, vp]
-    lib.aurppo_mlp_ppo_step_ev_f32.argtypes = lib.aurppo_mlp_ppo_step_f32.argtypes + [vp, vp]
-    lib.aurppo_mlp_ppo_grad_f32.argtypes = [vp] * 4 + [i32] * 5 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32, vp, vp, i32, vp, vp]
-    lib.aurppo_mlp_ppo_apply_f32.argtypes = [vp] * 4 + [C.POINTER(i32), i32, i32, f64, f64, vp, vp, f64, f64, f64, vp, vp, i32, vp, i32, vp, vp]
-    lib.aurppo_mlp_ppo_apply_parts_f32.argtypes = [vp] * 4 + [C.POINTER(i32), i32, i32, vp, i32, f64, vp, vp, f64, f64, f64, vp, vp, i32, vp, i32, vp, vp]
-    lib.aurppo_k7w_kernel.argtypes = [i32, i32]
+    lib.aurppo_mlp_ppo_step_f32.argtypes = step_prefix(1) + ws_stream
+    lib.aurppo_mlp_ppo_step_ev_f32.argtypes = step_prefix(1) + ws_stream + [vp, vp]
+    lib.aurppo_mlp_ppo_minibatch_f32.argtypes = step_prefix(1) + adam_tail + next_pair + [i32] + ws_stream
+    lib.aurppo_pack_records_f32.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.aurppo_mlp_ppo_grad_f32.argtypes = step_prefix(1) + [vp, i32] + ws_stream
+    lib.aurppo_mlp_ppo_apply_f32.argtypes = [vp] * 4 + [pi32, i32, i32, f64] + adam_knobs + rec_pair + next_pair + ws_stream
+    lib.aurppo_mlp_ppo_apply_parts_f32.argtypes = [vp] * 4 + [pi32, i32, i32, vp, i32] + adam_knobs + rec_pair + next_pair + ws_stream
+    # K11, the linear products, K13, K12
+    lib.aurppo_conv3x3_wop_bytes.argtypes = [i32, i32]
+    lib.aurppo_conv3x3_f32.argtypes = [vp, vp, vp] + [i32] * 7 + ws_stream
+    lib.aurppo_linear_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
+    lib.aurppo_linear_bias_act_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
+    lib.aurppo_linear_wgrad_ws_bytes.argtypes = [C.c_longlong, i32, i32]
+    lib.aurppo_linear_wgrad_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32] + ws_stream
+    lib.aurppo_linear_rows_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
+    lib.aurppo_linear_wgrad_rows_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32] + ws_stream
+    lib.aurppo_linear_dx_tanh_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32] + ws_stream
+    lib.aurppo_head_ppo_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.aurppo_head_ppo_f32.argtypes = [vp] * 7 + [i32] * 4 + [vp, pi32, i32, vp] + loss_knobs + [vp] + ws_stream
+    lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
+    lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
+    # the one-shot exchange
     lib.aurppo_p2p_parts.argtypes = [i32]
     lib.aurppo_p2p_create.argtypes = [C.POINTER(vp), i32, i32, i32, vp]
     lib.aurppo_p2p_get_handle.argtypes = [vp, vp]
     lib.aurppo_p2p_open_peers.argtypes = [vp, vp]
     lib.aurppo_p2p_allreduce_mean_f32.argtypes = [vp, vp, i32, vp, vp, f64, vp]
-    lib.aurppo_p2p_status.argtypes = [vp, C.POINTER(i32), vp]
+    lib.aurppo_p2p_status.argtypes = [vp, pi32, vp]
     lib.aurppo_p2p_destroy.argtypes = [vp]
-    lib.aurppo_pack_records_f32.argtypes = [vp, vp, i32, i32, vp, vp]
-    lib.aurppo_mlp_ppo_minibatch_f32.argtypes = ([vp] * 4 + [i32] * 5 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32, vp] +
-                                                 [vp, vp, f64, vp, vp, f64, f64, f64, vp, vp, i32, i32, vp, vp])
+    # K8, K7w / K8w
+    lib.aurppo_mlp_act_f32.argtypes = [vp, vp] + [i32] * 5 + [vp, pi32, i32, vp, vp, vp, vp]
+    lib.aurppo_mlp_wide_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.aurppo_mlp_wide_ppo_step_f32.argtypes = step_prefix(2) + ws_stream + [vp, vp]
+    lib.aurppo_mlp_wide_ppo_minibatch_f32.argtypes = step_prefix(2) + adam_tail + next_pair + [i32] + ws_stream
+    lib.aurppo_mlp_wide_act_f32.argtypes = [vp, vp] + [i32] * 6 + [vp, pi32, i32, vp, vp, vp] + ws_stream
+    # K6, K6b
+    lib.aurppo_clip_workspace_bytes.argtypes = [i64]
+    lib.aurppo_grad_norm_clip_f32.argtypes = [vp, i64, f64, vp] + ws_stream
+    lib.aurppo_clip_adam_f32.argtypes = [vp] * 4 + [i64, i64] + adam_knobs + ws_stream
+    # K9, K10
     lib.aurppo_bias_relu_pool2_fwd_f32.argtypes = [vp] * 6 + [i32] * 4 + [vp]
     lib.aurppo_bias_relu_pool2_bwd_f32.argtypes = [vp] * 4 + [i32] * 4 + [vp]
-    lib.aurppo_weighted_batch_sum_f32.argtypes = [vp, vp, vp, i32, C.c_int64, vp]
+    lib.aurppo_weighted_batch_sum_f32.argtypes = [vp, vp, vp, i32, i64, vp]
     lib.aurppo_first_block_fwd_f32.argtypes = [vp] * 6 + [i32] * 5 + [vp]
     lib.aurppo_first_block_bwd_f32.argtypes = [vp] * 6 + [i32] * 5 + [vp]
-    lib.aurppo_conv3x3_wop_bytes.argtypes = [i32, i32]
-    lib.aurppo_conv3x3_wop_bytes.restype = C.c_size_t
-    lib.aurppo_conv3x3_f32.argtypes = [vp, vp, vp] + [i32] * 7 + [vp, vp]
-    lib.aurppo_linear_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, i32, vp, vp]
-    lib.aurppo_linear_bias_act_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, i32, vp, vp]
-    lib.aurppo_linear_wgrad_ws_bytes.argtypes = [C.c_longlong, i32, i32]
-    lib.aurppo_linear_wgrad_ws_bytes.restype = C.c_size_t
-    lib.aurppo_linear_wgrad_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
-    lib.aurppo_linear_rows_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, vp, vp]
-    lib.aurppo_linear_wgrad_rows_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
-    lib.aurppo_linear_dx_tanh_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, vp, vp]
-    lib.aurppo_head_ppo_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.aurppo_head_ppo_f32.argtypes = ([vp] * 7 + [i32] * 4 + [vp, C.POINTER(i32), i32, vp, f64, f64, f64, i32, i32, vp, vp, vp])
-    lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
-    lib.aurppo_conv3x3_wgrad_ws_bytes.restype = C.c_size_t
-    lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + [vp, vp]
-    lib.aurppo_clip_workspace_bytes.argtypes = [C.c_int64]
-    lib.aurppo_clip_workspace_bytes.restype = C.c_size_t
-    lib.aurppo_grad_norm_clip_f32.argtypes = [vp, C.c_int64, f64, vp, vp, vp]
-    # everything returns int except the error string and the size_t workspace plans (tests/test_abi_layered.py holds this list to the header)
+    # everything returns int except the error string and the size_t workspace plans
     sized = ("aurppo_loss_workspace_bytes", "aurppo_clip_workspace_bytes", "aurppo_mlp_workspace_bytes", "aurppo_conv3x3_wop_bytes",
              "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
              "aurppo_head_ppo_workspace_bytes")
     for name in SYMBOLS:
-        fn = getattr(lib, name)
-        if name in sized:
-            fn.restype = C.c_size_t
-        elif name != "aurppo_last_error":
-            fn.restype = i32
-    _lib = lib
-    return lib
+        getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

@@ -64,6 +64,16 @@ def _workspace(kind, nbytes, device):
     return ws
 
 
+def _ws_stream(ws):
+    """workspace, stream: the two arguments most calls end with."""
+    return (C.c_void_p(ws.data_ptr()), _stream())
+
+
+def _loss_knobs(clip, ent_coef, vf_coef, norm_adv, vloss_mode):
+    """clip, ent_coef, vf_coef, norm_adv, vloss_mode."""
+    return (float(clip), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(vloss_mode))
+
+
 # ------------------------------------------------------------------ K1
 def gae(rewards, values, terminals, next_value, next_done, gamma, lam, mode=GAE, out=None, log_probs=None, rec=None):
     """``ppo.run_gae`` / ``normal_advantage`` (src/ppo.py:125-157).  Returns (returns, advantages).
@@ -192,6 +202,18 @@ def gather(idx, srcs, outs=None, probe=None):
 
 
 # ------------------------------------------------------------------ K4 + K5
+def _loss_call(lib, name, inputs, M, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars):
+    """The part ``loss_fwd_bwd`` and ``loss_fwd_bwd_packed`` share: everything but ``inputs``, the kernel's leading pointers."""
+    dev = inputs[0].device
+    if out_scalars is None:
+        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=dev)
+    g_lp, g_v, g_e = (torch.empty(M, dtype=torch.float32, device=dev) for _ in range(3))
+    ws = _workspace("loss", lib.aurppo_loss_workspace_bytes(M), dev)
+    _check(getattr(lib, name)(*[_ptr(t) for t in inputs], M, *_loss_knobs(clip, ent_coef, vf_coef, norm_adv, vloss_mode),
+                              _ptr(out_scalars), _ptr(g_lp), _ptr(g_v), _ptr(g_e), *_ws_stream(ws)), name)
+    return out_scalars, g_lp, g_v, g_e
+
+
 def loss_fwd_bwd(newlogp, oldlogp, adv, newv, oldv, ret, entropy, clip, ent_coef, vf_coef, norm_adv=True,
                  vloss_mode=VLOSS_CLIPPED, out_scalars=None):
     """src/ppo.py:225-264 forward and backward.  Returns (scalars[9], g_newlogp, g_newv, g_entropy)."""
@@ -200,16 +222,8 @@ def loss_fwd_bwd(newlogp, oldlogp, adv, newv, oldv, ret, entropy, clip, ent_coef
     for t in (oldlogp, adv, newv, oldv, ret, entropy):
         if t.numel() != M:
             raise ValueError(f"loss_fwd_bwd: expected {M} elements, got {t.numel()}")
-    dev = newlogp.device
-    if out_scalars is None:
-        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=dev)
-    g_lp, g_v, g_e = (torch.empty(M, dtype=torch.float32, device=dev) for _ in range(3))
-    ws = _workspace("loss", lib.aurppo_loss_workspace_bytes(M), dev)
-    _check(lib.aurppo_loss_fwd_bwd_f32(_ptr(newlogp), _ptr(oldlogp), _ptr(adv), _ptr(newv), _ptr(oldv), _ptr(ret),
-                                       _ptr(entropy), M, float(clip), float(ent_coef), float(vf_coef),
-                                       int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars), _ptr(g_lp), _ptr(g_v),
-                                       _ptr(g_e), C.c_void_p(ws.data_ptr()), _stream()), "aurppo_loss_fwd_bwd_f32")
-    return out_scalars, g_lp, g_v, g_e
+    return _loss_call(lib, "aurppo_loss_fwd_bwd_f32", (newlogp, oldlogp, adv, newv, oldv, ret, entropy), M, clip, ent_coef, vf_coef,
+                      norm_adv, vloss_mode, out_scalars)
 
 
 def loss_fwd_bwd_packed(newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, norm_adv=True, vloss_mode=VLOSS_CLIPPED,
@@ -219,32 +233,34 @@ def loss_fwd_bwd_packed(newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, no
     M = newlogp.numel()
     if newv.numel() != M or entropy.numel() != M or rec.numel() != 4 * M:
         raise ValueError("loss_fwd_bwd_packed: size mismatch")
-    dev = newlogp.device
-    if out_scalars is None:
-        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=dev)
-    g_lp, g_v, g_e = (torch.empty(M, dtype=torch.float32, device=dev) for _ in range(3))
-    ws = _workspace("loss", lib.aurppo_loss_workspace_bytes(M), dev)
-    _check(lib.aurppo_loss_fwd_bwd_packed_f32(_ptr(newlogp), _ptr(newv), _ptr(entropy), _ptr(rec), M, float(clip),
-                                              float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(vloss_mode),
-                                              _ptr(out_scalars), _ptr(g_lp), _ptr(g_v), _ptr(g_e),
-                                              C.c_void_p(ws.data_ptr()), _stream()), "aurppo_loss_fwd_bwd_packed_f32")
-    return out_scalars, g_lp, g_v, g_e
+    return _loss_call(lib, "aurppo_loss_fwd_bwd_packed_f32", (newlogp, newv, entropy, rec), M, clip, ent_coef, vf_coef, norm_adv,
+                      vloss_mode, out_scalars)
 
 
-class PPOLossPackedFn(torch.autograd.Function):
+class _PPOLossBase(torch.autograd.Function):
+    """``loss = ppo_loss(newlogp, newvalue, entropy, ...)`` with the reference's semantics; the
+    HIP kernel produces the three input gradients in the forward pass, backward only scales them."""
+
     @staticmethod
-    def forward(ctx, newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars):
-        sc, g_lp, g_v, g_e = loss_fwd_bwd_packed(newlogp.detach().contiguous(), newv.detach().reshape(-1).contiguous(),
-                                                 entropy.detach().contiguous(), rec, clip, ent_coef, vf_coef, norm_adv,
-                                                 vloss_mode, out_scalars)
+    def _run(ctx, fwd_bwd, n_inputs, newlogp, newv, entropy):
+        """``fwd_bwd(newlogp, newv, entropy)`` on detached flat inputs; keeps what backward needs.  ``n_inputs``: forward's."""
+        sc, g_lp, g_v, g_e = fwd_bwd(newlogp.detach().contiguous(), newv.detach().reshape(-1).contiguous(),
+                                     entropy.detach().contiguous())
         ctx.save_for_backward(g_lp, g_v, g_e)
-        ctx.v_shape = newv.shape
+        ctx.v_shape, ctx.n_no_grad = newv.shape, n_inputs - 3
         return sc[S_LOSS].clone()
 
     @staticmethod
     def backward(ctx, grad_out):
         g_lp, g_v, g_e = ctx.saved_tensors
-        return (g_lp * grad_out, (g_v * grad_out).view(ctx.v_shape), g_e * grad_out) + (None,) * 7
+        return (g_lp * grad_out, (g_v * grad_out).view(ctx.v_shape), g_e * grad_out) + (None,) * ctx.n_no_grad
+
+
+class PPOLossPackedFn(_PPOLossBase):
+    @staticmethod
+    def forward(ctx, newlogp, newv, entropy, rec, *knobs):
+        return _PPOLossBase._run(ctx, lambda nl, nv, en: loss_fwd_bwd_packed(nl, nv, en, rec, *knobs), 4 + len(knobs),
+                                 newlogp, newv, entropy)
 
 
 def ppo_loss_packed(newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, norm_adv=True, vloss_mode=VLOSS_CLIPPED,
@@ -252,25 +268,11 @@ def ppo_loss_packed(newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, norm_a
     return PPOLossPackedFn.apply(newlogp, newv, entropy, rec, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars)
 
 
-class PPOLossFn(torch.autograd.Function):
-    """``loss = ppo_loss(newlogp, newvalue, entropy, ...)`` with the reference's semantics; the
-    HIP kernel produces the three input gradients in the forward pass, backward only scales them."""
-
+class PPOLossFn(_PPOLossBase):
     @staticmethod
-    def forward(ctx, newlogp, newv, entropy, oldlogp, adv, oldv, ret, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
-                out_scalars):
-        nv = newv.reshape(-1)
-        sc, g_lp, g_v, g_e = loss_fwd_bwd(newlogp.detach().contiguous(), oldlogp, adv, nv.detach().contiguous(), oldv,
-                                          ret, entropy.detach().contiguous(), clip, ent_coef, vf_coef, norm_adv,
-                                          vloss_mode, out_scalars)
-        ctx.save_for_backward(g_lp, g_v, g_e)
-        ctx.v_shape = newv.shape
-        return sc[S_LOSS].clone()
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        g_lp, g_v, g_e = ctx.saved_tensors
-        return (g_lp * grad_out, (g_v * grad_out).view(ctx.v_shape), g_e * grad_out) + (None,) * 10
+    def forward(ctx, newlogp, newv, entropy, oldlogp, adv, oldv, ret, *knobs):
+        return _PPOLossBase._run(ctx, lambda nl, nv, en: loss_fwd_bwd(nl, oldlogp, adv, nv, oldv, ret, en, *knobs), 7 + len(knobs),
+                                 newlogp, newv, entropy)
 
 
 def ppo_loss(newlogp, newv, entropy, oldlogp, adv, oldv, ret, clip, ent_coef, vf_coef, norm_adv=True,
@@ -281,9 +283,8 @@ def ppo_loss(newlogp, newv, entropy, oldlogp, adv, oldv, ret, clip, ent_coef, vf
 
 # ------------------------------------------------------------------ K7
 MLP_HIDDEN, MLP_MAX_D, MLP_MAX_A = 64, 64, 16
-
-
 MLP_WIDE_MAX_HIDDEN, MLP_WIDE_MAX_D, MLP_WIDE_MAX_LAYERS = 128, 128, 3
+MLP_LAYERED_MAX_HIDDEN = 1024
 
 
 def _mlp_structure(policy, bucket):
@@ -340,9 +341,6 @@ def mlp_layout(policy, bucket):
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, wide=not fast)
 
 
-MLP_LAYERED_MAX_HIDDEN = 1024
-
-
 def mlp_layered_layout(policy, bucket):
     """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
     kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, a state of a
@@ -367,7 +365,7 @@ def k7_variant():
 def mlp_step_flops(layout, M):
     """Algorithmic FLOPs of one K7 / K7w launch (un-padded): forward of both nets, weight gradients of every
     layer, input gradients of every layer but the first (which needs none)."""
-    D, A, Hd, NL = layout["D"], layout["A"], layout.get("hidden", MLP_HIDDEN), layout.get("num_layers", 2)
+    D, A, Hd, NL = layout["D"], layout["A"], layout["hidden"], layout["num_layers"]
     total = 0
     for out in (A, 1):
         dims = [D] + [Hd] * NL + [out]
@@ -427,17 +425,72 @@ def pack_records(rec, actions, out=None):
 
 
 def _mlp_buffers_ok(obs, actions, rec, layout):
-    D, A = layout["D"], layout["A"]
-    aw = A if layout.get("continuous", True) else 1
-    if obs.shape[-1] != D:
+    """The one place that knows the record / action shape rule of the fused-step family: (B, 4) records beside (B, A) actions
+    ((B,) indices for the Categorical head), or ``actions=None`` and (B, 16) packed records (``pack_records``: at most 12 action
+    floats).  ``obs`` (B, D) gives B; K13 has no observations (``obs=None``) and counts the records' rows."""
+    aw = layout["A"] if layout["continuous"] else 1
+    if obs is None:
+        B = rec.shape[0]
+    elif obs.shape[-1] != layout["D"]:
         return False
-    if actions is None:                       # packed records
-        return aw <= 12 and rec.numel() == obs.shape[0] * 16
-    return actions.numel() == obs.shape[0] * aw and rec.numel() == obs.shape[0] * 4
+    else:
+        B = obs.shape[0]
+    if actions is None:
+        return aw <= 12 and rec.numel() == B * 16
+    return actions.numel() == B * aw and rec.numel() == B * 4
+
+
+def _bucket_fits(n, *tensors, who):
+    if min(t.numel() for t in tensors) < n:
+        raise ValueError(f"{who}: the flat bucket is smaller than the policy")
 
 
 def _optr(t, dtype=torch.float32):
     return _ptr(t, dtype) if t is not None else None
+
+
+# The argument order of the fused-step family (include/aurppo.h) lives in the builders below and nowhere else in this layer; each
+# returns one run of a call's arguments, and _lib._declare spells the matching run of argtypes.  A transposition inside a run of
+# same-typed pointers raises nothing on the host and faults on the GPU: tests/test_hip_ops_calls.py pins what every call passes.
+def _mlp_family(lib, layout, rows, device, n_ws):
+    """What differs between the default 64-64 layout (K7 / K8) and the wide ones (K7w / K8w): the entry points' infix (also the
+    workspace kind), the workspace for ``n_ws`` parameters (K8 has none: ``n_ws=None``), the offsets as a ``c_int`` array, and the
+    shape arguments: rows (M or N), D, A, continuous, hidden and, for the wide layouts, num_layers."""
+    lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
+    shape = (rows, layout["D"], layout["A"], int(layout["continuous"]), layout["hidden"])
+    if layout.get("wide"):
+        ws = _workspace("mlp_wide", lib.aurppo_mlp_wide_workspace_bytes(n_ws, layout["hidden"], layout["D"]), device)
+        return "mlp_wide", ws, lay, shape + (layout["num_layers"],)
+    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n_ws), device) if n_ws is not None else None
+    return "mlp", ws, lay, shape
+
+
+def _step_prefix(inputs, actions, rec, idx, shape, flat_param, lay, n, flat_grad, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
+                 out_scalars):
+    """``inputs`` ((obs,), or K13's four activation / gradient matrices), actions, rec, idx; ``shape`` (``_mlp_family``'s; K13: M, H,
+    A, continuous); params, layout_h, n_params; grads; clip, ent_coef, vf_coef, norm_adv, vloss_mode; out_scalars."""
+    return (*[_ptr(t) for t in inputs], _optr(actions), _ptr(rec), _ptr(idx, torch.int32), *shape, _ptr(flat_param), lay, n,
+            _ptr(flat_grad), *_loss_knobs(clip, ent_coef, vf_coef, norm_adv, vloss_mode), _ptr(out_scalars))
+
+
+def _adam_knobs(max_norm, lr_dev, step_dev, betas, eps, out_norm):
+    """max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm."""
+    return (float(max_norm), _ptr(lr_dev), _ptr(step_dev), float(betas[0]), float(betas[1]), float(eps), _ptr(out_norm))
+
+
+def _adam_tail(exp_avg, exp_avg_sq, *knobs):
+    """exp_avg, exp_avg_sq, then ``_adam_knobs``."""
+    return (_ptr(exp_avg), _ptr(exp_avg_sq)) + _adam_knobs(*knobs)
+
+
+def _next_pair(next_idx):
+    """next_idx, next_M."""
+    return (None, 0) if next_idx is None else (_ptr(next_idx, torch.int32), int(next_idx.numel()))
+
+
+def _rec_pair(rec):
+    """rec, rec_floats (4, or 16 for packed records)."""
+    return (None, 4) if rec is None else (_ptr(rec), rec.numel() // rec.shape[0])
 
 
 def mlp_ppo_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv=True,
@@ -446,38 +499,26 @@ def mlp_ppo_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, en
     ``flat_grad[:n_params]`` and returns the 9 loss scalars.  ``events``: optional pair of
     ``torch.cuda.Event(enable_timing=True)`` recorded right around the main kernel (bench.py)."""
     lib = _lib_or_raise()
-    M, D, A, n = idx.numel(), layout["D"], layout["A"], layout["n_params"]
-    cont = layout.get("continuous", True)
+    n = layout["n_params"]
     if not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_ppo_step: buffer shapes do not match the policy")
     if out_scalars is None:
         out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=obs.device)
-    if layout.get("wide"):
-        ws = _workspace("mlp_wide", lib.aurppo_mlp_wide_workspace_bytes(n, layout["hidden"], D), obs.device)
-        lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
-        if events is not None:
-            for ev in events:
-                ev.record()
-        null = C.c_void_p(0)
-        _check(lib.aurppo_mlp_wide_ppo_step_f32(
-            _ptr(obs), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, D, A, int(cont), layout["hidden"],
-            layout["num_layers"], _ptr(flat_param), lay, n, _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef),
-            int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars), C.c_void_p(ws.data_ptr()), _stream(),
-            C.c_void_p(events[0].cuda_event) if events is not None else null,
-            C.c_void_p(events[1].cuda_event) if events is not None else null), "aurppo_mlp_wide_ppo_step_f32")
-        return out_scalars
-    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n), obs.device)
-    lay = (C.c_int * 13)(*layout["offsets"])
-    args = (_ptr(obs), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, D, A, int(cont), MLP_HIDDEN, _ptr(flat_param), lay, n,
-            _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(vloss_mode),
-            _ptr(out_scalars), C.c_void_p(ws.data_ptr()), _stream())
-    if events is None:
-        _check(lib.aurppo_mlp_ppo_step_f32(*args), "aurppo_mlp_ppo_step_f32")
-    else:
+    family, ws, lay, shape = _mlp_family(lib, layout, idx.numel(), obs.device, n)
+    handles = (C.c_void_p(0), C.c_void_p(0))
+    if events is not None:
         for ev in events:          # materialise the hipEvent handles (torch creates them lazily on record())
             ev.record()
-        _check(lib.aurppo_mlp_ppo_step_ev_f32(*args, C.c_void_p(events[0].cuda_event), C.c_void_p(events[1].cuda_event)),
-               "aurppo_mlp_ppo_step_ev_f32")
+        handles = tuple(C.c_void_p(ev.cuda_event) for ev in events)
+    args = _step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, n, flat_grad, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
+                        out_scalars) + _ws_stream(ws)
+    if family == "mlp_wide":       # K7w's one entry point always takes the handles; K7 has a measurement variant beside the plain one
+        name, args = "aurppo_mlp_wide_ppo_step_f32", args + handles
+    elif events is not None:
+        name, args = "aurppo_mlp_ppo_step_ev_f32", args + handles
+    else:
+        name = "aurppo_mlp_ppo_step_f32"
+    _check(getattr(lib, name)(*args), name)
     return out_scalars
 
 
@@ -486,38 +527,23 @@ def mlp_ppo_minibatch(obs, actions, rec, idx, flat_param, layout, flat_grad, cli
                       chained=False):
     """K7 (K7w) + K6b chained: one whole minibatch (src/ppo.py:219-269) -- fused step, clip_grad_norm_ and Adam over the
     same flat bucket -- in three launches.  ``next_idx``: the slice stepped next (its statistics are prepared by
-    this call); ``chained=True`` when the previous call named this ``idx`` as its ``next_idx``."""
+    this call); ``chained=True`` when the previous call named this ``idx`` as its ``next_idx``.
+
+    K7w: prepare + step + slab reduce + clip/Adam; with ``next_idx`` the optimizer launch leaves the operand copies and the
+    next slice's statistics, and a chained call then skips its prepare launch."""
     lib = _lib_or_raise()
-    M, D, A, n = idx.numel(), layout["D"], layout["A"], layout["n_params"]
-    cont = layout.get("continuous", True)
+    n = layout["n_params"]
     if not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_ppo_minibatch: buffer shapes do not match the policy")
-    if min(flat_param.numel(), flat_grad.numel(), exp_avg.numel(), exp_avg_sq.numel()) < n:
-        raise ValueError("mlp_ppo_minibatch: the flat bucket is smaller than the policy")
     # alignment padding past n_params is left alone: its gradient is never written, so clip and Adam are no-ops there
-    if layout.get("wide"):
-        # K7w: prepare + step + slab reduce + clip/Adam; with next_idx the optimizer launch leaves the operand copies and the
-        # next slice's statistics, and a chained call then skips its prepare launch
-        ws = _workspace("mlp_wide", lib.aurppo_mlp_wide_workspace_bytes(n, layout["hidden"], D), obs.device)
-        lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
-        _check(lib.aurppo_mlp_wide_ppo_minibatch_f32(
-            _ptr(obs), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, D, A, int(cont), layout["hidden"], layout["num_layers"],
-            _ptr(flat_param), lay, n, _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef), int(bool(norm_adv)),
-            int(vloss_mode), _ptr(out_scalars), _ptr(exp_avg), _ptr(exp_avg_sq), float(max_norm), _ptr(lr_dev), _ptr(step_dev),
-            float(betas[0]), float(betas[1]), float(eps), _ptr(out_norm),
-            _ptr(next_idx, torch.int32) if next_idx is not None else None, int(next_idx.numel()) if next_idx is not None else 0,
-            int(bool(chained)), C.c_void_p(ws.data_ptr()), _stream()),
-            "aurppo_mlp_wide_ppo_minibatch_f32")
-        return out_scalars
-    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n), obs.device)
-    lay = (C.c_int * 13)(*layout["offsets"])
-    _check(lib.aurppo_mlp_ppo_minibatch_f32(
-        _ptr(obs), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, D, A, int(cont), MLP_HIDDEN, _ptr(flat_param), lay, n,
-        _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars),
-        _ptr(exp_avg), _ptr(exp_avg_sq), float(max_norm), _ptr(lr_dev), _ptr(step_dev), float(betas[0]), float(betas[1]),
-        float(eps), _ptr(out_norm), _ptr(next_idx, torch.int32) if next_idx is not None else None,
-        int(next_idx.numel()) if next_idx is not None else 0, int(bool(chained)), C.c_void_p(ws.data_ptr()), _stream()),
-        "aurppo_mlp_ppo_minibatch_f32")
+    _bucket_fits(n, flat_param, flat_grad, exp_avg, exp_avg_sq, who="mlp_ppo_minibatch")
+    family, ws, lay, shape = _mlp_family(lib, layout, idx.numel(), obs.device, n)
+    name = f"aurppo_{family}_ppo_minibatch_f32"
+    _check(getattr(lib, name)(
+        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, n, flat_grad, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
+                      out_scalars),
+        *_adam_tail(exp_avg, exp_avg_sq, max_norm, lr_dev, step_dev, betas, eps, out_norm), *_next_pair(next_idx), int(bool(chained)),
+        *_ws_stream(ws)), name)
     return out_scalars
 
 
@@ -526,17 +552,15 @@ def mlp_ppo_grad(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, en
     """First half of a minibatch for one process per GPU: K7 + slab reduce into ``flat_grad[:n_params]`` (as
     ``mlp_ppo_step``), the Adam step count advanced.  The caller all-reduces ``flat_grad`` and calls ``mlp_ppo_apply``."""
     lib = _lib_or_raise()
-    M, D, A, n = idx.numel(), layout["D"], layout["A"], layout["n_params"]
-    cont = layout.get("continuous", True)
+    n = layout["n_params"]
     if not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_ppo_grad: buffer shapes do not match the policy")
     _wide_only_step(layout, "mlp_ppo_grad")
-    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n), obs.device)
-    lay = (C.c_int * 13)(*layout["offsets"])
+    _family, ws, lay, shape = _mlp_family(lib, layout, idx.numel(), obs.device, n)
     _check(lib.aurppo_mlp_ppo_grad_f32(
-        _ptr(obs), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, D, A, int(cont), MLP_HIDDEN, _ptr(flat_param), lay, n,
-        _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars),
-        _ptr(step_dev), int(bool(chained)), C.c_void_p(ws.data_ptr()), _stream()), "aurppo_mlp_ppo_grad_f32")
+        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, n, flat_grad, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
+                      out_scalars),
+        _ptr(step_dev), int(bool(chained)), *_ws_stream(ws)), "aurppo_mlp_ppo_grad_f32")
     return out_scalars
 
 
@@ -546,17 +570,13 @@ def mlp_ppo_apply(flat_param, flat_grad, exp_avg, exp_avg_sq, layout, lr_dev, st
     one launch, which also prepares ``next_idx`` for the next ``mlp_ppo_grad(..., chained=True)``."""
     lib = _lib_or_raise()
     n = layout["n_params"]
-    if min(flat_param.numel(), flat_grad.numel(), exp_avg.numel(), exp_avg_sq.numel()) < n:
-        raise ValueError("mlp_ppo_apply: the flat bucket is smaller than the policy")
+    _bucket_fits(n, flat_param, flat_grad, exp_avg, exp_avg_sq, who="mlp_ppo_apply")
     _wide_only_step(layout, "mlp_ppo_apply")
-    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n), flat_param.device)
-    lay = (C.c_int * 13)(*layout["offsets"])
+    _family, ws, lay, _shape = _mlp_family(lib, layout, None, flat_param.device, n)
     _check(lib.aurppo_mlp_ppo_apply_f32(
-        _ptr(flat_param), _ptr(flat_grad), _ptr(exp_avg), _ptr(exp_avg_sq), lay, n, layout["D"], float(grad_scale), float(max_norm),
-        _ptr(lr_dev), _ptr(step_dev), float(betas[0]), float(betas[1]), float(eps), _ptr(out_norm),
-        _ptr(rec) if rec is not None else None, (rec.numel() // rec.shape[0]) if rec is not None else 4,
-        _ptr(next_idx, torch.int32) if next_idx is not None else None,
-        int(next_idx.numel()) if next_idx is not None else 0, C.c_void_p(ws.data_ptr()), _stream()), "aurppo_mlp_ppo_apply_f32")
+        _ptr(flat_param), _ptr(flat_grad), _ptr(exp_avg), _ptr(exp_avg_sq), lay, n, layout["D"], float(grad_scale),
+        *_adam_knobs(max_norm, lr_dev, step_dev, betas, eps, out_norm), *_rec_pair(rec), *_next_pair(next_idx), *_ws_stream(ws)),
+        "aurppo_mlp_ppo_apply_f32")
     return out_norm
 
 
@@ -566,17 +586,13 @@ def mlp_ppo_apply_parts(flat_param, flat_grad, exp_avg, exp_avg_sq, layout, lr_d
     (``P2PExchange.allreduce_mean_``): the clip's norm is their sum, nothing is rescaled."""
     lib = _lib_or_raise()
     n = layout["n_params"]
-    if min(flat_param.numel(), flat_grad.numel(), exp_avg.numel(), exp_avg_sq.numel()) < n:
-        raise ValueError("mlp_ppo_apply_parts: the flat bucket is smaller than the policy")
+    _bucket_fits(n, flat_param, flat_grad, exp_avg, exp_avg_sq, who="mlp_ppo_apply_parts")
     _wide_only_step(layout, "mlp_ppo_apply_parts")
-    ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n), flat_param.device)
-    lay = (C.c_int * 13)(*layout["offsets"])
+    _family, ws, lay, _shape = _mlp_family(lib, layout, None, flat_param.device, n)
     _check(lib.aurppo_mlp_ppo_apply_parts_f32(
         _ptr(flat_param), _ptr(flat_grad), _ptr(exp_avg), _ptr(exp_avg_sq), lay, n, layout["D"], _ptr(sq_part, torch.float64),
-        int(sq_part.numel()), float(max_norm), _ptr(lr_dev), _ptr(step_dev), float(betas[0]), float(betas[1]), float(eps),
-        _ptr(out_norm), _ptr(rec) if rec is not None else None, (rec.numel() // rec.shape[0]) if rec is not None else 4,
-        _ptr(next_idx, torch.int32) if next_idx is not None else None,
-        int(next_idx.numel()) if next_idx is not None else 0, C.c_void_p(ws.data_ptr()), _stream()), "aurppo_mlp_ppo_apply_parts_f32")
+        int(sq_part.numel()), *_adam_knobs(max_norm, lr_dev, step_dev, betas, eps, out_norm), *_rec_pair(rec), *_next_pair(next_idx),
+        *_ws_stream(ws)), "aurppo_mlp_ppo_apply_parts_f32")
     return out_norm
 
 
@@ -645,8 +661,7 @@ def mlp_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None)
     (Gaussian head) or (N,) uniform draws (Categorical head); None -> value only.  Outputs may be rows of
     the rollout buffer.  Returns (actions, logp, value)."""
     lib = _lib_or_raise()
-    N, D, A = obs.shape[0], layout["D"], layout["A"]
-    cont = layout.get("continuous", True)
+    N, D, A, cont = obs.shape[0], layout["D"], layout["A"], layout["continuous"]
     dev = obs.device
     if value is None:
         value = torch.empty(N, dtype=torch.float32, device=dev)
@@ -659,20 +674,13 @@ def mlp_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None)
             raise ValueError("mlp_act: noise / output shapes do not match the policy")
     if obs.shape[-1] != D or value.numel() != N:
         raise ValueError("mlp_act: obs / value shapes do not match the policy")
+    # K8w keeps the operand-order copy of the weights in a workspace sized for no parameters; K8 has none
+    family, ws, lay, shape = _mlp_family(lib, layout, N, dev, 0 if layout.get("wide") else None)
+    name = f"aurppo_{family}_act_f32"
     null = C.c_void_p(0)
-    if layout.get("wide"):
-        ws = _workspace("mlp_wide", lib.aurppo_mlp_wide_workspace_bytes(0, layout["hidden"], layout["D"]), dev)
-        lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
-        _check(lib.aurppo_mlp_wide_act_f32(_ptr(obs), _ptr(noise) if noise is not None else null, N, D, A, int(cont),
-                                           layout["hidden"], layout["num_layers"], _ptr(flat_param), lay, layout["n_params"],
-                                           _ptr(actions) if noise is not None else null,
-                                           _ptr(logp) if noise is not None else null, _ptr(value),
-                                           C.c_void_p(ws.data_ptr()), _stream()), "aurppo_mlp_wide_act_f32")
-        return actions, logp, value
-    lay = (C.c_int * 13)(*layout["offsets"])
-    _check(lib.aurppo_mlp_act_f32(_ptr(obs), _ptr(noise) if noise is not None else null, N, D, A, int(cont), MLP_HIDDEN,
-                                  _ptr(flat_param), lay, layout["n_params"], _ptr(actions) if noise is not None else null,
-                                  _ptr(logp) if noise is not None else null, _ptr(value), _stream()), "aurppo_mlp_act_f32")
+    _check(getattr(lib, name)(_ptr(obs), _ptr(noise) if noise is not None else null, *shape, _ptr(flat_param), lay, layout["n_params"],
+                              _ptr(actions) if noise is not None else null, _ptr(logp) if noise is not None else null, _ptr(value),
+                              *(_ws_stream(ws) if ws is not None else (_stream(),))), name)
     return actions, logp, value
 
 
@@ -686,7 +694,7 @@ def grad_norm_clip_(flat_grads, max_norm, out_norm=None):
         out_norm = torch.empty(1, dtype=torch.float32, device=flat_grads.device)
     ws = _workspace("clip", lib.aurppo_clip_workspace_bytes(n), flat_grads.device)
     _check(lib.aurppo_grad_norm_clip_f32(_ptr(flat_grads), n, float(max_norm), _ptr(out_norm),
-                                         C.c_void_p(ws.data_ptr()), _stream()), "aurppo_grad_norm_clip_f32")
+                                         *_ws_stream(ws)), "aurppo_grad_norm_clip_f32")
     return out_norm
 
 
@@ -702,8 +710,7 @@ def clip_adam_(flat_param, flat_grad, exp_avg, exp_avg_sq, lr_dev, step_dev, max
         out_norm = torch.empty(1, dtype=torch.float32, device=flat_param.device)
     ws = _workspace("clip", lib.aurppo_clip_workspace_bytes(n), flat_param.device)
     _check(lib.aurppo_clip_adam_f32(_ptr(flat_param), _ptr(flat_grad), _ptr(exp_avg), _ptr(exp_avg_sq), n, int(clip_n),
-                                    float(max_norm), _ptr(lr_dev), _ptr(step_dev), float(betas[0]), float(betas[1]),
-                                    float(eps), _ptr(out_norm), C.c_void_p(ws.data_ptr()), _stream()),
+                                    *_adam_knobs(max_norm, lr_dev, step_dev, betas, eps, out_norm), *_ws_stream(ws)),
            "aurppo_clip_adam_f32")
     return out_norm
 
@@ -792,6 +799,7 @@ class _FirstBlock(torch.autograd.Function):
 
 CONV3X3_MIN_PIXELS = 131072
 CONV3X3_MIN_WGS = 512
+K12_MIN_COUT, K12_MIN_CIN, K12_MIN_PIXELS = 64, 32, 16384
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -804,7 +812,7 @@ class _Conv3x3(torch.autograd.Function):
         z = torch.empty((B, Co, Hh + 2 * pad - 2, Ww + 2 * pad - 2), dtype=torch.float32, device=x.device)
         ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
         _check(lib.aurppo_conv3x3_f32(_ptr(x.detach()), _ptr(w.detach()), _ptr(z), B, Ci, Co, Hh, Ww, int(pad), 0,
-                                      C.c_void_p(ws.data_ptr()), _stream()), "aurppo_conv3x3_f32")
+                                      *_ws_stream(ws)), "aurppo_conv3x3_f32")
         ctx.save_for_backward(x, w)
         ctx.pad = int(pad)
         return z
@@ -825,7 +833,7 @@ class _Conv3x3(torch.autograd.Function):
             dx = torch.empty_like(x)
             ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Co, Ci), x.device)
             _check(lib.aurppo_conv3x3_f32(_ptr(g), _ptr(w.detach()), _ptr(dx), B, Ci, Co, g.shape[2], g.shape[3], pad, 1,
-                                          C.c_void_p(ws.data_ptr()), _stream()), "aurppo_conv3x3_f32")
+                                          *_ws_stream(ws)), "aurppo_conv3x3_f32")
         if ctx.needs_input_grad[1]:
             if conv3x3_wgrad_ok(x, Ci, Co, pad):
                 dw = conv3x3_wgrad(g, x, Co, pad)       # K12
@@ -851,9 +859,6 @@ def conv3x3_wgrad_ok(x, cin, cout, pad):
     return cout >= K12_MIN_COUT and cin >= K12_MIN_CIN and pixels >= K12_MIN_PIXELS
 
 
-K12_MIN_COUT, K12_MIN_CIN, K12_MIN_PIXELS = 64, 32, 16384
-
-
 def conv3x3_wgrad(g, x, cout, pad):
     """K12: the gradient of ``conv2d(x, w (cout, cin, 3, 3), padding=pad)`` with respect to ``w`` given the output gradient ``g``
     (csrc/conv.hip::k_conv3x3_wgrad: a product over the batch's output pixels, both operands split once per workgroup)."""
@@ -866,8 +871,7 @@ def conv3x3_wgrad(g, x, cout, pad):
         raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_wgrad_f32 does not take this shape")
     ws = _workspace("wgrad", nb, x.device)
     dw = torch.empty((cout, Ci, 3, 3), dtype=torch.float32, device=x.device)
-    _check(lib.aurppo_conv3x3_wgrad_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), C.c_void_p(ws.data_ptr()),
-                                        _stream()), "aurppo_conv3x3_wgrad_f32")
+    _check(lib.aurppo_conv3x3_wgrad_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), *_ws_stream(ws)), "aurppo_conv3x3_wgrad_f32")
     return dw
 
 
@@ -916,23 +920,32 @@ def linear_nobias(x, w, mode=0):
     Nw, Kw = w.shape
     y = torch.empty((M, Nw if mode == 0 else Kw), dtype=torch.float32, device=x.device)
     ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw if mode == 0 else Nw, Nw if mode == 0 else Kw), x.device)
-    _check(lib.aurppo_linear_f32(_ptr(x), _ptr(w), _ptr(y), M, Kw, Nw, int(mode), C.c_void_p(ws.data_ptr()), _stream()),
+    _check(lib.aurppo_linear_f32(_ptr(x), _ptr(w), _ptr(y), M, Kw, Nw, int(mode), *_ws_stream(ws)),
            "aurppo_linear_f32")
     return y
+
+
+def _linear_wgrad(gy, x, rows):
+    lib = _lib_or_raise()
+    gy, x = gy.contiguous(), x.contiguous()
+    M, N = gy.shape
+    K = x.shape[1]
+    if rows is not None and rows.numel() != M:
+        raise ValueError("linear_wgrad_rows: one index per row of gy")
+    ws = _workspace("wgrad", lib.aurppo_linear_wgrad_ws_bytes(M, N, K), x.device)
+    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    if rows is None:
+        _check(lib.aurppo_linear_wgrad_f32(_ptr(gy), _ptr(x.detach()), _ptr(dw), M, N, K, *_ws_stream(ws)), "aurppo_linear_wgrad_f32")
+    else:
+        _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(gy), _ptr(x), _ptr(rows, torch.int32), _ptr(dw), M, N, K, *_ws_stream(ws)),
+               "aurppo_linear_wgrad_rows_f32")
+    return dw
 
 
 def linear_wgrad(gy, x):
     """``gy.T @ x`` -- nn.Linear's weight gradient -- on the bf16 matrix pipe (csrc/conv.hip::k_linear_wgrad: both operands split
     once per workgroup through LDS, the rows cut into slices that are summed in slice order)."""
-    lib = _lib_or_raise()
-    gy, x = gy.contiguous(), x.contiguous()
-    M, N = gy.shape
-    K = x.shape[1]
-    ws = _workspace("wgrad", lib.aurppo_linear_wgrad_ws_bytes(M, N, K), x.device)
-    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    _check(lib.aurppo_linear_wgrad_f32(_ptr(gy), _ptr(x.detach()), _ptr(dw), M, N, K, C.c_void_p(ws.data_ptr()), _stream()),
-           "aurppo_linear_wgrad_f32")
-    return dw
+    return _linear_wgrad(gy, x, None)
 
 
 def linear_wgrad_ok(gy, x):
@@ -940,17 +953,24 @@ def linear_wgrad_ok(gy, x):
             and gy.shape[0] >= LINEAR_MIN_ROWS and gy.shape[1] >= 64 and x.shape[1] >= 64)
 
 
-def linear_bias_act(x, w, bias, act=0):
-    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/conv.hip::k_linear with the layer's tail in its epilogue."""
+def _linear_bias_act(x, rows, w, bias, act):
     lib = _lib_or_raise()
     x, w = x.contiguous(), w.contiguous()
-    M = x.shape[0]
+    M = x.shape[0] if rows is None else rows.numel()
     Nw, Kw = w.shape
     y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
     ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
-    _check(lib.aurppo_linear_bias_act_f32(_ptr(x), _ptr(w), _ptr(bias.contiguous()) if bias is not None else None, _ptr(y), M, Kw, Nw,
-                                          int(act), C.c_void_p(ws.data_ptr()), _stream()), "aurppo_linear_bias_act_f32")
+    tail = (_ptr(w), _optr(bias.contiguous() if bias is not None else None), _ptr(y), M, Kw, Nw, int(act), *_ws_stream(ws))
+    if rows is None:
+        _check(lib.aurppo_linear_bias_act_f32(_ptr(x), *tail), "aurppo_linear_bias_act_f32")
+    else:
+        _check(lib.aurppo_linear_rows_bias_act_f32(_ptr(x), _ptr(rows, torch.int32), *tail), "aurppo_linear_rows_bias_act_f32")
     return y
+
+
+def linear_bias_act(x, w, bias, act=0):
+    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/conv.hip::k_linear with the layer's tail in its epilogue."""
+    return _linear_bias_act(x, None, w, bias, act)
 
 
 def first_block(obs, state, weight, bias):
@@ -962,31 +982,12 @@ def first_block(obs, state, weight, bias):
 
 def linear_rows_bias_act(x, rows, w, bias, act=0):
     """``act(x[rows] @ w.T + bias)`` without materialising ``x[rows]``: k_linear reads its rows through the int32 index."""
-    lib = _lib_or_raise()
-    x, w = x.contiguous(), w.contiguous()
-    M = rows.numel()
-    Nw, Kw = w.shape
-    y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
-    ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
-    _check(lib.aurppo_linear_rows_bias_act_f32(_ptr(x), _ptr(rows, torch.int32), _ptr(w), _optr(bias.contiguous() if bias is not None else None),
-                                               _ptr(y), M, Kw, Nw, int(act), C.c_void_p(ws.data_ptr()), _stream()),
-           "aurppo_linear_rows_bias_act_f32")
-    return y
+    return _linear_bias_act(x, rows, w, bias, act)
 
 
 def linear_wgrad_rows(gy, x, rows):
     """``gy.T @ x[rows]`` (k_linear_wgrad with its x operand read through the index)."""
-    lib = _lib_or_raise()
-    gy, x = gy.contiguous(), x.contiguous()
-    M, N = gy.shape
-    K = x.shape[1]
-    if rows.numel() != M:
-        raise ValueError("linear_wgrad_rows: one index per row of gy")
-    ws = _workspace("wgrad", lib.aurppo_linear_wgrad_ws_bytes(M, N, K), x.device)
-    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
-    _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(gy), _ptr(x), _ptr(rows, torch.int32), _ptr(dw), M, N, K, C.c_void_p(ws.data_ptr()),
-                                            _stream()), "aurppo_linear_wgrad_rows_f32")
-    return dw
+    return _linear_wgrad(gy, x, rows)
 
 
 def linear_dx_tanh(gz, w, h, out=None):
@@ -1001,7 +1002,7 @@ def linear_dx_tanh(gz, w, h, out=None):
     if h.shape != (M, Kw) or out.shape != (M, Kw) or gz.shape[1] != Nw:
         raise ValueError("linear_dx_tanh: shape mismatch")
     ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Nw, Kw), gz.device)
-    _check(lib.aurppo_linear_dx_tanh_f32(_ptr(gz), _ptr(w), _ptr(h), _ptr(out), M, Kw, Nw, C.c_void_p(ws.data_ptr()), _stream()),
+    _check(lib.aurppo_linear_dx_tanh_f32(_ptr(gz), _ptr(w), _ptr(h), _ptr(out), M, Kw, Nw, *_ws_stream(ws)),
            "aurppo_linear_dx_tanh_f32")
     return out
 
@@ -1021,16 +1022,13 @@ def head_ppo(hA, hC, actions, rec, idx, flat_param, layout, flat_grad, clip, ent
     hidden layers' bias gradients at their bucket offsets in ``flat_grad``, and returns the 9 scalars."""
     lib = _lib_or_raise()
     M, Hd = hA.shape
-    A, cont, n = layout["A"], layout.get("continuous", True), layout["n_params"]
+    A, n = layout["A"], layout["n_params"]
     gzA, gzC = hA if gzA is None else gzA, hC if gzC is None else gzC
     if hC.shape != (M, Hd) or gzA.shape != (M, Hd) or gzC.shape != (M, Hd) or idx.numel() != M or Hd != layout["hidden"]:
         raise ValueError("head_ppo: shape mismatch")
-    aw = A if cont else 1
-    B = rec.shape[0]
-    if (actions is None and rec.numel() != B * 16) or (actions is not None and (rec.numel() != B * 4 or actions.numel() != B * aw)):
+    if not _mlp_buffers_ok(None, actions, rec, layout):
         raise ValueError("head_ppo: buffer shapes do not match the policy")
-    if min(flat_param.numel(), flat_grad.numel()) < n:
-        raise ValueError("head_ppo: the flat bucket is smaller than the policy")
+    _bucket_fits(n, flat_param, flat_grad, who="head_ppo")
     if out_scalars is None:
         out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=hA.device)
     nb = lib.aurppo_head_ppo_workspace_bytes(M, Hd, A)
@@ -1038,10 +1036,9 @@ def head_ppo(hA, hC, actions, rec, idx, flat_param, layout, flat_grad, clip, ent
         raise RuntimeError("aur_ppo_amd: aurppo_head_ppo_f32 does not take this shape")
     ws = _workspace("head", nb, hA.device)
     lay = (C.c_int * 7)(*head_layout(layout))
-    _check(lib.aurppo_head_ppo_f32(_ptr(hA), _ptr(hC), _ptr(gzA), _ptr(gzC), _optr(actions), _ptr(rec), _ptr(idx, torch.int32), M, Hd, A,
-                                   int(cont), _ptr(flat_param), lay, n, _ptr(flat_grad), float(clip), float(ent_coef), float(vf_coef),
-                                   int(bool(norm_adv)), int(vloss_mode), _ptr(out_scalars), C.c_void_p(ws.data_ptr()), _stream()),
-           "aurppo_head_ppo_f32")
+    _check(lib.aurppo_head_ppo_f32(
+        *_step_prefix((hA, hC, gzA, gzC), actions, rec, idx, (M, Hd, A, int(layout["continuous"])), flat_param, lay, n, flat_grad, clip,
+                      ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars), *_ws_stream(ws)), "aurppo_head_ppo_f32")
     return out_scalars
 
 
@@ -1071,8 +1068,7 @@ def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip
     M, D, Hd, L, n = idx.numel(), layout["D"], layout["hidden"], layout["num_layers"], layout["n_params"]
     if not layout.get("layered") or not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_layered_step: buffer shapes do not match the policy")
-    if min(flat_param.numel(), flat_grad.numel()) < n:
-        raise ValueError("mlp_layered_step: the flat bucket is smaller than the policy")
+    _bucket_fits(n, flat_param, flat_grad, who="mlp_layered_step")
     dev = obs.device
     if out_scalars is None:
         out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=dev)

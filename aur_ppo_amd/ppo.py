@@ -419,104 +419,113 @@ class ppo(FlatAdamMixin):
         self._graph.replay()
         return self._graph_steps
 
-    def _update_body(self, returns, advantages, perms, packed):
+    def _vloss_mode(self):
+        return self.ops.VLOSS_CLIPPED if self.clip_vloss else self.ops.VLOSS_OLDVALUES   # src/ppo.py:250-261 (F8)
+
+    def _step_pair(self):
+        """(actions, records) as the fused steps read them: packed records alone when ``_gae`` built them."""
+        if self._rec64 is not None:
+            return None, self._rec64
+        return self.buffer.actions.reshape((-1,) + self.buffer.action_shape), self._rec
+
+    def _update_route(self, packed):
+        """Which of the six ways one minibatch is stepped; decided once per update."""
         ops = self.ops
+        # single process, MLP policy, fused Adam over exactly the policy's bucket: K7 + clip + Adam chained, three
+        # launches per minibatch (each call also prepares the statistics of the slice that follows it)
+        if (packed and self._mlp is not None and not self._dp and self._fused_adam
+                and self._bucket_is_policy and hasattr(ops, "mlp_ppo_minibatch")):
+            return "chained"
+        # one process per GPU: the same chain in two halves around the gradient all-reduce (SUM; the 1/W rides in the
+        # apply kernel), three launches + one collective per minibatch
+        if (packed and self._mlp is not None and not self._mlp.get("wide") and self._dp and self._fused_adam
+                and self._bucket_is_policy and hasattr(ops, "mlp_ppo_grad")):
+            return "halves_p2p" if self._p2p is not None else "halves_allreduce"
+        if packed and self._mlp is not None:
+            return "fused_step"         # one fused launch: rows are read through the permutation, gradients land in the bucket
+        if packed and self._mlp_layered is not None:
+            return "layered_step"       # rows through the permutation in the first product, the loss behind the last one
+        return "autograd"
+
+    def _next_slice(self, perms, ep, si, starts):
+        """The index slice stepped after slice ``si`` of epoch ``ep``: the epoch's next one, the first of the next epoch, or None."""
+        M = self.minibatch_size
+        if si + 1 < len(starts):
+            return perms[ep][starts[si + 1]:starts[si + 1] + M]
+        if ep + 1 < self.num_update_epochs:
+            return perms[ep + 1][0:M]
+        return None
+
+    def _update_body(self, returns, advantages, perms, packed):
+        ops, bk = self.ops, self.bucket
         b_obs, b_logprobs, b_actions, b_advantages, b_returns, b_values = self.buffer.flatten(returns, advantages)
         # packed path when (returns, advantages) are the tensors K1 just produced; otherwise (a caller
         # handing in its own) the six separate streams of buffer.flatten()
         srcs = [b_obs, b_actions, self._rec] if packed else [b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values]
-        vmode = ops.VLOSS_CLIPPED if self.clip_vloss else ops.VLOSS_OLDVALUES   # src/ppo.py:250-261 (F8)
+        vmode = self._vloss_mode()
         B, M = self.batch_size, self.minibatch_size
+        route = self._update_route(packed)
+        # what a fused step takes before its index slice (head), and between the slice and its row of scalars (mid)
+        k7_act, k7_rec = self._step_pair()
+        layout = self._mlp_layered if route == "layered_step" else self._mlp
+        head = (b_obs, k7_act, k7_rec)
+        mid = (bk.flat_param, layout, bk.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff, self.norm_adv, vmode)
+        if route in ("fused_step", "layered_step"):
+            step_fn = ops.mlp_ppo_step if route == "fused_step" else ops.mlp_layered_step
+        if route in ("chained", "halves_allreduce", "halves_p2p"):
+            g = self.optimizer.param_groups[0]
+            adam = (self._lr_tensor, self._adam_t, self.max_grad_norm, g["betas"], g["eps"])
+
         step = 0
-        # single process, MLP policy, fused Adam over exactly the policy's bucket: K7 + clip + Adam chained, three
-        # launches per minibatch (each call also prepares the statistics of the slice that follows it)
-        chain = (packed and self._mlp is not None and not self._dp and self._fused_adam
-                 and self._bucket_is_policy and hasattr(ops, "mlp_ppo_minibatch"))
-        # one process per GPU: the same chain in two halves around the gradient all-reduce (SUM; the 1/W rides in the
-        # apply kernel), three launches + one collective per minibatch
-        chain_dp = (packed and self._mlp is not None and not self._mlp.get("wide") and self._dp and self._fused_adam
-                    and self._bucket_is_policy and hasattr(ops, "mlp_ppo_grad"))
-        k7_act, k7_rec = (None, self._rec64) if (packed and self._rec64 is not None) else (b_actions, self._rec)
+
+        def probe_first_grad(divisor=None):
+            """bench.py / tests: a copy of step 1's REDUCED gradient (``divisor``: the world, behind a SUM all-reduce)."""
+            if step == 0 and self.first_grad_probe is not None:
+                grad = bk.flat_grad.detach().clone()
+                self.first_grad_probe.append(grad if divisor is None else grad / divisor)
+
         starts = list(range(0, B, M))
         for ep in range(self.num_update_epochs):
             idx_ep = perms[ep]
             for si, start in enumerate(starts):
                 mb_inds = idx_ep[start:start + M]
-                if chain or chain_dp:
-                    if si + 1 < len(starts):
-                        nxt = idx_ep[starts[si + 1]:starts[si + 1] + M]
-                    elif ep + 1 < self.num_update_epochs:
-                        nxt = perms[ep + 1][0:M]
-                    else:
-                        nxt = None
-                    g = self.optimizer.param_groups[0]
-                if chain_dp:
-                    ops.mlp_ppo_grad(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp,
-                                     self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
-                                     self.norm_adv, vmode, self._scalars[step], self._adam_t, chained=step > 0)
-                    if self._p2p is not None:
+                sc, norm = self._scalars[step], self._norms[step:step + 1]
+                if route == "chained":
+                    ops.mlp_ppo_minibatch(*head, mb_inds, *mid, sc, self._adam_m, self._adam_v, *adam, norm,
+                                          next_idx=self._next_slice(perms, ep, si, starts), chained=step > 0)
+                elif route in ("halves_allreduce", "halves_p2p"):
+                    nxt = self._next_slice(perms, ep, si, starts)
+                    ops.mlp_ppo_grad(*head, mb_inds, *mid, sc, self._adam_t, chained=step > 0)
+                    if route == "halves_p2p":
                         # one launch, one hop: every rank reads its peers' published gradients and forms the mean in rank order
                         n = self._mlp["n_params"]
-                        self._p2p.allreduce_mean_(self.bucket.flat_grad, n, self._adam_t, timeout_s=self._p2p_timeout)
-                        if step == 0 and self.first_grad_probe is not None:
-                            self.first_grad_probe.append(self.bucket.flat_grad.detach().clone())
-                        ops.mlp_ppo_apply_parts(self.bucket.flat_param, self.bucket.flat_grad, self._adam_m, self._adam_v, self._mlp,
-                                                self._lr_tensor, self._adam_t, self.max_grad_norm, g["betas"], g["eps"],
-                                                self._norms[step:step + 1], self._p2p.parts(n), rec=k7_rec, next_idx=nxt)
-                        step += 1
-                        continue
-                    D.allreduce_sum_(self.bucket.flat_grad, self.world, force=True)
-                    if step == 0 and self.first_grad_probe is not None:
-                        self.first_grad_probe.append(self.bucket.flat_grad.detach().clone() / self.world)
-                    ops.mlp_ppo_apply(self.bucket.flat_param, self.bucket.flat_grad, self._adam_m, self._adam_v, self._mlp,
-                                      self._lr_tensor, self._adam_t, self.max_grad_norm, g["betas"], g["eps"],
-                                      self._norms[step:step + 1], grad_scale=1.0 / self.world, rec=k7_rec, next_idx=nxt)
-                    step += 1
-                    continue
-                if chain:
-                    ops.mlp_ppo_minibatch(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp,
-                                          self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
-                                          self.norm_adv, vmode, self._scalars[step], self._adam_m, self._adam_v,
-                                          self._lr_tensor, self._adam_t, self.max_grad_norm, g["betas"], g["eps"],
-                                          self._norms[step:step + 1], next_idx=nxt, chained=step > 0)
-                    step += 1
-                    continue
-                if packed and self._mlp is not None:
-                    # one fused launch: rows are read through the permutation, gradients land in the bucket
-                    ops.mlp_ppo_step(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp,
-                                     self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
-                                     self.norm_adv, vmode, self._scalars[step])
-                    D.allreduce_mean_(self.bucket.flat_grad, self.world, force=self._dp)
-                    if step == 0 and self.first_grad_probe is not None:
-                        self.first_grad_probe.append(self.bucket.flat_grad.detach().clone())
-                    self._clip_and_step(self._norms[step:step + 1])
-                    step += 1
-                    continue
-                if packed and self._mlp_layered is not None:
-                    # the layered step: rows through the permutation in the first product, the loss behind the last one
-                    ops.mlp_layered_step(b_obs, k7_act, k7_rec, mb_inds, self.bucket.flat_param, self._mlp_layered,
-                                         self.bucket.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff,
-                                         self.norm_adv, vmode, self._scalars[step])
-                    D.allreduce_mean_(self.bucket.flat_grad, self.world, force=self._dp)
-                    if step == 0 and self.first_grad_probe is not None:
-                        self.first_grad_probe.append(self.bucket.flat_grad.detach().clone())
-                    self._clip_and_step(self._norms[step:step + 1])
-                    step += 1
-                    continue
-                mb = ops.gather(mb_inds, srcs, probe=self._probe) if self._probe is not None else ops.gather(mb_inds, srcs)
-                _, newlogprob, entropy, newvalue = self.policy.evaluate(mb[0], mb[1])
-                if packed:
-                    loss = ops.ppo_loss_packed(newlogprob, newvalue, entropy, mb[2], self.clip_coeff,
-                                               self.entropy_coeff, self.value_coeff, self.norm_adv, vmode,
-                                               self._scalars[step])
+                        self._p2p.allreduce_mean_(bk.flat_grad, n, self._adam_t, timeout_s=self._p2p_timeout)
+                        probe_first_grad()
+                        ops.mlp_ppo_apply_parts(bk.flat_param, bk.flat_grad, self._adam_m, self._adam_v, self._mlp, *adam, norm,
+                                                self._p2p.parts(n), rec=k7_rec, next_idx=nxt)
+                    else:
+                        D.allreduce_sum_(bk.flat_grad, self.world, force=True)
+                        probe_first_grad(self.world)
+                        ops.mlp_ppo_apply(bk.flat_param, bk.flat_grad, self._adam_m, self._adam_v, self._mlp, *adam, norm,
+                                          grad_scale=1.0 / self.world, rec=k7_rec, next_idx=nxt)
+                elif route in ("fused_step", "layered_step"):
+                    step_fn(*head, mb_inds, *mid, sc)
+                    D.allreduce_mean_(bk.flat_grad, self.world, force=self._dp)
+                    probe_first_grad()
+                    self._clip_and_step(norm)
                 else:
-                    loss = ops.ppo_loss(newlogprob, newvalue, entropy, mb[2], mb[3], mb[5], mb[4], self.clip_coeff,
-                                        self.entropy_coeff, self.value_coeff, self.norm_adv, vmode,
-                                        self._scalars[step])
-                self.bucket.zero_grad()
-                loss.backward()
-                D.allreduce_mean_(self.bucket.flat_grad, self.world)
-                self._clip_and_step(self._norms[step:step + 1])
+                    mb = ops.gather(mb_inds, srcs, probe=self._probe) if self._probe is not None else ops.gather(mb_inds, srcs)
+                    _, newlogprob, entropy, newvalue = self.policy.evaluate(mb[0], mb[1])
+                    if packed:
+                        loss = ops.ppo_loss_packed(newlogprob, newvalue, entropy, mb[2], self.clip_coeff,
+                                                   self.entropy_coeff, self.value_coeff, self.norm_adv, vmode, sc)
+                    else:
+                        loss = ops.ppo_loss(newlogprob, newvalue, entropy, mb[2], mb[3], mb[5], mb[4], self.clip_coeff,
+                                            self.entropy_coeff, self.value_coeff, self.norm_adv, vmode, sc)
+                    bk.zero_grad()
+                    loss.backward()
+                    D.allreduce_mean_(bk.flat_grad, self.world)
+                    self._clip_and_step(norm)
                 step += 1
             if self.target_kl is not None:
                 # the reference compares the LAST minibatch's approx_kl (src/ppo.py:271-273)
@@ -548,12 +557,10 @@ class ppo(FlatAdamMixin):
         perms = self._perm_static if self._perm_static is not None else self._last_perms
         if self._probe_mlp_outs is None:
             self._probe_mlp_outs = [torch.empty_like(self.bucket.flat_grad), torch.empty(self.ops.N_SCALARS, device=self.device)]
-        vmode = self.ops.VLOSS_CLIPPED if self.clip_vloss else self.ops.VLOSS_OLDVALUES
-        acts, rec = (None, self._rec64) if self._rec64 is not None else (
-            self.buffer.actions.reshape((-1,) + self.buffer.action_shape), self._rec)
+        acts, rec = self._step_pair()
         self.ops.mlp_ppo_step(self.buffer.states.reshape((-1,) + self.buffer.observation_shape), acts, rec,
                               perms[0][:self.minibatch_size], self.bucket.flat_param, self._mlp, self._probe_mlp_outs[0],
-                              self.clip_coeff, self.entropy_coeff, self.value_coeff, self.norm_adv, vmode,
+                              self.clip_coeff, self.entropy_coeff, self.value_coeff, self.norm_adv, self._vloss_mode(),
                               self._probe_mlp_outs[1], events=events)
 
     def _rewind_rng(self, last_epoch_run):
