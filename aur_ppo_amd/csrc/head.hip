@@ -25,7 +25,6 @@ constexpr int kHT = 256;             // threads per workgroup
 constexpr int kHeadMaxGrid = 512;
 constexpr int kHeadStat = 64;        // statistics workgroups (at most)
 constexpr int kSmall = 48;           // slab tail: d b_actor [16], d logstd [16], d b_critic [1] + padding
-constexpr float kHalfLog2Pi = 0.9189385332046727f;
 
 struct HeadArgs {
     const float* hA;                 // (M, H) last hidden activations, minibatch order
@@ -213,8 +212,8 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
                     if (k < A) {
                         const float ls = s_small[16 + k], var = s_small[32 + k];
                         const float z = actv[k] - (p[k] + s_small[k]);
-                        logp += (-(z * z) / (2.0f * var) - ls) - kHalfLog2Pi;
-                        ent += (0.5f + kHalfLog2Pi) + ls;
+                        logp += gauss_logp_var(z, var, ls);
+                        ent += gauss_ent(ls);
                     }
                 }
                 ts = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
@@ -223,8 +222,8 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
                     if (k < A) {
                         const float var = s_small[32 + k];
                         const float z = actv[k] - (p[k] + s_small[k]);
-                        p[k] = ts.g_logp * (z / var);
-                        dlr[k] = ts.g_logp * ((z * z) / var - 1.0f) + g_ent;
+                        p[k] = gauss_dmu_var(ts.g_logp, z, var);
+                        dlr[k] = gauss_dls_var(ts.g_logp, z, var, g_ent);
                     }
                 }
                 l_ent += (double)ent;
@@ -258,7 +257,7 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
                     if (k < A) {
                         const float lpk = p[k] - lse;
                         const float pk = expf(lpk);
-                        p[k] = ts.g_logp * ((k == ai ? 1.0f : 0.0f) - pk) + g_ent * (-pk * (lpk + ent));
+                        p[k] = cat_dlogit(ts.g_logp, k == ai, pk, lpk, ent, g_ent);
                     }
                 }
                 l_ent += (double)ent;

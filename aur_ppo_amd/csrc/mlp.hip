@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
                 const float act = m + sd * a.noise[(size_t)n * A + k];
                 a.actions[(size_t)n * A + k] = act;
                 const float z = act - m;                                   // as evaluate() forms it: (a - mu)
-                lp += (-(z * z) / (2.0f * (sd * sd)) - ls) - 0.9189385332046727f;
+                lp += gauss_logp_var(z, sd * sd, ls);
             }
         }
         lp = sum8(lp);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
                     a.actions[(size_t)n * A + k] = act;
                     const float z = act - mu[k];                       // as evaluate() forms it: (a - mu)
                     const float sd = expf(ls);
-                    lp += (-(z * z) / (2.0f * (sd * sd)) - ls) - 0.9189385332046727f;
+                    lp += gauss_logp_var(z, sd * sd, ls);
                 }
                 a.logp[n] = lp;
             } else {
@@ -451,9 +451,7 @@ OperandCopies operand_copies(int n_params, const MlpLayout* L = nullptr, int D =
     if (wide) oc.wide = *wide;
     return oc;
 }
-// bucket element i has just become pn: drop it wherever the weight appears as an operand.  The addresses are mlp_common.h's w1op_index,
-// op_index and op3_index written out (= op3_at(slot, nn >> 5, kk >> 4, 0, (nn & 31) + 32 ((kk >> 3) & 1), kk & 7) ...): called as
-// functions they compile k_adam_chain to other instructions, which is held back until that build has been timed against this one.
+// bucket element i has just become pn: drop it wherever the weight appears as an operand (mlp_common.h's index functions say where)
 __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, int i, float pn) {
     if (oc.wide.wop) {
         // K7w: forward copy of every hidden layer, backward copy of layers >= 1
@@ -468,24 +466,15 @@ __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, 
                     unsigned p0, p1, p2;
                     bf3::split3(pn, 0.0f, p0, p1, p2);
                     for (int dir = 0; dir < (l > 0 ? 2 : 1); ++dir) {
-                        const int nn = dir == 0 ? row : col, kk = dir == 0 ? col : row;
-                        const int at = op3_slot(n, l, dir) * kOp3Slot + (nn >> 5) * kOp3Slice +
-                                       (((kk >> 4) * 3) * 64 + (nn & 31) + 32 * ((kk >> 3) & 1)) * 8 + (kk & 7);
+                        const int at = op3_index(n, l, dir, row, col);
                         wc.wop3[at] = (unsigned short)p0;
                         wc.wop3[at + kOp3Plane] = (unsigned short)p1;
                         wc.wop3[at + 2 * kOp3Plane] = (unsigned short)p2;
                     }
                     continue;
                 }
-                const int nl = n * MAXL + l;
-                {
-                    const int blk = (row >> 5) * 4 + (col >> 5), lane = (row & 31) + 32 * (col & 1), m = (col & 31) >> 1;
-                    wc.wop[(((nl * 2 + 0) * 16 + blk) * 64 + lane) * 16 + m] = pn;
-                }
-                if (l > 0) {
-                    const int blk = (col >> 5) * 4 + (row >> 5), lane = (col & 31) + 32 * (row & 1), m = (row & 31) >> 1;
-                    wc.wop[(((nl * 2 + 1) * 16 + blk) * 64 + lane) * 16 + m] = pn;
-                }
+                wc.wop[op_index(n, l, 0, row, col)] = pn;
+                if (l > 0) wc.wop[op_index(n, l, 1, row, col)] = pn;
             }
         return;
     }
@@ -495,7 +484,7 @@ __device__ __forceinline__ void refresh_operand_copies(const OperandCopies& oc, 
     if (e >= 0 && oc.w1op) {
         const int net = (ea >= 0 && ea < H * D) ? 0 : 1;
         const int row = e / D, k = e - row * D;
-        oc.w1op[((net * 2 + (row >> 5)) * 32 + (k >> 1)) * kWave + (row & 31) + 32 * (k & 1)] = pn;
+        oc.w1op[w1op_index(net, row, k)] = pn;
     }
     if (oc.wop3) {      // k_mlp_step3's copies: the bf16 planes of the new value wherever the weight appears as an operand
         const int e2a = i - oc.w2_actor, e2c = i - oc.w2_critic;

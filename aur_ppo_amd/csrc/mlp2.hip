@@ -273,7 +273,7 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
     // entropy of the state-independent Gaussian (actor_critic.py:43), summed in action order
     float ent_sum = 0.0f;
     if (a.continuous)
-        for (int k = 0; k < A; ++k) ent_sum += (0.5f + 0.9189385332046727f) + sLs[k];
+        for (int k = 0; k < A; ++k) ent_sum += gauss_ent(sLs[k]);
     const float ent_gauss = uniform(ent_sum);
 
     // ---- persistent accumulators (registers)
@@ -470,9 +470,8 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
                 t1 = t2;
                 t2 = t3;
             }
-            // Everything below is straight-line per lane: all LDS reads go out together, the 8-lane reductions are
-            // DPP moves (no LDS round trip), the loss sums are fire-and-forget LDS atomics, and a padding row only
-            // masks what is written back.
+            // Everything below is straight-line per lane (loss_lanes, mlp_twoset.h): all LDS reads go out together, the loss sums are
+            // fire-and-forget LDS atomics.
             float* mu = sOut + (0 * R + lr) * LDO;
             float* vv = sOut + (1 * R + lr) * LDO;
             const bool real = sSrc[lr] >= 0;
@@ -480,37 +479,10 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
             const float v_new = vv[0];
             const int k0 = lj, k1 = lj + 8;
             const float m0 = mu[k0], m1 = mu[k1];
-            float logp = 0.0f, ent = 0.0f, d0, d1;
-            PpoSample t;
-            if (a.continuous) {
-                // Normal(mu, exp(logstd)): log-prob summed over action dims (actor_critic.py:36-43)
-                const float iv0 = k0 < A ? sIvar[k0] : 0.0f, iv1 = k1 < A ? sIvar[k1] : 0.0f;
-                const float z0 = act_cur[0] - m0, z1 = act_cur[1] - m1;
-                if (k0 < A) logp += (-(z0 * z0) * (0.5f * iv0) - sLs[k0]) - 0.9189385332046727f;
-                if (k1 < A) logp += (-(z1 * z1) * (0.5f * iv1) - sLs[k1]) - 0.9189385332046727f;
-                logp = sum8(logp);
-                ent = ent_gauss;
-                t = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
-                d0 = (real && k0 < A) ? t.g_logp * (z0 * iv0) : 0.0f;
-                d1 = (real && k1 < A) ? t.g_logp * (z1 * iv1) : 0.0f;
-                if (real && k0 < A) g_ls[0] += t.g_logp * (z0 * z0 * iv0 - 1.0f) + g_ent;
-                if (real && k1 < A) g_ls[1] += t.g_logp * (z1 * z1 * iv1 - 1.0f) + g_ent;
-            } else {
-                // Categorical(logits): log_softmax, log-prob of the stored action, entropy (actor_critic.py:45-50)
-                const int ai = (int)sum8(act_cur[0]);   // only lane lj == 0 holds the action index, the others hold 0
-                const float z0 = k0 < A ? m0 : -INFINITY, z1 = k1 < A ? m1 : -INFINITY;
-                const float mx = max8(fmaxf(z0, z1));
-                const float se = sum8((k0 < A ? expf(z0 - mx) : 0.0f) + (k1 < A ? expf(z1 - mx) : 0.0f));
-                const float lse = mx + logf(se);
-                const float lp0 = k0 < A ? z0 - lse : 0.0f, lp1 = k1 < A ? z1 - lse : 0.0f;
-                const float p0 = k0 < A ? expf(lp0) : 0.0f, p1 = k1 < A ? expf(lp1) : 0.0f;
-                ent = sum8(-(p0 * lp0) - p1 * lp1);
-                logp = sum8((k0 == ai ? lp0 : 0.0f) + (k1 == ai ? lp1 : 0.0f));
-                t = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
-                // d logp / d z_k = [k == a] - p_k ;  d H / d z_k = -p_k (log p_k + H)
-                d0 = (real && k0 < A) ? t.g_logp * ((k0 == ai ? 1.0f : 0.0f) - p0) + g_ent * (-p0 * (lp0 + ent)) : 0.0f;
-                d1 = (real && k1 < A) ? t.g_logp * ((k1 == ai ? 1.0f : 0.0f) - p1) + g_ent * (-p1 * (lp1 + ent)) : 0.0f;
-            }
+            const LossLanes ll = loss_lanes(a.continuous, A, lj, real, m0, m1, act_cur, sIvar, sLs, ent_gauss, g_ent, rc, v_new, mean, denom,
+                                            invM, a.h, g_ls);
+            const PpoSample& t = ll.t;
+            const float ent = ll.ent, d0 = ll.d0, d1 = ll.d1;
             mu[k0] = d0;
             mu[k1] = d1;
             g_b3a[0] += d0;
@@ -630,7 +602,8 @@ __global__ __launch_bounds__(kThreads2, 1) void k_mlp_step2(const MlpArgs a) {
 
     int le = lane, se = st;   // fresh opaque copies: nothing lane-derived has to stay live across the tile loop
     asm volatile("" : "+v"(le), "+v"(se));
-    // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab
+    // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab.  (The same lines
+    // in both two-set kernels on purpose: shared as one function they were measurably slower, see mlp_twoset.h.)
     float* park = lds + (size_t)wi * kTwoSetAccRegs * kWave + le;   // [role][reg][le]: set 0's wave of the same role reads it
     // head-side column sums: fold the 8 rows a wave's loss lanes cover
     float hs[5] = {g_b3a[0], g_b3a[1], g_ls[0], g_ls[1], (se & 7) == 0 ? g_b3c : 0.0f};

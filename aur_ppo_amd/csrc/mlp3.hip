@@ -329,7 +329,7 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
     if (!early) prefetch(sIdx, st);
     float ent_sum = 0.0f;
     if (a.continuous)
-        for (int k = 0; k < A; ++k) ent_sum += (0.5f + 0.9189385332046727f) + sLs[k];
+        for (int k = 0; k < A; ++k) ent_sum += gauss_ent(sLs[k]);
     const float ent_gauss = uniform(ent_sum);
 
     // ---- persistent accumulators (registers); layouts as in k_mlp_step2
@@ -454,34 +454,10 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
             const float v_new = vv[0];
             const int k0 = lj, k1 = lj + 8;
             const float m0 = mu[k0], m1 = mu[k1];
-            float logp = 0.0f, ent = 0.0f, d0, d1;
-            PpoSample t;
-            if (a.continuous) {
-                const float iv0 = k0 < A ? sIvar[k0] : 0.0f, iv1 = k1 < A ? sIvar[k1] : 0.0f;
-                const float z0 = act_cur[0] - m0, z1 = act_cur[1] - m1;
-                if (k0 < A) logp += (-(z0 * z0) * (0.5f * iv0) - sLs[k0]) - 0.9189385332046727f;
-                if (k1 < A) logp += (-(z1 * z1) * (0.5f * iv1) - sLs[k1]) - 0.9189385332046727f;
-                logp = sum8(logp);
-                ent = ent_gauss;
-                t = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
-                d0 = (real && k0 < A) ? t.g_logp * (z0 * iv0) : 0.0f;
-                d1 = (real && k1 < A) ? t.g_logp * (z1 * iv1) : 0.0f;
-                if (real && k0 < A) g_ls[0] += t.g_logp * (z0 * z0 * iv0 - 1.0f) + g_ent;
-                if (real && k1 < A) g_ls[1] += t.g_logp * (z1 * z1 * iv1 - 1.0f) + g_ent;
-            } else {
-                const int ai = (int)sum8(act_cur[0]);
-                const float z0 = k0 < A ? m0 : -INFINITY, z1 = k1 < A ? m1 : -INFINITY;
-                const float mx = max8(fmaxf(z0, z1));
-                const float se = sum8((k0 < A ? expf(z0 - mx) : 0.0f) + (k1 < A ? expf(z1 - mx) : 0.0f));
-                const float lse = mx + logf(se);
-                const float lp0 = k0 < A ? z0 - lse : 0.0f, lp1 = k1 < A ? z1 - lse : 0.0f;
-                const float p0 = k0 < A ? expf(lp0) : 0.0f, p1 = k1 < A ? expf(lp1) : 0.0f;
-                ent = sum8(-(p0 * lp0) - p1 * lp1);
-                logp = sum8((k0 == ai ? lp0 : 0.0f) + (k1 == ai ? lp1 : 0.0f));
-                t = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
-                d0 = (real && k0 < A) ? t.g_logp * ((k0 == ai ? 1.0f : 0.0f) - p0) + g_ent * (-p0 * (lp0 + ent)) : 0.0f;
-                d1 = (real && k1 < A) ? t.g_logp * ((k1 == ai ? 1.0f : 0.0f) - p1) + g_ent * (-p1 * (lp1 + ent)) : 0.0f;
-            }
+            const LossLanes ll = loss_lanes(a.continuous, A, lj, real, m0, m1, act_cur, sIvar, sLs, ent_gauss, g_ent, rc, v_new, mean, denom,
+                                            invM, a.h, g_ls);
+            const PpoSample& t = ll.t;
+            const float ent = ll.ent, d0 = ll.d0, d1 = ll.d1;
             // rows of tile it+1 (its indices landed in LDS two tiles ago): issued here, landed at the next S -- five phases
             // cover the HBM latency, and the 16 registers they arrive in are not live through the forward phases
             prefetch(sIdx + ((it + 1) & 1) * R, sl);
@@ -568,7 +544,8 @@ __global__ __launch_bounds__(kThreads3, 1) void k_mlp_step3(const MlpArgs a) {
 
     int le = lane, se = st;
     asm volatile("" : "+v"(le), "+v"(se));
-    // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab
+    // ---- hand-over: set 1 parks its accumulators in the (dead) tile memory, set 0 adds them and writes the slab.  (The same lines
+    // in both two-set kernels on purpose: shared as one function they were measurably slower, see mlp_twoset.h.)
     float* const fl = reinterpret_cast<float*>(lds);
     float* park = fl + (size_t)wi * kTwoSetAccRegs * kWave + le;
     float (*s_small)[8][5] = reinterpret_cast<float (*)[8][5]>(lds + kSmallOff);

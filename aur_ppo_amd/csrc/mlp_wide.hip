@@ -464,15 +464,15 @@ __global__ __launch_bounds__(256, DUAL ? 2 : 1) void k_mlpw_step(const WideArgs 
                     for (int k = 0; k < A; ++k) {
                         const float ls = s.sLs[k];
                         const float zk = act[k] - out[k];
-                        logp += (-(zk * zk) * (0.5f * s.sIvar[k]) - ls) - 0.9189385332046727f;
-                        ent += (0.5f + 0.9189385332046727f) + ls;
+                        logp += gauss_logp_ivar(zk, s.sIvar[k], ls);
+                        ent += gauss_ent(ls);
                     }
                     const PpoSample t = ppo_sample(logp, rc.x, rc.y, rc.w, rc.w, rc.z, mean, denom, invM, a.h);
                     l_a += t.pg; l_b += ent; l_c += t.okl; l_d += t.kl; l_e += t.cf;
                     for (int k = 0; k < A; ++k) {
                         const float zk = act[k] - out[k];
-                        out[k] = t.g_logp * (zk * s.sIvar[k]);
-                        s.sDls[lrow * LDO + k] = t.g_logp * (zk * zk * s.sIvar[k] - 1.0f) + g_ent;
+                        out[k] = gauss_dmu(t.g_logp, zk, s.sIvar[k]);
+                        s.sDls[lrow * LDO + k] = gauss_dls(t.g_logp, zk, s.sIvar[k], g_ent);
                     }
                 } else {
                     const float* act = s.sAct + lrow * LDO;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256, DUAL ? 2 : 1) void k_mlpw_step(const WideArgs 
                     for (int k = 0; k < A; ++k) {
                         const float lpk = out[k] - lse;
                         const float pk = expf(lpk);
-                        out[k] = t.g_logp * ((k == ai ? 1.0f : 0.0f) - pk) + g_ent * (-pk * (lpk + ent));
+                        out[k] = cat_dlogit(t.g_logp, k == ai, pk, lpk, ent, g_ent);
                     }
                 }
             } else {
@@ -877,7 +877,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
     const int k16 = tid & 15, lrow = tid >> 4;
     const float my_ls = sLs[k16], my_ivar = sIvar[k16];
     float ent_c = 0.0f;                                     // the Gaussian's entropy: the same for every row
-    for (int k = 0; k < A; ++k) ent_c += (0.5f + 0.9189385332046727f) + sLs[k];
+    for (int k = 0; k < A; ++k) ent_c += gauss_ent(sLs[k]);
 
     // persistent accumulators: dW_l blocks (out-block ob, in-block cb), the head's two 16x16 blocks, bias columns
     f32x16 gW[NL][4];
@@ -1198,13 +1198,13 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 }
             } else if (a.continuous) {
                 const float zk = sAct[row * LDO + k16] - o_k;
-                const float logp = row16_sum(k16 < A ? (-(zk * zk) * (0.5f * my_ivar) - my_ls) - 0.9189385332046727f : 0.0f);
+                const float logp = row16_sum(k16 < A ? gauss_logp_ivar(zk, my_ivar, my_ls) : 0.0f);
                 const PpoSample t = ppo_sample(logp, rc.x, rc.y, rc.w, rc.w, rc.z, mean, denom, invM, a.h);
                 if (live) {
                     if (k16 == 0) { l_a += t.pg; l_b += ent_c; l_c += t.okl; l_d += t.kl; l_e += t.cf; }
                     if (k16 < A) {
-                        g_out = t.g_logp * (zk * my_ivar);
-                        sDls[row * LDO + k16] = t.g_logp * (zk * zk * my_ivar - 1.0f) + g_ent;
+                        g_out = gauss_dmu(t.g_logp, zk, my_ivar);
+                        sDls[row * LDO + k16] = gauss_dls(t.g_logp, zk, my_ivar, g_ent);
                     }
                 } else {
                     sDls[row * LDO + k16] = 0.0f;
@@ -1221,7 +1221,7 @@ __global__ __launch_bounds__(256, 1) void k_mlpw3_step(const WideArgs a) {
                 const PpoSample t = ppo_sample(logp, rc.x, rc.y, rc.w, rc.w, rc.z, mean, denom, invM, a.h);
                 if (live) {
                     if (k16 == 0) { l_a += t.pg; l_b += ent; l_c += t.okl; l_d += t.kl; l_e += t.cf; }
-                    if (in) g_out = t.g_logp * ((k16 == ai ? 1.0f : 0.0f) - pk) + g_ent * (-pk * (lpk + ent));
+                    if (in) g_out = cat_dlogit(t.g_logp, k16 == ai, pk, lpk, ent, g_ent);
                 }
                 sDls[row * LDO + k16] = 0.0f;
             }
@@ -1428,7 +1428,7 @@ __global__ __launch_bounds__(256) void k_mlpw_act(const WideArgs a) {
             const float act = mu[k] + sd * a.noise[(size_t)n * A + k];
             a.out_actions[(size_t)n * A + k] = act;
             const float z = act - mu[k];                               // as evaluate() forms it: (a - mu)
-            lp += (-(z * z) / (2.0f * (sd * sd)) - ls) - 0.9189385332046727f;
+            lp += gauss_logp_var(z, sd * sd, ls);
         }
         a.out_logp[n] = lp;
     } else {

@@ -68,6 +68,29 @@ __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, fl
     return o;
 }
 
+// ---- Per-element terms of the action distributions (src/models/actor_critic.py:36-50), shared by every fused step (mlp2.hip, mlp3.hip,
+// mlp_wide.hip, head.hip) and rollout kernel (mlp.hip, mlp_wide.hip).  Scalars only: the sums over a row's outputs stay in the kernels,
+// whose lane layouts differ.  Each compiles in its includer's contract mode, like ppo_sample.
+constexpr float kHalfLog2Pi = 0.9189385332046727f;   // log(2 pi) / 2
+
+// Normal(mu, exp(ls)): one action dim's log-prob term, z = a - mu.  Two deliberate forms, not the same bits.  _ivar: the fused MLP steps
+// (K7, K7w), which keep 1 / sd^2 in LDS and multiply.  _var: as torch forms it, a division by 2 var -- the rollout kernels (k_mlp_act,
+// k_mlpw_act), whose log-prob becomes the stored old_logp that evaluate() is compared with, and K13 (k_head_ppo), which follows
+// evaluate() through its gradients too (gauss_dmu_var / gauss_dls_var).
+__device__ __forceinline__ float gauss_logp_ivar(float z, float ivar, float ls) { return (-(z * z) * (0.5f * ivar) - ls) - kHalfLog2Pi; }
+__device__ __forceinline__ float gauss_logp_var(float z, float var, float ls) { return (-(z * z) / (2.0f * var) - ls) - kHalfLog2Pi; }
+// ... its entropy term (state-independent), and d loss / d mu and d loss / d logstd from g_logp = d loss / d logp, g_ent = d loss / d entropy
+__device__ __forceinline__ float gauss_ent(float ls) { return (0.5f + kHalfLog2Pi) + ls; }
+__device__ __forceinline__ float gauss_dmu(float g_logp, float z, float ivar) { return g_logp * (z * ivar); }
+__device__ __forceinline__ float gauss_dls(float g_logp, float z, float ivar, float g_ent) { return g_logp * (z * z * ivar - 1.0f) + g_ent; }
+__device__ __forceinline__ float gauss_dmu_var(float g_logp, float z, float var) { return g_logp * (z / var); }
+__device__ __forceinline__ float gauss_dls_var(float g_logp, float z, float var, float g_ent) { return g_logp * ((z * z) / var - 1.0f) + g_ent; }
+// Categorical(logits): d loss / d logit k from p = softmax_k, lp = log p, ent = the row's entropy; hit: k is the action taken.
+// d logp / d z_k = [k == a] - p_k ;  d H / d z_k = -p_k (log p_k + H)
+__device__ __forceinline__ float cat_dlogit(float g_logp, bool hit, float p, float lp, float ent, float g_ent) {
+    return g_logp * ((hit ? 1.0f : 0.0f) - p) + g_ent * (-p * (lp + ent));
+}
+
 // Mean and standard deviation (torch.std: over M - 1; M == 1 -> 0/0 = NaN, as there) of a minibatch's advantages from their sum and
 // sum of squares, formed in double: every kernel that normalises advantages folds the same partial sums with this.
 __device__ __forceinline__ void adv_mean_std(double ts, double tq, int M, float& mean, float& std) {
