@@ -47,6 +47,11 @@ static inline int aurppo_device_slot() {
 // CUs of the calling thread's current device (asked once per device; `fallback` if the runtime reports none), or a negative AURPPO_E*
 // code with the error set (api.hip)
 int aurppo_cu_count(int fallback);
+// The prepared-operand half of the linear products (conv.hip), for the layered rollout step (head.hip): bytes of one forward
+// operand copy of a (N, K) weight, and y (M, N) = act(x (M, K) . w^T + bias) from such a copy (act: 0 none, 1 tanh).
+constexpr int kLayeredMaxLayers = 16;
+size_t aurppo_linear_wop_bytes(int K, int N);
+int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N, void* stream);
 // Diagnostic knobs.  Every environment variable the library looks at is parsed in ONE place (api.hip) into this struct,
 // once per process -- or on every call when AURPPO_TEST_KNOBS=1 (tests/conftest.py), so that one test process can flip
 // them.  None of them changes results beyond summation order; the defaults are the product configuration.

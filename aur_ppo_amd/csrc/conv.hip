@@ -799,19 +799,18 @@ extern "C" int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const 
     return linear_impl(gz, w, nullptr, 2, out, M, K_w, N_w, 1, wop_ws, stream, nullptr, h);
 }
 
-static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream, const int32_t* rows, const float* h) {
-    AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
-    AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
+// The two halves of a product, host side: the filter into operand order (forward B[k][n] = w[n][k]; input gradient
+// B[k = n_w][n = k_w] = w[k][n]: k_conv_prep, one tap), and k_linear from an operand copy that exists.  linear_impl does both per
+// call; the layered rollout step (aurppo_mlp_layered_prep_f32 / aurppo_linear_prepared) builds the copies once per rollout.
+static int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s) {
     const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && K % 16 == 0, AURPPO_ESHAPE,
-                   "aurppo_linear_f32: M=%lld, inner dimension %d (a multiple of 16), %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL, "aurppo_linear_f32: x / workspace not 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    // filter in operand order: forward B[k][n] = w[n][k]; input gradient B[k = n_w][n = k_w] = w[k][n] (k_conv_prep, one tap)
     hipLaunchKernelGGL(k_conv_prep, dim3(64), dim3(256), 0, s, w, N_w, K_w, K, N, mode, wop, 1);
     AURPPO_LAUNCH_CHECK("k_conv_prep");
+    return AURPPO_OK;
+}
+
+static int linear_launch(const float* x, const unsigned short* wop, const float* bias, int act, float* y, long long M, int K, int N,
+                         hipStream_t s, const int32_t* rows, const float* h) {
     LinArgs a;
     a.x = x; a.wop = wop; a.y = y; a.M = M; a.K = K; a.N = N;
     a.bias = bias; a.act = act; a.rows = rows; a.h = h;
@@ -834,6 +833,72 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     else if (NB == 2) hipLaunchKernelGGL(k_linear<2>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(k_linear<1>, g, blk, 0, s, a);
     AURPPO_LAUNCH_CHECK("k_linear");
+    return AURPPO_OK;
+}
+
+static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
+                       void* wop_ws, void* stream, const int32_t* rows, const float* h) {
+    AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
+    AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
+    const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && K % 16 == 0, AURPPO_ESHAPE,
+                   "aurppo_linear_f32: M=%lld, inner dimension %d (a multiple of 16), %d columns", M, K, N);
+    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL, "aurppo_linear_f32: x / workspace not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
+    const int rc = linear_prep(w, K_w, N_w, mode, wop, s);
+    if (rc != AURPPO_OK) return rc;
+    return linear_launch(x, wop, bias, act, y, M, K, N, s, rows, h);
+}
+
+// ---- prepared weights for the layered rollout step (head.hip: aurppo_mlp_layered_act_f32).  The parameters stand still for the T
+// steps of a rollout, so the operand-order copies of the 2 L hidden-layer matrices are built once, into a caller-owned buffer:
+// [net][layer], each copy aurppo_linear_wop_bytes(its K, hidden) bytes.
+// Bytes of one forward operand copy: the blocks k_conv_prep writes and one group of slack, as a workgroup reads whole groups.
+size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + kNBW) * (size_t)(K / 16) * 3 * 1024; }
+
+// y (M, N) = act(x (M, K) . B + bias) from the operand copy `wop` of a (N, K) weight: linear_impl without its k_conv_prep launch.
+int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
+                           void* stream) {
+    AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_prepared: null pointer");
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && K % 16 == 0, AURPPO_ESHAPE,
+                   "aurppo_linear_prepared: M=%lld, inner dimension %d (a multiple of 16), %d columns", M, K, N);
+    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_prepared: x / operand copy not 16-byte aligned");
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_prepared: act %d", act);
+    return linear_launch(x, reinterpret_cast<const unsigned short*>(wop), bias, act, y, M, K, N, (hipStream_t)stream, nullptr, nullptr);
+}
+
+static bool layered_hidden_ok(int D, int hidden, int num_layers) {
+    return D > 0 && D % 16 == 0 && hidden >= 32 && hidden <= 1024 && hidden % 32 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers;
+}
+
+extern "C" size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers) {
+    if (!layered_hidden_ok(D, hidden, num_layers)) return 0;
+    return 2 * (aurppo_linear_wop_bytes(D, hidden) + (size_t)(num_layers - 1) * aurppo_linear_wop_bytes(hidden, hidden));
+}
+
+extern "C" int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers,
+                                           void* wop, void* stream) {
+    AURPPO_REQUIRE(params && offsets && wop, AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: null pointer");
+    AURPPO_REQUIRE(layered_hidden_ok(D, hidden, num_layers), AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_prep_f32: D=%d (a multiple of 16), hidden=%d (a multiple of 32, 32..1024), %d layers (1..%d)", D, hidden,
+                   num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: operand buffer not 16-byte aligned");
+    const int per = 2 * (num_layers + 1);
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < num_layers; ++l) {
+            const int o = offsets[net * per + 2 * l];
+            AURPPO_REQUIRE(o >= 0 && (long long)o + (long long)hidden * (l ? hidden : D) <= (long long)n_params, AURPPO_EINVAL,
+                           "aurppo_mlp_layered_prep_f32: layout offset %d (%d) outside the bucket of %d", net * per + 2 * l, o, n_params);
+        }
+    char* at = reinterpret_cast<char*>(wop);
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < num_layers; ++l) {
+            const int K = l ? hidden : D;
+            const int rc = linear_prep(params + offsets[net * per + 2 * l], K, hidden, 0, reinterpret_cast<unsigned short*>(at), (hipStream_t)stream);
+            if (rc != AURPPO_OK) return rc;
+            at += aurppo_linear_wop_bytes(K, hidden);
+        }
     return AURPPO_OK;
 }
 

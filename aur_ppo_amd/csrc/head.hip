@@ -17,6 +17,9 @@
 //     registers over the rows of a thread, are summed over the workgroup's row groups in group order, and leave as one slab
 //     per workgroup.  k_head_fold sums the slabs in workgroup order (fp64 accumulator, rounded once) into the bucket's
 //     gradient and folds the nine scalars.  The grid depends on (M, H) only: two launches on the same inputs give the same bits.
+// K14 (k_head_act, below K13's host helpers) is the forward half alone for the rollout step: same layout, same head expressions in the
+// same order, then sampling -- so the log-prob it stores is the one K13 forms from the stored action.  aurppo_mlp_layered_act_f32 at
+// the end of the file is the whole rollout step: k_linear from prepared operand copies (conv.hip), then K14.
 #include "mlp_common.h"
 
 namespace {
@@ -445,6 +448,201 @@ HeadWs head_carve(void* workspace, int M, int H, int A) {
 }
 bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
 
+// ---- K14: the forward-only sibling of k_head_ppo for the rollout step (src/ppo.py:103-108: policy.evaluate(next_obs) under no_grad,
+// then the three buffer row stores) of the policies whose hidden layers run on k_linear.  K13's thread layout, LDS weights, butterfly
+// and fixed-order sum over a row's waves; the head dot products, their reduction and the log-prob are K13's expressions in K13's
+// order, so the log-prob stored here is bit for bit the one k_head_ppo forms from the stored action at the same parameters.  Lane 0
+// of a row samples (a = mu + exp(logstd) * eps for the Gaussian head; the inverse CDF of softmax(logits) at u for the Categorical
+// head, counted as k_mlp_act counts it) and stores action, log-prob and value with 4-byte stores: the outputs are rows of the rollout
+// buffer.  One launch, no slabs: a row is finished by the workgroup that read it.  noise == nullptr: the value only (the bootstrap).
+struct HeadActArgs {
+    const float* hA;                 // (N, H) last hidden activations; nullptr allowed without noise
+    const float* hC;
+    const float* noise;              // (N, A) standard normal | (N,) uniform [0, 1) | nullptr
+    const float* params;
+    float* actions;                  // (N, A) | (N,)
+    float* logp;                     // (N,)
+    float* value;                    // (N,)
+    int off_wa, off_ba, off_wc, off_bc, off_ls;
+    int N, H, A, continuous, n_iter;
+};
+
+template <int TPR>
+__global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
+    constexpr int GPW = kHT / TPR;
+    constexpr int NWG = TPR > kWave ? TPR / kWave : 1;
+    constexpr int LW = TPR > kWave ? kWave : TPR;
+    extern __shared__ __attribute__((aligned(16))) float sW[];       // (A + 1, H): actor head rows, then the critic's
+    __shared__ float s_small[kSmall];                  // b_actor [16], logstd [16], std [16]
+    __shared__ float s_part[2][kHT / kWave][20];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int H = a.H, A = a.A;
+    const int nA = a.noise ? A : 0;                    // actor outputs to form: none for the value alone
+    for (int e = tid; e < (A + 1) * H; e += kHT) {
+        if (e >= A * H) sW[e] = a.params[a.off_wc + (e - A * H)];
+        else if (nA) sW[e] = a.params[a.off_wa + e];
+    }
+    if (tid < 16) {
+        s_small[tid] = tid < nA ? a.params[a.off_ba + tid] : 0.0f;
+        const float ls = (a.continuous && tid < nA) ? a.params[a.off_ls + tid] : 0.0f;
+        s_small[16 + tid] = ls;
+        s_small[32 + tid] = expf(ls);
+    }
+    __syncthreads();
+    const float bc = a.params[a.off_bc];
+
+    const int g = tid / TPR, t = tid % TPR;
+    const int c0 = 4 * t;
+    const bool colok = c0 < H;
+    const int cw = colok ? c0 : 0;
+    const int G = (int)gridDim.x * GPW, gg = (int)blockIdx.x * GPW + g;
+    const float4 wc = *reinterpret_cast<const float4*>(sW + A * H + cw);
+    const float4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+
+    float4 na = zero4, nc = zero4;
+    auto fetch = [&](long long row) {
+        na = nc = zero4;
+        if (row < a.N && colok) {
+            if (nA) na = *reinterpret_cast<const float4*>(a.hA + (size_t)row * H + c0);
+            nc = *reinterpret_cast<const float4*>(a.hC + (size_t)row * H + c0);
+        }
+    };
+    fetch(gg);
+    for (int it = 0; it < a.n_iter; ++it) {
+        const long long row = (long long)it * G + gg;
+        const bool valid = row < a.N;
+        const float4 ha = na, hc = nc;
+        fetch(row + G);
+
+        float p[17];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            p[k] = 0.0f;
+            if (k < nA) p[k] = dot4(ha, *reinterpret_cast<const float4*>(sW + k * H + cw));
+        }
+        p[16] = dot4(hc, wc);
+#pragma unroll
+        for (int k = 0; k < 17; ++k) {
+            if (k < nA || k == 16) {
+#pragma unroll
+                for (int off = LW / 2; off > 0; off >>= 1) p[k] += __shfl_xor(p[k], off, kWave);
+            }
+        }
+        if (NWG > 1) {
+            float* const mine = s_part[it & 1][wave];
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 17; ++k)
+                    if (k < nA || k == 16) mine[k] = p[k];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 17; ++k) {
+                if (k < nA || k == 16) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int w = 0; w < NWG; ++w) s += s_part[it & 1][g * NWG + w][k];
+                    p[k] = s;
+                }
+            }
+        }
+        if (!valid || t != 0) continue;
+        a.value[row] = p[16] + bc;
+        if (!nA) continue;
+        if (a.continuous) {
+            const float* const eps = a.noise + (size_t)row * A;
+            float* const out = a.actions + (size_t)row * A;
+            float logp = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                if (k < A) {
+                    const float ls = s_small[16 + k], sd = s_small[32 + k];
+                    const float mu = p[k] + s_small[k];
+                    const float act = mu + sd * eps[k];
+                    out[k] = act;
+                    const float z = act - mu;                              // as k_head_ppo forms it from the stored action
+                    logp += gauss_logp_var(z, sd * sd, ls);
+                }
+            }
+            a.logp[row] = logp;
+        } else {
+            float mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                if (k < A) {
+                    p[k] += s_small[k];
+                    mx = fmaxf(mx, p[k]);
+                }
+            }
+            float se = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < A) se += expf(p[k] - mx);
+            const float lse = mx + logf(se);
+            const float u = a.noise[row];
+            float cdf = 0.0f;
+            int pick = A - 1;
+            bool open = true;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                if (k < A && open) {
+                    cdf += expf(p[k] - lse);
+                    if (u < cdf) {
+                        pick = k;
+                        open = false;
+                    }
+                }
+            }
+            float logp = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k == pick) logp = p[k] - lse;
+            a.actions[row] = (float)pick;
+            a.logp[row] = logp;
+        }
+    }
+}
+
+// workgroups of K14: two rows per row group where the step has them -- a rollout step is a few thousand rows, spread over the chip
+int head_act_grid(int N, int H) {
+    const int gpw = kHT / head_tpr(H);
+    long long g = ((long long)N + gpw * 2 - 1) / (gpw * 2);
+    if (g < 1) g = 1;
+    if (g > 2 * kHeadMaxGrid) g = 2 * kHeadMaxGrid;
+    return (int)g;
+}
+
+int head_act_launch(HeadActArgs a, hipStream_t s) {
+    const int tpr = head_tpr(a.H), gpw = kHT / tpr, grid = head_act_grid(a.N, a.H);
+    a.n_iter = (int)(((long long)a.N + (long long)grid * gpw - 1) / ((long long)grid * gpw));
+    const size_t lds = (size_t)(a.A + 1) * a.H * sizeof(float);
+    constexpr size_t kMaxLds = (size_t)17 * 1024 * sizeof(float);
+    static bool attr_set[kMaxDevices][6] = {};
+    const int dslot = aurppo_device_slot();
+#define AURPPO_HEAD_ACT_LAUNCH(T, SLOT)                                                                                          \
+    do {                                                                                                                         \
+        if (!attr_set[dslot][SLOT]) {                                                                                            \
+            AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_act<T>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                               (int)kMaxLds));                                                                   \
+            attr_set[dslot][SLOT] = true;                                                                                        \
+        }                                                                                                                        \
+        hipLaunchKernelGGL(k_head_act<T>, dim3(grid), dim3(kHT), lds, s, a);                                                     \
+    } while (0)
+    switch (tpr) {
+        case 8: AURPPO_HEAD_ACT_LAUNCH(8, 0); break;
+        case 16: AURPPO_HEAD_ACT_LAUNCH(16, 1); break;
+        case 32: AURPPO_HEAD_ACT_LAUNCH(32, 2); break;
+        case 64: AURPPO_HEAD_ACT_LAUNCH(64, 3); break;
+        case 128: AURPPO_HEAD_ACT_LAUNCH(128, 4); break;
+        default: AURPPO_HEAD_ACT_LAUNCH(256, 5); break;
+    }
+#undef AURPPO_HEAD_ACT_LAUNCH
+    AURPPO_LAUNCH_CHECK("k_head_act");
+    return AURPPO_OK;
+}
+
+size_t layered_act_plane_bytes(int N, int hidden) { return ((size_t)N * hidden * sizeof(float) + 63) & ~(size_t)63; }
+
 }  // namespace
 
 extern "C" size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A) {
@@ -517,4 +715,86 @@ extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA,
     hipLaunchKernelGGL(k_head_fold, dim3((n + 31) / 32 + 1), dim3(kHT), 0, s, a, grid, grads, out_scalars);
     AURPPO_LAUNCH_CHECK("k_head_fold");
     return AURPPO_OK;
+}
+
+// K14 alone: layout_h = {actor head w, b; critic head w, b; actor_logstd}.
+extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
+                                   const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
+                                   void* stream) {
+    AURPPO_REQUIRE(hC && params && layout_h && value && (!noise || (hA && actions && logp)), AURPPO_EINVAL,
+                   "aurppo_head_act_f32: null pointer");
+    AURPPO_REQUIRE(N > 0, AURPPO_ESHAPE, "aurppo_head_act_f32: N=%d", N);
+    AURPPO_REQUIRE(head_shape_ok(H, A, continuous), AURPPO_ESHAPE,
+                   "aurppo_head_act_f32: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", H, A);
+    AURPPO_REQUIRE((!noise || aligned_to(hA, 16)) && aligned_to(hC, 16), AURPPO_EINVAL, "aurppo_head_act_f32: activations not 16-byte aligned");
+    AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
+                   AURPPO_EINVAL, "aurppo_head_act_f32: noise / outputs not 4-byte aligned");
+    const long long need[5] = {(long long)A * H, A, H, 1, continuous ? A : 0};
+    for (int i = 0; i < 5; ++i)
+        AURPPO_REQUIRE(layout_h[i] >= 0 && (long long)layout_h[i] + need[i] <= (long long)n_params, AURPPO_EINVAL,
+                       "aurppo_head_act_f32: layout offset %d (%d) outside the bucket of %d", i, layout_h[i], n_params);
+    HeadActArgs a;
+    a.hA = hA; a.hC = hC; a.noise = noise; a.params = params;
+    a.actions = actions; a.logp = logp; a.value = value;
+    a.off_wa = layout_h[0]; a.off_ba = layout_h[1]; a.off_wc = layout_h[2]; a.off_bc = layout_h[3]; a.off_ls = layout_h[4];
+    a.N = N; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0; a.n_iter = 0;
+    return head_act_launch(a, (hipStream_t)stream);
+}
+
+// ---- the layered rollout step: per net, the hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand
+// copies (conv.hip: aurppo_mlp_layered_prep_f32), then K14.  2 L + 1 launches; the value alone: the critic only, L + 1.
+extern "C" size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden) {
+    if (N <= 0 || hidden <= 0) return 0;
+    return 4 * layered_act_plane_bytes(N, hidden);      // two activation planes per net, written in turn
+}
+
+extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                          int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                          float* logp, float* value, const void* wop, void* workspace, void* stream) {
+    AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL,
+                   "aurppo_mlp_layered_act_f32: null pointer");
+    AURPPO_REQUIRE(N > 0 && D > 0 && D % 16 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_act_f32: N=%d, D=%d (a multiple of 16), %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_act_f32: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", hidden, A);
+    AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
+                   "aurppo_mlp_layered_act_f32: obs / operand copies not 16-byte / workspace not 64-byte aligned");
+    AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
+                   AURPPO_EINVAL, "aurppo_mlp_layered_act_f32: noise / outputs not 4-byte aligned");
+    const int L = num_layers, per = 2 * (L + 1), n_off = 2 * per + 1;
+    for (int i = 0; i < n_off; ++i) {
+        const int net = i / per, j = i % per, l = j / 2;
+        const int out = i == 2 * per ? 0 : (l < L ? hidden : (net ? 1 : A));
+        long long need;
+        if (i == 2 * per) need = continuous ? A : 0;
+        else if (j & 1) need = out;
+        else need = (long long)out * (l == 0 ? D : hidden);
+        AURPPO_REQUIRE(offsets[i] >= 0 && (long long)offsets[i] + need <= (long long)n_params, AURPPO_EINVAL,
+                       "aurppo_mlp_layered_act_f32: layout offset %d (%d) outside the bucket of %d", i, offsets[i], n_params);
+    }
+    const size_t plane = layered_act_plane_bytes(N, hidden);
+    const char* const wbase = reinterpret_cast<const char*>(wop);
+    const size_t net_wop = aurppo_linear_wop_bytes(D, hidden) + (size_t)(L - 1) * aurppo_linear_wop_bytes(hidden, hidden);
+    const float* last[2] = {nullptr, nullptr};
+    for (int net = noise ? 0 : 1; net < 2; ++net) {
+        const int* o = offsets + net * per;
+        const char* w = wbase + net * net_wop;
+        const float* x = obs;
+        for (int l = 0; l < L; ++l) {
+            const int K = l ? hidden : D;
+            float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane);
+            const int rc = aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream);
+            if (rc != AURPPO_OK) return rc;
+            w += aurppo_linear_wop_bytes(K, hidden);
+            x = y;
+        }
+        last[net] = x;
+    }
+    HeadActArgs a;
+    a.hA = last[0]; a.hC = last[1]; a.noise = noise; a.params = params;
+    a.actions = actions; a.logp = logp; a.value = value;
+    a.off_wa = offsets[2 * L]; a.off_ba = offsets[2 * L + 1]; a.off_wc = offsets[per + 2 * L]; a.off_bc = offsets[per + 2 * L + 1];
+    a.off_ls = offsets[2 * per];
+    a.N = N; a.H = hidden; a.A = A; a.continuous = continuous ? 1 : 0; a.n_iter = 0;
+    return head_act_launch(a, (hipStream_t)stream);
 }

@@ -452,15 +452,22 @@ def _optr(t, dtype=torch.float32):
 # The argument order of the fused-step family (include/aurppo.h) lives in the builders below and nowhere else in this layer; each
 # returns one run of a call's arguments, and _lib._declare spells the matching run of argtypes.  A transposition inside a run of
 # same-typed pointers raises nothing on the host and faults on the GPU: tests/test_hip_ops_calls.py pins what every call passes.
+def _layout_shape(layout, rows):
+    """The offsets as a ``c_int`` array and the shape run: rows (M or N), D, A, continuous, hidden and, for every layout but the
+    default 64-64 one, num_layers."""
+    lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
+    shape = (rows, layout["D"], layout["A"], int(layout["continuous"]), layout["hidden"])
+    return lay, shape + ((layout["num_layers"],) if layout.get("wide") or layout.get("layered") else ())
+
+
 def _mlp_family(lib, layout, rows, device, n_ws):
     """What differs between the default 64-64 layout (K7 / K8) and the wide ones (K7w / K8w): the entry points' infix (also the
     workspace kind), the workspace for ``n_ws`` parameters (K8 has none: ``n_ws=None``), the offsets as a ``c_int`` array, and the
     shape arguments: rows (M or N), D, A, continuous, hidden and, for the wide layouts, num_layers."""
-    lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
-    shape = (rows, layout["D"], layout["A"], int(layout["continuous"]), layout["hidden"])
+    lay, shape = _layout_shape(layout, rows)
     if layout.get("wide"):
         ws = _workspace("mlp_wide", lib.aurppo_mlp_wide_workspace_bytes(n_ws, layout["hidden"], layout["D"]), device)
-        return "mlp_wide", ws, lay, shape + (layout["num_layers"],)
+        return "mlp_wide", ws, lay, shape
     ws = _workspace("mlp", lib.aurppo_mlp_workspace_bytes(n_ws), device) if n_ws is not None else None
     return "mlp", ws, lay, shape
 
@@ -661,19 +668,10 @@ def mlp_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None)
     (Gaussian head) or (N,) uniform draws (Categorical head); None -> value only.  Outputs may be rows of
     the rollout buffer.  Returns (actions, logp, value)."""
     lib = _lib_or_raise()
-    N, D, A, cont = obs.shape[0], layout["D"], layout["A"], layout["continuous"]
-    dev = obs.device
-    if value is None:
-        value = torch.empty(N, dtype=torch.float32, device=dev)
-    if noise is not None:
-        if actions is None:
-            actions = torch.empty((N, A) if cont else (N,), dtype=torch.float32, device=dev)
-        if logp is None:
-            logp = torch.empty(N, dtype=torch.float32, device=dev)
-        if noise.numel() != (N * A if cont else N) or actions.numel() != noise.numel() or logp.numel() != N:
-            raise ValueError("mlp_act: noise / output shapes do not match the policy")
-    if obs.shape[-1] != D or value.numel() != N:
-        raise ValueError("mlp_act: obs / value shapes do not match the policy")
+    N, dev = obs.shape[0], obs.device
+    if obs.shape[-1] != layout["D"]:
+        raise ValueError("mlp_act: obs shape does not match the policy")
+    actions, logp, value = _act_outputs("mlp_act", N, layout, noise, actions, logp, value, dev)
     # K8w keeps the operand-order copy of the weights in a workspace sized for no parameters; K8 has none
     family, ws, lay, shape = _mlp_family(lib, layout, N, dev, 0 if layout.get("wide") else None)
     name = f"aurppo_{family}_act_f32"
@@ -1100,3 +1098,103 @@ def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip
             torch.sum(h[l - 1], 0, out=flat_grad[o[2 * l - 1]:o[2 * l - 1] + Hd])
         _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(h[0]), obs_p, idx_p, at(g0, o[0]), M, Hd, D, wgw, st), "aurppo_linear_wgrad_rows_f32")
     return out_scalars
+
+
+# ------------------------------------------------------------------ K14 + the layered rollout step
+def head_act_layout(layout):
+    """K14's five offsets out of a layered (or K7w) layout: actor head w, b; critic head w, b; actor_logstd."""
+    return head_layout(layout)[:5]
+
+
+def _act_outputs(who, N, layout, noise, actions, logp, value, device):
+    """``mlp_act``'s output rule: the value always; with noise, the actions ((N, A), or (N,) indices for the Categorical head) and
+    the log-prob.  Allocates what the caller did not pass; raises ValueError on a mismatch."""
+    A, cont = layout["A"], layout["continuous"]
+    if value is None:
+        value = torch.empty(N, dtype=torch.float32, device=device)
+    if noise is not None:
+        if actions is None:
+            actions = torch.empty((N, A) if cont else (N,), dtype=torch.float32, device=device)
+        if logp is None:
+            logp = torch.empty(N, dtype=torch.float32, device=device)
+        if noise.numel() != (N * A if cont else N) or actions.numel() != noise.numel() or logp.numel() != N:
+            raise ValueError(f"{who}: noise / output shapes do not match the policy")
+    if value.numel() != N:
+        raise ValueError(f"{who}: value shape does not match the policy")
+    return actions, logp, value
+
+
+def _act_outputs_ptrs(noise, actions, logp, value):
+    """actions, logp, value (the first two NULL without noise)."""
+    return (_optr(actions if noise is not None else None), _optr(logp if noise is not None else None), _ptr(value))
+
+
+def head_act(hA, hC, noise, flat_param, layout, actions=None, logp=None, value=None):
+    """K14: both heads, the sampled action, its log-prob and the value from the last hidden activations ``hA`` / ``hC`` (N, H).
+    ``noise`` as ``mlp_act``'s; None -> the value only (``hA`` may then be None).  Returns (actions, logp, value)."""
+    lib = _lib_or_raise()
+    N, Hd = hC.shape
+    if Hd != layout["hidden"] or (noise is not None and (hA is None or hA.shape != (N, Hd))):
+        raise ValueError("head_act: activation shapes do not match the policy")
+    actions, logp, value = _act_outputs("head_act", N, layout, noise, actions, logp, value, hC.device)
+    _bucket_fits(layout["n_params"], flat_param, who="head_act")
+    lay = (C.c_int * 5)(*head_act_layout(layout))
+    _check(lib.aurppo_head_act_f32(_optr(hA if noise is not None else None), _ptr(hC), _optr(noise), N, Hd, layout["A"],
+                                   int(layout["continuous"]), _ptr(flat_param), lay, layout["n_params"],
+                                   *_act_outputs_ptrs(noise, actions, logp, value), _stream()), "aurppo_head_act_f32")
+    return actions, logp, value
+
+
+_layered_wop_cache = {}
+
+
+def _layered_wop(lib, layout, device):
+    """The prepared-weights buffer of a layered shape: a tensor of its own per (shape, device) -- not ``_workspace("conv")``, which
+    every other linear call overwrites."""
+    D, Hd, L = layout["D"], layout["hidden"], layout["num_layers"]
+    key = (D, Hd, L, device.index if device.index is not None else torch.cuda.current_device())
+    wop = _layered_wop_cache.get(key)
+    if wop is None:
+        nb = lib.aurppo_mlp_layered_wop_bytes(D, Hd, L)
+        if nb == 0:
+            raise RuntimeError("aur_ppo_amd: aurppo_mlp_layered_prep_f32 does not take this shape")
+        wop = _layered_wop_cache[key] = torch.empty(nb, dtype=torch.uint8, device=device)
+    return wop
+
+
+def mlp_layered_prepare(flat_param, layout):
+    """The operand-order copies of the 2 L hidden-layer matrices of a layered policy, built from ``flat_param`` as it stands now
+    (k_conv_prep, 2 L launches) into the shape's prepared buffer, which is returned: pass it as ``wop`` to ``mlp_layered_act``
+    for as long as the parameters stand still (a rollout).  No host synchronisation; capturable."""
+    lib = _lib_or_raise()
+    if not layout.get("layered"):
+        raise ValueError("mlp_layered_prepare: not a layered layout")
+    _bucket_fits(layout["n_params"], flat_param, who="mlp_layered_prepare")
+    wop = _layered_wop(lib, layout, flat_param.device)
+    lay, _ = _layout_shape(layout, 0)
+    _check(lib.aurppo_mlp_layered_prep_f32(_ptr(flat_param), lay, layout["n_params"], layout["D"], layout["hidden"], layout["num_layers"],
+                                           C.c_void_p(wop.data_ptr()), _stream()), "aurppo_mlp_layered_prep_f32")
+    return wop
+
+
+def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None, wop=None):
+    """``mlp_act``'s contract and return value for the MLP policies wider than the fused kernels (``mlp_layered_layout``): per net the
+    hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand copies ``wop`` (``mlp_layered_prepare``;
+    None: prepared here, from ``flat_param`` as it stands), then K14.  No host synchronisation; capturable."""
+    lib = _lib_or_raise()
+    N = obs.shape[0]
+    if not layout.get("layered") or obs.dim() != 2 or obs.shape[1] != layout["D"]:
+        raise ValueError("mlp_layered_act: obs shape does not match the policy")
+    dev = obs.device
+    actions, logp, value = _act_outputs("mlp_layered_act", N, layout, noise, actions, logp, value, dev)
+    _bucket_fits(layout["n_params"], flat_param, who="mlp_layered_act")
+    if wop is None:
+        wop = mlp_layered_prepare(flat_param, layout)
+    elif wop.numel() * wop.element_size() < lib.aurppo_mlp_layered_wop_bytes(layout["D"], layout["hidden"], layout["num_layers"]):
+        raise ValueError("mlp_layered_act: the prepared buffer is smaller than the policy's operand copies")
+    lay, shape = _layout_shape(layout, N)
+    ws = _workspace("layered_act", lib.aurppo_mlp_layered_act_workspace_bytes(N, layout["hidden"]), dev)
+    _check(lib.aurppo_mlp_layered_act_f32(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"],
+                                          *_act_outputs_ptrs(noise, actions, logp, value), C.c_void_p(wop.data_ptr()), *_ws_stream(ws)),
+           "aurppo_mlp_layered_act_f32")
+    return actions, logp, value

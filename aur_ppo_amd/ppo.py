@@ -59,6 +59,7 @@ class torch_buffer:
 
 
 LAYERED_STEP_DEFAULT = "0"      # AURPPO_LAYERED_STEP when the environment does not set it
+LAYERED_ACT_DEFAULT = "0"       # AURPPO_LAYERED_ACT when the environment does not set it
 
 
 class ppo(FlatAdamMixin):
@@ -147,11 +148,19 @@ class ppo(FlatAdamMixin):
             self._mlp = ops.mlp_layout(self.policy, self.bucket)
         # MLP policies wider than the fused kernels: layer-at-a-time products + K13 in place of gather / evaluate / autograd in
         # the update.  Opt-in (AURPPO_LAYERED_STEP=1) until it is timed against the per-op route on the bench shapes.
-        # ``_mlp`` stays None: rollout and bootstrap keep the torch modules.
+        # ``_mlp`` stays None: rollout and bootstrap keep the torch modules unless the switch below is on.
         self._mlp_layered = None
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_layout")
                 and os.environ.get("AURPPO_LAYERED_STEP", LAYERED_STEP_DEFAULT) != "0"):
             self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket)
+        # The same policies' rollout step and bootstrap: k_linear from operand copies prepared once per rollout + K14
+        # (ops.mlp_layered_act) in place of policy.evaluate / policy.value.  Opt-in (AURPPO_LAYERED_ACT=1), independent of the
+        # update's switch above; ``_mlp`` stays None.
+        self._mlp_layered_act = None
+        if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_act")
+                and os.environ.get("AURPPO_LAYERED_ACT", LAYERED_ACT_DEFAULT) != "0"):
+            self._mlp_layered_act = ops.mlp_layered_layout(self.policy, self.bucket)
+        self._act_wop = None       # the rollout's prepared operand copies (layered act), None outside _rollout_steps
         # the flat bucket holds the MLP policy and nothing else (up to alignment padding): K7 + clip + Adam can chain
         self._bucket_is_policy = self._mlp is not None and self.bucket.numel == self._mlp["n_params"]
         self._ro_state, self._ro_graph, self._ro_obs, self._ro_done, self._ro_out = 0, None, None, None, None   # captured rollout
@@ -260,18 +269,31 @@ class ppo(FlatAdamMixin):
             return env
         return thunk
 
+    def _act_layout(self):
+        """The layout the rollout step and the bootstrap run a kernel with -- K8 / K8w's, or the layered act's -- or None (torch modules)."""
+        if self._mlp is not None:
+            return self._mlp if hasattr(self.ops, "mlp_act") else None
+        return self._mlp_layered_act
+
+    def _act(self, lay, obs, noise, *outs):
+        """K8 / K8w in one launch, or the layered rollout step (from the rollout's prepared copies when ``_rollout_steps`` made them)."""
+        if lay.get("layered"):
+            return self.ops.mlp_layered_act(obs, noise, self.bucket.flat_param, lay, *outs, wop=self._act_wop if noise is not None else None)
+        return self.ops.mlp_act(obs, noise, self.bucket.flat_param, lay, *outs)
+
     def rewards_to_go(self, step, next_obs, global_step, writer):
-        if self._mlp is not None and hasattr(self.ops, "mlp_act"):
+        lay = self._act_layout()
+        if lay is not None:
             # K8: forward of both nets, sampling, log-prob and the three buffer row stores in one launch
-            cont = self._mlp["continuous"]
+            cont = lay["continuous"]
             pre = getattr(self, "_rollout_noise", None)      # train() draws the whole rollout's noise in one call
             if pre is not None and step < pre.shape[0]:
                 noise = pre[step]
             else:
-                noise = (torch.randn((self.num_envs, self._mlp["A"]), device=self.device) if cont
+                noise = (torch.randn((self.num_envs, lay["A"]), device=self.device) if cont
                          else torch.rand(self.num_envs, device=self.device))
-            action, _, _ = self.ops.mlp_act(next_obs.to(self.device).contiguous(), noise, self.bucket.flat_param, self._mlp,
-                                            self.buffer.actions[step], self.buffer.log_probs[step], self.buffer.values[step])
+            action, _, _ = self._act(lay, next_obs.to(self.device).contiguous(), noise,
+                                     self.buffer.actions[step], self.buffer.log_probs[step], self.buffer.values[step])
             if not cont:
                 action = action.long()
         else:
@@ -301,16 +323,22 @@ class ppo(FlatAdamMixin):
 
     def _rollout_steps(self, next_obs, next_done, global_step, writer):
         """The T rollout steps of src/ppo.py:201-205."""
-        if self._mlp is not None and hasattr(self.ops, "mlp_act"):
+        lay = self._act_layout()
+        if lay is not None:
             # one generator call per rollout instead of one per step (the sampling noise K8 consumes)
-            self._rollout_noise = (torch.randn((self.num_steps, self.num_envs, self._mlp["A"]), device=self.device)
-                                   if self._mlp["continuous"] else torch.rand((self.num_steps, self.num_envs), device=self.device))
+            self._rollout_noise = (torch.randn((self.num_steps, self.num_envs, lay["A"]), device=self.device)
+                                   if lay["continuous"] else torch.rand((self.num_steps, self.num_envs), device=self.device))
+            if lay.get("layered"):
+                # the parameters stand still for the T steps: one set of operand-order copies per rollout (inside a captured
+                # rollout too, so a replay prepares from the updated parameters)
+                self._act_wop = self.ops.mlp_layered_prepare(self.bucket.flat_param, lay)
         for step in range(0, self.num_steps):
             global_step += 1 * self.num_envs * self.world
             self.buffer.states[step] = next_obs
             self.buffer.terminals[step] = next_done
             next_obs, next_done = self.rewards_to_go(step, next_obs, global_step, writer)
         self._rollout_noise = None      # a stand-alone rewards_to_go() call draws fresh noise, as upstream does
+        self._act_wop = None            # ... and prepares for itself: nothing can go stale
         return next_obs, next_done, global_step
 
     def _rollout(self, next_obs, next_done, global_step, writer):
@@ -318,7 +346,7 @@ class ppo(FlatAdamMixin):
         policy (K8) and one process, the T steps -- ~10 launches each, host-bound -- are captured once as a hipGraph and
         replayed: rollout 1 runs eagerly, rollout 2 is captured, later ones replay."""
         env = self.envs
-        ok = (self.use_graph and self.world == 1 and self._mlp is not None and hasattr(self.ops, "mlp_act")
+        ok = (self.use_graph and self.world == 1 and self._act_layout() is not None
               and getattr(env, "device_native", False) and getattr(env, "capturable", False) and self.device.type == "cuda")
         if not ok or self._ro_state == 0:
             self._ro_state = 1 if ok else 0
@@ -365,8 +393,9 @@ class ppo(FlatAdamMixin):
 
     def advantages(self, next_obs, next_done):
         with torch.no_grad():
-            if self._mlp is not None and hasattr(self.ops, "mlp_act"):
-                _, _, next_value = self.ops.mlp_act(next_obs.contiguous(), None, self.bucket.flat_param, self._mlp)
+            lay = self._act_layout()
+            if lay is not None:
+                _, _, next_value = self._act(lay, next_obs.contiguous(), None)
             else:
                 next_value = self.policy.value(next_obs)
             if self.gae:

@@ -314,6 +314,37 @@ int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC
                         int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
                         float* out_scalars, void* workspace, void* stream);
 
+/* ---- K14 and the layered rollout step: K8's contract for the MLP policies the fused kernels do not cover ------------------
+ * Replaces `action, logprob, _, value = policy.evaluate(next_obs)` under no_grad and the three buffer row stores behind it
+ * (src/ppo.py:104-108), and with noise == NULL the bootstrap `policy.value(next_obs)` (src/ppo.py:161), for hidden_dim > 128 or a
+ * state of more than 128 floats.  The parameters stand still for the T steps of a rollout, so the operand-order copies of the
+ * 2 L hidden-layer matrices are built once (aurppo_mlp_layered_prep_f32) and every step runs from them.
+ *   offsets: the layered layout, as K7w's layout_h: for the actor, then the critic: {w_0, b_0, ..., w_L, b_L}, then actor_logstd --
+ *     4 * (num_layers + 1) + 1 float offsets into the bucket of n_params floats; each is range-checked.
+ *   wop: aurppo_mlp_layered_wop_bytes(D, hidden, num_layers) bytes (0: shape not supported), 16-byte aligned, caller-owned:
+ *     aurppo_mlp_layered_prep_f32 fills it (2 L launches) and it stays valid until the parameters change.
+ *   aurppo_mlp_layered_act_f32: per net L products with bias and tanh in the epilogue from the prepared copies, then K14: 2 L + 1
+ *     launches; noise == NULL: the critic only, L + 1 launches, and actions / logp may be NULL.  obs (N, D) 16-byte aligned;
+ *     noise (N, A) standard-normal draws (a = mu + exp(logstd) * eps) or (N,) uniform [0, 1) draws (inverse CDF of
+ *     softmax(logits)); actions (N, A) | (N,), logp (N,), value (N,) go wherever the caller points them; noise and the outputs
+ *     need 4-byte alignment only.  workspace: aurppo_mlp_layered_act_workspace_bytes(N, hidden) bytes, 64-byte aligned (the
+ *     activations).  The log-prob is bit for bit the one aurppo_head_ppo_f32 forms from the stored action at the same parameters.
+ *   aurppo_head_act_f32: K14 alone, from the last hidden activations hA, hC (N, H), 16-byte aligned (hA may be NULL without
+ *     noise); layout_h: 5 float offsets {actor head weight (A, H), actor head bias, critic head weight (1, H), critic head bias,
+ *     actor_logstd (ignored for the Categorical head)}.
+ * Limits (AURPPO_ESHAPE otherwise): hidden / H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16), D a multiple of 16,
+ * num_layers 1..16. */
+size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers);
+int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers, void* wop,
+                                void* stream);
+size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden);
+int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                               int num_layers, const float* params, const int* offsets, int n_params, float* actions, float* logp,
+                               float* value, const void* wop, void* workspace, void* stream);
+int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
+                        const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
+                        void* stream);
+
 /* K12 -- the weight gradient of the 3x3 convolution of aurppo_conv3x3_f32 (src/nets/base_cnns.py:32-45, src/nets/equiv.py:12-62;
  * what loss.backward() leaves in <conv>.weight.grad, src/robot_ppo.py:389): dw (Co, Ci, 3, 3) from x (B, Ci, H, W) and the
  * output gradient dy (B, Co, H + 2 pad - 2, W + 2 pad - 2), NCHW fp32, as a product over the batch's output pixels on bf16 MFMAs
