@@ -44,6 +44,27 @@ static inline int aurppo_device_slot() {
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
     return d;
 }
+// Launch of a kernel with dynamic LDS that may be above the default limit: the first launch per device sets the kernel's
+// hipFuncAttributeMaxDynamicSharedMemorySize to lds_cap, whatever this launch needs; every launch asks for lds (<= lds_cap; most
+// callers pass the same figure twice) and is checked under `name`.  Keyed on the kernel itself, so every instantiation owns its
+// per-device flags.
+template <auto Kernel, class Args>
+int launch_dyn_lds(const char* name, int grid, int threads, size_t lds, size_t lds_cap, hipStream_t s, const Args& a) {
+    static bool done[kMaxDevices] = {};
+    const int dslot = aurppo_device_slot();
+    if (!done[dslot]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);
+        if (e != hipSuccess) {
+            aurppo_set_error("hipFuncSetAttribute(%s, hipFuncAttributeMaxDynamicSharedMemorySize, %d) failed: %s", name, (int)lds_cap,
+                             hipGetErrorString(e));
+            return AURPPO_EHIP;
+        }
+        done[dslot] = true;
+    }
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, a);
+    AURPPO_LAUNCH_CHECK(name);
+    return AURPPO_OK;
+}
 // CUs of the calling thread's current device (asked once per device; `fallback` if the runtime reports none), or a negative AURPPO_E*
 // code with the error set (api.hip)
 int aurppo_cu_count(int fallback);

@@ -18,8 +18,9 @@
 //     per workgroup.  k_head_fold sums the slabs in workgroup order (fp64 accumulator, rounded once) into the bucket's
 //     gradient and folds the nine scalars.  The grid depends on (M, H) only: two launches on the same inputs give the same bits.
 // K14 (k_head_act, below K13's host helpers) is the forward half alone for the rollout step: same layout, same head expressions in the
-// same order, then sampling -- so the log-prob it stores is the one K13 forms from the stored action.  aurppo_mlp_layered_act_f32 at
-// the end of the file is the whole rollout step: k_linear from prepared operand copies (conv.hip), then K14.
+// same order, then sampling -- so the log-prob it stores is the one K13 forms from the stored action.  One dispatcher by threads per
+// row launches either kernel (launch_k_head_ppo / launch_k_head_act), one function checks a layout's bounds, one fills K14's arguments.
+// aurppo_mlp_layered_act_f32 at the end of the file is the whole rollout step: k_linear from prepared operand copies (conv.hip), then K14.
 #include "mlp_common.h"
 
 namespace {
@@ -88,6 +89,12 @@ __device__ __forceinline__ void fma4(float4& acc, float s, const float4 v) {
     acc.w = __builtin_fmaf(s, v.w, acc.w);
 }
 
+// The forward half (staging, thread geometry, dot4 products, butterfly, in-order sum over a row's waves, Categorical opening) stays
+// written out in both k_head_ppo and k_head_act.  As shared __forceinline__ pieces called by both it kept every bit (build_bitdiff:
+// identical) but was taken out again: k_head_ppo with a Categorical head ran 1528 -> 1547 us at H = 512 and 3061 -> 3081 us at
+// H = 1024 (M = 131072), above the two-copy build in every one of four alternating rounds, and no single piece carried it
+// (profiles/refactor_head_rollout.txt, section 5).  tests/test_layered_act_fp64_gpu.py and tools/build_bitdiff.py hold the two copies
+// to the same bits.
 template <int TPR>      // threads per row: the power of two >= H / 4, 8 ... 256
 __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
     constexpr int GPW = kHT / TPR;                     // rows a workgroup works on at a time
@@ -554,16 +561,8 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             float* const out = a.actions + (size_t)row * A;
             float logp = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                if (k < A) {
-                    const float ls = s_small[16 + k], sd = s_small[32 + k];
-                    const float mu = p[k] + s_small[k];
-                    const float act = mu + sd * eps[k];
-                    out[k] = act;
-                    const float z = act - mu;                              // as k_head_ppo forms it from the stored action
-                    logp += gauss_logp_var(z, sd * sd, ls);
-                }
-            }
+            for (int k = 0; k < 16; ++k)
+                if (k < A) logp += gauss_sample(p[k] + s_small[k], s_small[32 + k], s_small[16 + k], eps[k], out[k]);
             a.logp[row] = logp;
         } else {
             float mx = -INFINITY;
@@ -612,33 +611,49 @@ int head_act_grid(int N, int H) {
     return (int)g;
 }
 
-int head_act_launch(HeadActArgs a, hipStream_t s) {
-    const int tpr = head_tpr(a.H), gpw = kHT / tpr, grid = head_act_grid(a.N, a.H);
-    a.n_iter = (int)(((long long)a.N + (long long)grid * gpw - 1) / ((long long)grid * gpw));
-    const size_t lds = (size_t)(a.A + 1) * a.H * sizeof(float);
-    constexpr size_t kMaxLds = (size_t)17 * 1024 * sizeof(float);
-    static bool attr_set[kMaxDevices][6] = {};
-    const int dslot = aurppo_device_slot();
-#define AURPPO_HEAD_ACT_LAUNCH(T, SLOT)                                                                                          \
-    do {                                                                                                                         \
-        if (!attr_set[dslot][SLOT]) {                                                                                            \
-            AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_act<T>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)kMaxLds));                                                                   \
-            attr_set[dslot][SLOT] = true;                                                                                        \
-        }                                                                                                                        \
-        hipLaunchKernelGGL(k_head_act<T>, dim3(grid), dim3(kHT), lds, s, a);                                                     \
-    } while (0)
-    switch (tpr) {
-        case 8: AURPPO_HEAD_ACT_LAUNCH(8, 0); break;
-        case 16: AURPPO_HEAD_ACT_LAUNCH(16, 1); break;
-        case 32: AURPPO_HEAD_ACT_LAUNCH(32, 2); break;
-        case 64: AURPPO_HEAD_ACT_LAUNCH(64, 3); break;
-        case 128: AURPPO_HEAD_ACT_LAUNCH(128, 4); break;
-        default: AURPPO_HEAD_ACT_LAUNCH(256, 5); break;
+// The TPR build of a head kernel for a.H, on `grid` workgroups with its (A + 1) x H weights as dynamic LDS: launch_k_head_ppo,
+// launch_k_head_act.  The limit is raised to the largest shape's, once per build and device.
+#define AURPPO_HEAD_DISPATCH(K, ARGS)                                                                                  \
+    int launch_##K(const ARGS& a, int grid, hipStream_t s) {                                                           \
+        const size_t lds = (size_t)(a.A + 1) * a.H * sizeof(float), cap = (size_t)17 * 1024 * sizeof(float);           \
+        switch (head_tpr(a.H)) {                                                                                       \
+            case 8: return launch_dyn_lds<K<8>>(#K, grid, kHT, lds, cap, s, a);                                        \
+            case 16: return launch_dyn_lds<K<16>>(#K, grid, kHT, lds, cap, s, a);                                      \
+            case 32: return launch_dyn_lds<K<32>>(#K, grid, kHT, lds, cap, s, a);                                      \
+            case 64: return launch_dyn_lds<K<64>>(#K, grid, kHT, lds, cap, s, a);                                      \
+            case 128: return launch_dyn_lds<K<128>>(#K, grid, kHT, lds, cap, s, a);                                    \
+            default: return launch_dyn_lds<K<256>>(#K, grid, kHT, lds, cap, s, a);                                     \
+        }                                                                                                              \
     }
-#undef AURPPO_HEAD_ACT_LAUNCH
-    AURPPO_LAUNCH_CHECK("k_head_act");
+AURPPO_HEAD_DISPATCH(k_head_act, HeadActArgs)
+AURPPO_HEAD_DISPATCH(k_head_ppo, HeadArgs)
+#undef AURPPO_HEAD_DISPATCH
+
+// rows each of the grid's row groups takes: ceil(rows / (grid * rows per workgroup))
+int head_n_iter(int rows, int H, int grid) {
+    const long long per = (long long)grid * (kHT / head_tpr(H));
+    return (int)((rows + per - 1) / per);
+}
+
+// layout[i] .. layout[i] + need[i] lies in the bucket, for the first `count` offsets
+int head_layout_check(const int* layout, const long long* need, int count, int n_params, const char* who) {
+    for (int i = 0; i < count; ++i)
+        AURPPO_REQUIRE(layout[i] >= 0 && (long long)layout[i] + need[i] <= (long long)n_params, AURPPO_EINVAL,
+                       "%s: layout offset %d (%d) outside the bucket of %d", who, i, layout[i], n_params);
     return AURPPO_OK;
+}
+
+// K14 on checked operands; lay = {actor head w, b; critic head w, b; actor_logstd}
+int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,
+                    const int* lay, float* actions, float* logp, float* value, hipStream_t s) {
+    HeadActArgs a;
+    a.hA = hA; a.hC = hC; a.noise = noise; a.params = params;
+    a.actions = actions; a.logp = logp; a.value = value;
+    a.off_wa = lay[0]; a.off_ba = lay[1]; a.off_wc = lay[2]; a.off_bc = lay[3]; a.off_ls = lay[4];
+    a.N = N; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0;
+    const int grid = head_act_grid(N, H);
+    a.n_iter = head_n_iter(N, H, grid);
+    return launch_k_head_act(a, grid, s);
 }
 
 size_t layered_act_plane_bytes(int N, int hidden) { return ((size_t)N * hidden * sizeof(float) + 63) & ~(size_t)63; }
@@ -669,9 +684,7 @@ extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA,
     a.off_wa = layout_h[0]; a.off_ba = layout_h[1]; a.off_wc = layout_h[2]; a.off_bc = layout_h[3]; a.off_ls = layout_h[4];
     a.off_bla = layout_h[5]; a.off_blc = layout_h[6];
     const long long need[7] = {(long long)A * H, A, H, 1, continuous ? A : 0, H, H};
-    for (int i = 0; i < 7; ++i)
-        AURPPO_REQUIRE(layout_h[i] >= 0 && (long long)layout_h[i] + need[i] <= (long long)n_params, AURPPO_EINVAL,
-                       "aurppo_head_ppo_f32: layout offset %d (%d) outside the bucket of %d", i, layout_h[i], n_params);
+    if (const int rc = head_layout_check(layout_h, need, 7, n_params, "aurppo_head_ppo_f32")) return rc;
     const HeadWs w = head_carve(workspace, M, H, A);
     a.hA = hA; a.hC = hC; a.gzA = gzA; a.gzC = gzC;
     a.actions = actions; a.rec = reinterpret_cast<const float4*>(rec); a.rec_stride = actions ? 1 : 4; a.aw = aw;
@@ -680,37 +693,15 @@ extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA,
     a.slab_stride = head_slab_stride(H, A);
     a.M = M; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0;
     a.h = make_hyper(M, clip, ent_coef, vf_coef, norm_adv, vloss_mode);
-    const int tpr = head_tpr(H), gpw = kHT / tpr, grid = head_grid(M, H);
-    a.n_iter = (int)(((long long)M + (long long)grid * gpw - 1) / ((long long)grid * gpw));
+    const int grid = head_grid(M, H);
+    a.n_iter = head_n_iter(M, H, grid);
     int n_stat = (M + kHT * 4 - 1) / (kHT * 4);
     if (n_stat > kHeadStat) n_stat = kHeadStat;
     a.n_stat = n_stat;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_head_stats, dim3(n_stat), dim3(kHT), 0, s, a.rec, a.rec_stride, idx, M, w.stats);
     AURPPO_LAUNCH_CHECK("k_head_stats");
-    const size_t lds = (size_t)(A + 1) * H * sizeof(float);
-    constexpr size_t kMaxLds = (size_t)17 * 1024 * sizeof(float);
-    static bool attr_set[kMaxDevices][6] = {};
-    const int dslot = aurppo_device_slot();
-#define AURPPO_HEAD_LAUNCH(T, SLOT)                                                                                              \
-    do {                                                                                                                         \
-        if (!attr_set[dslot][SLOT]) {                                                                                            \
-            AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_ppo<T>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)kMaxLds));                                                                   \
-            attr_set[dslot][SLOT] = true;                                                                                        \
-        }                                                                                                                        \
-        hipLaunchKernelGGL(k_head_ppo<T>, dim3(grid), dim3(kHT), lds, s, a);                                                     \
-    } while (0)
-    switch (tpr) {
-        case 8: AURPPO_HEAD_LAUNCH(8, 0); break;
-        case 16: AURPPO_HEAD_LAUNCH(16, 1); break;
-        case 32: AURPPO_HEAD_LAUNCH(32, 2); break;
-        case 64: AURPPO_HEAD_LAUNCH(64, 3); break;
-        case 128: AURPPO_HEAD_LAUNCH(128, 4); break;
-        default: AURPPO_HEAD_LAUNCH(256, 5); break;
-    }
-#undef AURPPO_HEAD_LAUNCH
-    AURPPO_LAUNCH_CHECK("k_head_ppo");
+    if (const int rc = launch_k_head_ppo(a, grid, s)) return rc;
     const int n = head_slab_floats(H, A);
     hipLaunchKernelGGL(k_head_fold, dim3((n + 31) / 32 + 1), dim3(kHT), 0, s, a, grid, grads, out_scalars);
     AURPPO_LAUNCH_CHECK("k_head_fold");
@@ -730,15 +721,8 @@ extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float
     AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
                    AURPPO_EINVAL, "aurppo_head_act_f32: noise / outputs not 4-byte aligned");
     const long long need[5] = {(long long)A * H, A, H, 1, continuous ? A : 0};
-    for (int i = 0; i < 5; ++i)
-        AURPPO_REQUIRE(layout_h[i] >= 0 && (long long)layout_h[i] + need[i] <= (long long)n_params, AURPPO_EINVAL,
-                       "aurppo_head_act_f32: layout offset %d (%d) outside the bucket of %d", i, layout_h[i], n_params);
-    HeadActArgs a;
-    a.hA = hA; a.hC = hC; a.noise = noise; a.params = params;
-    a.actions = actions; a.logp = logp; a.value = value;
-    a.off_wa = layout_h[0]; a.off_ba = layout_h[1]; a.off_wc = layout_h[2]; a.off_bc = layout_h[3]; a.off_ls = layout_h[4];
-    a.N = N; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0; a.n_iter = 0;
-    return head_act_launch(a, (hipStream_t)stream);
+    if (const int rc = head_layout_check(layout_h, need, 5, n_params, "aurppo_head_act_f32")) return rc;
+    return head_act_launch(hA, hC, noise, N, H, A, continuous, params, layout_h, actions, logp, value, (hipStream_t)stream);
 }
 
 // ---- the layered rollout step: per net, the hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand
@@ -790,11 +774,6 @@ extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, 
         }
         last[net] = x;
     }
-    HeadActArgs a;
-    a.hA = last[0]; a.hC = last[1]; a.noise = noise; a.params = params;
-    a.actions = actions; a.logp = logp; a.value = value;
-    a.off_wa = offsets[2 * L]; a.off_ba = offsets[2 * L + 1]; a.off_wc = offsets[per + 2 * L]; a.off_bc = offsets[per + 2 * L + 1];
-    a.off_ls = offsets[2 * per];
-    a.N = N; a.H = hidden; a.A = A; a.continuous = continuous ? 1 : 0; a.n_iter = 0;
-    return head_act_launch(a, (hipStream_t)stream);
+    const int lay[5] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per]};
+    return head_act_launch(last[0], last[1], noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
 }

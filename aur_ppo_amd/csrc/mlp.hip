@@ -172,13 +172,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int k = lj + 8 * q;
-            if (live && k < A) {
-                const float ls = sLs[k], sd = sSd[k], m = mu[k];
-                const float act = m + sd * a.noise[(size_t)n * A + k];
-                a.actions[(size_t)n * A + k] = act;
-                const float z = act - m;                                   // as evaluate() forms it: (a - mu)
-                lp += gauss_logp_var(z, sd * sd, ls);
-            }
+            if (live && k < A) lp += gauss_sample(mu[k], sSd[k], sLs[k], a.noise[(size_t)n * A + k], a.actions[(size_t)n * A + k]);
         }
         lp = sum8(lp);
         if (live && lj == 0) {
@@ -191,38 +185,11 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
         const int n = row0 + tid;
         const float* mu = sOut + tid * LDO;
         a.value[n] = sOut[(R + tid) * LDO];
-        if (a.noise) {
-            if (a.continuous) {
-                float lp = 0.0f;
-                for (int k = 0; k < A; ++k) {
-                    const float ls = a.params[a.L.logstd + k];
-                    const float eps = a.noise[(size_t)n * A + k];
-                    const float act = mu[k] + expf(ls) * eps;
-                    a.actions[(size_t)n * A + k] = act;
-                    const float z = act - mu[k];                       // as evaluate() forms it: (a - mu)
-                    const float sd = expf(ls);
-                    lp += gauss_logp_var(z, sd * sd, ls);
-                }
-                a.logp[n] = lp;
-            } else {
-                float mx = mu[0];
-                for (int k = 1; k < A; ++k) mx = fmaxf(mx, mu[k]);
-                float se = 0.0f;
-                for (int k = 0; k < A; ++k) se += expf(mu[k] - mx);
-                const float lse = mx + logf(se);
-                const float u = a.noise[n];
-                float cdf = 0.0f;
-                int pick = A - 1;
-                for (int k = 0; k < A; ++k) {
-                    cdf += expf(mu[k] - lse);
-                    if (u < cdf) {
-                        pick = k;
-                        break;
-                    }
-                }
-                a.actions[n] = (float)pick;
-                a.logp[n] = mu[pick] - lse;
-            }
+        if (a.noise) {      // Categorical: the Gaussian head has returned above
+            const float lse = cat_lse(mu, A);
+            float lp;
+            a.actions[n] = (float)cat_sample(mu, A, lse, a.noise[n], lp);
+            a.logp[n] = lp;
         }
     }
 }
@@ -933,14 +900,5 @@ extern "C" int aurppo_mlp_act_f32(const float* obs, const float* noise, int N, i
     a.obs = obs; a.noise = noise; a.params = params; a.actions = actions; a.logp = logp; a.value = value;
     a.N = N; a.D = D; a.A = A; a.continuous = continuous ? 1 : 0;
     if (const int rc = fill_layout(a.L, layout_h, continuous, n_params, "aurppo_mlp_act_f32")) return rc;
-    static bool attr_set[kMaxDevices] = {false};
-    const int dslot = aurppo_device_slot();
-    if (!attr_set[dslot]) {
-        AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_act),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)act_lds_bytes()));
-        attr_set[dslot] = true;
-    }
-    hipLaunchKernelGGL(k_mlp_act, dim3((N + R - 1) / R), dim3(kThreads), act_lds_bytes(), (hipStream_t)stream, a);
-    AURPPO_LAUNCH_CHECK("k_mlp_act");
-    return AURPPO_OK;
+    return launch_dyn_lds<k_mlp_act>("k_mlp_act", (N + R - 1) / R, kThreads, act_lds_bytes(), act_lds_bytes(), (hipStream_t)stream, a);
 }

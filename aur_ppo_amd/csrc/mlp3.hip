@@ -660,16 +660,7 @@ size_t mlp_step3_lds_bytes() { return (size_t)kDynBytes; }
 size_t mlp_step3_wop_bytes() { return sizeof(unsigned short) * (size_t)kWopElems; }
 
 int launch_mlp_step3(const MlpArgs& a, int grid, hipStream_t s) {
-    static bool attr_set[kMaxDevices] = {false};
-    const int dslot = aurppo_device_slot();
-    if (!attr_set[dslot]) {
-        AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_mlp_step3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)mlp_step3_lds_bytes()));
-        attr_set[dslot] = true;
-    }
-    hipLaunchKernelGGL(k_mlp_step3, dim3(grid), dim3(kThreads3), mlp_step3_lds_bytes(), s, a);
-    AURPPO_LAUNCH_CHECK("k_mlp_step3");
-    return AURPPO_OK;
+    return launch_dyn_lds<k_mlp_step3>("k_mlp_step3", grid, kThreads3, mlp_step3_lds_bytes(), mlp_step3_lds_bytes(), s, a);
 }
 
 }  // namespace aurppo_mlp

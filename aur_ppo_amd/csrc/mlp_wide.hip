@@ -476,11 +476,7 @@ __global__ __launch_bounds__(256, DUAL ? 2 : 1) void k_mlpw_step(const WideArgs 
                     }
                 } else {
                     const float* act = s.sAct + lrow * LDO;
-                    float mx = out[0];
-                    for (int k = 1; k < A; ++k) mx = fmaxf(mx, out[k]);
-                    float se = 0.0f;
-                    for (int k = 0; k < A; ++k) se += expf(out[k] - mx);
-                    const float lse = mx + logf(se);
+                    const float lse = cat_lse(out, A);
                     const int ai = (int)act[0];
                     float logp = 0.0f, ent = 0.0f;
                     for (int k = 0; k < A; ++k) {
@@ -1423,32 +1419,14 @@ __global__ __launch_bounds__(256) void k_mlpw_act(const WideArgs a) {
     if (!a.noise) return;
     if (a.continuous) {
         float lp = 0.0f;
-        for (int k = 0; k < A; ++k) {
-            const float ls = s.sLs[k], sd = s.sIvar[k];
-            const float act = mu[k] + sd * a.noise[(size_t)n * A + k];
-            a.out_actions[(size_t)n * A + k] = act;
-            const float z = act - mu[k];                               // as evaluate() forms it: (a - mu)
-            lp += gauss_logp_var(z, sd * sd, ls);
-        }
+        for (int k = 0; k < A; ++k)      // (sIvar holds exp(logstd) here: stage_small's last argument)
+            lp += gauss_sample(mu[k], s.sIvar[k], s.sLs[k], a.noise[(size_t)n * A + k], a.out_actions[(size_t)n * A + k]);
         a.out_logp[n] = lp;
     } else {
-        float mx = mu[0];
-        for (int k = 1; k < A; ++k) mx = fmaxf(mx, mu[k]);
-        float se = 0.0f;
-        for (int k = 0; k < A; ++k) se += expf(mu[k] - mx);
-        const float lse = mx + logf(se);
-        const float u = a.noise[n];
-        float cdf = 0.0f;
-        int pick = A - 1;
-        for (int k = 0; k < A; ++k) {
-            cdf += expf(mu[k] - lse);
-            if (u < cdf) {
-                pick = k;
-                break;
-            }
-        }
-        a.out_actions[n] = (float)pick;
-        a.out_logp[n] = mu[pick] - lse;
+        const float lse = cat_lse(mu, A);
+        float lp;
+        a.out_actions[n] = (float)cat_sample(mu, A, lse, a.noise[n], lp);
+        a.out_logp[n] = lp;
     }
 }
 
@@ -1502,17 +1480,6 @@ int check_shape(int D, int A, int continuous, int hidden, int num_layers, const 
     return AURPPO_OK;
 }
 
-template <class K>
-int launch_wide(K kernel, bool* attr_done, int grid, size_t lds_bytes, hipStream_t s, const WideArgs& a) {
-    if (!*attr_done) {
-        AURPPO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes));
-        *attr_done = true;
-    }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds_bytes, s, a);
-    return AURPPO_OK;
-}
-
 }  // namespace
 
 extern "C" size_t aurppo_mlp_wide_workspace_bytes(int n_params, int hidden, int state_dim) {
@@ -1544,6 +1511,12 @@ struct WideTail {   // the optimizer half of aurppo_mlp_wide_ppo_minibatch_f32
     int chained;               // the previous call named this idx as its next_idx: no prepare pass
 };
 }  // namespace
+
+// K7w / K8w launches ask for the LDS they raise the kernel's limit to
+template <auto Kernel>
+static int wide_launch(const char* name, int grid, size_t lds, hipStream_t s, const WideArgs& a) {
+    return launch_dyn_lds<Kernel>(name, grid, kThreads, lds, lds, s, a);
+}
 
 static int wide_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
                           int continuous, int hidden, int num_layers, const float* params, const int* layout_h, int n_params,
@@ -1586,7 +1559,7 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
                                a.rec_stride, idx, M, reinterpret_cast<double (*)[2]>(wv.stats), sb, wv.tile_counter);
         AURPPO_LAUNCH_CHECK("k_mlpw_prep");
     }
-    const int cus = aurppo_cu_count(kMaxGrid), dslot = aurppo_device_slot();
+    const int cus = aurppo_cu_count(kMaxGrid);
     if (cus < 0) return cus;
     const int n_tiles = (M + R - 1) / R;
     // 8 CUs left to the side stream's shuffle kernels, as K7; a both-net workgroup is built to share its CU with a second one
@@ -1596,25 +1569,20 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
     if (pairs > (dual ? kMaxSlabs : kMaxGrid / 2)) pairs = dual ? kMaxSlabs : kMaxGrid / 2;
     if (pairs > n_tiles) pairs = n_tiles;
     if (pairs < 1) pairs = 1;
-    static bool attr[kMaxDevices][3][MAXL] = {};
     if (ev_begin) AURPPO_HIP_TRY(hipEventRecord((hipEvent_t)ev_begin, s));
     const int grid = dual ? pairs : 2 * pairs;
-    bool* ad = &attr[dslot][bf3k ? 2 : (dual ? 1 : 0)][num_layers - 1];
     if (bf3k) {
         // hidden layers of 113..128 / 81..96 units over <= 64 / <= 128 state floats: the builds whose matrix chains have compile-time
         // trip counts (v = 1..4); every other width runs the build with run-time counts (v = 0)
-        static bool attr3[kMaxDevices][5][MAXL] = {};
         const int hk = hidden > 112 ? 8 : ((hidden > 80 && hidden <= 96) ? 6 : 0);
         const int v = hk == 0 ? 0 : (hk == 8 ? 1 : 3) + (D <= 64 ? 0 : 1);
-        ad = &attr3[dslot][v][num_layers - 1];
-        const size_t lds = (size_t)w3::kBytes;
-#define AURPPO_W3_LAUNCH(NLV)                                                                                   \
-        switch (v) {                                                                                            \
-            case 1: rc = launch_wide(k_mlpw3_step<NLV, 8, 4>, ad, grid, lds, s, a); break;                        \
-            case 2: rc = launch_wide(k_mlpw3_step<NLV, 8, 8>, ad, grid, lds, s, a); break;                        \
-            case 3: rc = launch_wide(k_mlpw3_step<NLV, 6, 4>, ad, grid, lds, s, a); break;                        \
-            case 4: rc = launch_wide(k_mlpw3_step<NLV, 6, 8>, ad, grid, lds, s, a); break;                        \
-            default: rc = launch_wide(k_mlpw3_step<NLV, 0, 0>, ad, grid, lds, s, a); break;                       \
+#define AURPPO_W3_LAUNCH(NLV)                                \
+        switch (v) {                                         \
+            case 1: rc = wide_launch<k_mlpw3_step<NLV, 8, 4>>("k_mlpw_step", grid, w3::kBytes, s, a); break;  \
+            case 2: rc = wide_launch<k_mlpw3_step<NLV, 8, 8>>("k_mlpw_step", grid, w3::kBytes, s, a); break;  \
+            case 3: rc = wide_launch<k_mlpw3_step<NLV, 6, 4>>("k_mlpw_step", grid, w3::kBytes, s, a); break;  \
+            case 4: rc = wide_launch<k_mlpw3_step<NLV, 6, 8>>("k_mlpw_step", grid, w3::kBytes, s, a); break;  \
+            default: rc = wide_launch<k_mlpw3_step<NLV, 0, 0>>("k_mlpw_step", grid, w3::kBytes, s, a); break; \
         }
         if (num_layers == 1) { AURPPO_W3_LAUNCH(1) }
         else if (num_layers == 2) { AURPPO_W3_LAUNCH(2) }
@@ -1622,15 +1590,14 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
 #undef AURPPO_W3_LAUNCH
     } else
     switch (num_layers * 2 + (dual ? 1 : 0)) {
-        case 2: rc = launch_wide(k_mlpw_step<1, false>, ad, grid, wide_lds_bytes<false, 1>(1), s, a); break;
-        case 3: rc = launch_wide(k_mlpw_step<1, true>, ad, grid, wide_lds_bytes<true, 1>(2), s, a); break;
-        case 4: rc = launch_wide(k_mlpw_step<2, false>, ad, grid, wide_lds_bytes<false, 2>(1), s, a); break;
-        case 5: rc = launch_wide(k_mlpw_step<2, true>, ad, grid, wide_lds_bytes<true, 2>(2), s, a); break;
-        case 6: rc = launch_wide(k_mlpw_step<3, false>, ad, grid, wide_lds_bytes<false, 3>(1), s, a); break;
-        default: rc = launch_wide(k_mlpw_step<3, true>, ad, grid, wide_lds_bytes<true, 3>(2), s, a); break;
+        case 2: rc = wide_launch<k_mlpw_step<1, false>>("k_mlpw_step", grid, wide_lds_bytes<false, 1>(1), s, a); break;
+        case 3: rc = wide_launch<k_mlpw_step<1, true>>("k_mlpw_step", grid, wide_lds_bytes<true, 1>(2), s, a); break;
+        case 4: rc = wide_launch<k_mlpw_step<2, false>>("k_mlpw_step", grid, wide_lds_bytes<false, 2>(1), s, a); break;
+        case 5: rc = wide_launch<k_mlpw_step<2, true>>("k_mlpw_step", grid, wide_lds_bytes<true, 2>(2), s, a); break;
+        case 6: rc = wide_launch<k_mlpw_step<3, false>>("k_mlpw_step", grid, wide_lds_bytes<false, 3>(1), s, a); break;
+        default: rc = wide_launch<k_mlpw_step<3, true>>("k_mlpw_step", grid, wide_lds_bytes<true, 3>(2), s, a); break;
     }
     if (rc != AURPPO_OK) return rc;
-    AURPPO_LAUNCH_CHECK("k_mlpw_step");
     if (ev_end) AURPPO_HIP_TRY(hipEventRecord((hipEvent_t)ev_end, s));
     if (!tail) return launch_mlp_reduce(wv.slabs, wv.loss_part, pairs, n_params, a.h, grads, out_scalars, s);
     // (the reduce clears the tile counters for the launch that follows: the next chained call has no prepare pass to do it)
@@ -1701,16 +1668,11 @@ extern "C" int aurppo_mlp_wide_act_f32(const float* obs, const float* noise, int
                        (const float4*)nullptr, 0, (const int32_t*)nullptr, 0, (double (*)[2]) nullptr, 0, (unsigned*)nullptr);
     AURPPO_LAUNCH_CHECK("k_mlpw_prep");
     const int grid = ((N + R - 1) / R) * a.net_count;
-    static bool attr[kMaxDevices][MAXL] = {};
-    bool* ad = &attr[aurppo_device_slot()][num_layers - 1];
     switch (num_layers) {
-        case 1: rc = launch_wide(k_mlpw_act<1>, ad, grid, wide_lds_bytes<false, 1>(1), s, a); break;
-        case 2: rc = launch_wide(k_mlpw_act<2>, ad, grid, wide_lds_bytes<false, 2>(1), s, a); break;
-        default: rc = launch_wide(k_mlpw_act<3>, ad, grid, wide_lds_bytes<false, 3>(1), s, a); break;
+        case 1: return wide_launch<k_mlpw_act<1>>("k_mlpw_act", grid, wide_lds_bytes<false, 1>(1), s, a);
+        case 2: return wide_launch<k_mlpw_act<2>>("k_mlpw_act", grid, wide_lds_bytes<false, 2>(1), s, a);
+        default: return wide_launch<k_mlpw_act<3>>("k_mlpw_act", grid, wide_lds_bytes<false, 3>(1), s, a);
     }
-    if (rc != AURPPO_OK) return rc;
-    AURPPO_LAUNCH_CHECK("k_mlpw_act");
-    return AURPPO_OK;
 }
 
 #ifdef K7W_STAMPS

@@ -69,8 +69,11 @@ __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, fl
 }
 
 // ---- Per-element terms of the action distributions (src/models/actor_critic.py:36-50), shared by every fused step (mlp2.hip, mlp3.hip,
-// mlp_wide.hip, head.hip) and rollout kernel (mlp.hip, mlp_wide.hip).  Scalars only: the sums over a row's outputs stay in the kernels,
-// whose lane layouts differ.  Each compiles in its includer's contract mode, like ppo_sample.
+// mlp_wide.hip, head.hip) and rollout kernel (mlp.hip, mlp_wide.hip, head.hip).  The loss terms are scalars: the sums over a row's outputs
+// stay in the loss lanes, whose layouts differ.  Sampling is here whole (below the terms): a Gaussian dimension is a scalar, and the
+// Categorical rows of K8, K8w and k_mlpw_step<> share one layout -- one lane per row, its logits behind a pointer into LDS.  The kernels
+// that hold a row elsewhere (k_head_ppo / k_head_act: registers; k_mlpw3_step: spread over lanes) keep their own Categorical sums.
+// Each compiles in its includer's contract mode, like ppo_sample.
 constexpr float kHalfLog2Pi = 0.9189385332046727f;   // log(2 pi) / 2
 
 // Normal(mu, exp(ls)): one action dim's log-prob term, z = a - mu.  Two deliberate forms, not the same bits.  _ivar: the fused MLP steps
@@ -89,6 +92,37 @@ __device__ __forceinline__ float gauss_dls_var(float g_logp, float z, float var,
 // d logp / d z_k = [k == a] - p_k ;  d H / d z_k = -p_k (log p_k + H)
 __device__ __forceinline__ float cat_dlogit(float g_logp, bool hit, float p, float lp, float ent, float g_ent) {
     return g_logp * ((hit ? 1.0f : 0.0f) - p) + g_ent * (-p * (lp + ent));
+}
+
+// ---- Sampling (the rollout kernels K8 k_mlp_act, K8w k_mlpw_act, K14 k_head_act).
+// Normal(mu, sd = exp(ls)) at the standard-normal draw eps: writes the action, returns the dimension's log-prob term with z formed from
+// the action as evaluate() forms it, (a - mu) -- so the stored log-prob is the one the update computes from the stored action.
+__device__ __forceinline__ float gauss_sample(float mu, float sd, float ls, float eps, float& action) {
+    const float act = mu + sd * eps;
+    action = act;
+    return gauss_logp_var(act - mu, sd * sd, ls);
+}
+// Categorical(logits z[0 .. A)), one lane per row: log sum exp (max-subtracted) ...
+__device__ __forceinline__ float cat_lse(const float* z, int A) {
+    float mx = z[0];
+    for (int k = 1; k < A; ++k) mx = fmaxf(mx, z[k]);
+    float se = 0.0f;
+    for (int k = 0; k < A; ++k) se += expf(z[k] - mx);
+    return mx + logf(se);
+}
+// ... and the inverse CDF of softmax(z) at the uniform draw u (the last class where rounding leaves the sum below u), with its log-prob
+__device__ __forceinline__ int cat_sample(const float* z, int A, float lse, float u, float& logp) {
+    float cdf = 0.0f;
+    int pick = A - 1;
+    for (int k = 0; k < A; ++k) {
+        cdf += expf(z[k] - lse);
+        if (u < cdf) {
+            pick = k;
+            break;
+        }
+    }
+    logp = z[pick] - lse;
+    return pick;
 }
 
 // Mean and standard deviation (torch.std: over M - 1; M == 1 -> 0/0 = NaN, as there) of a minibatch's advantages from their sum and

@@ -1,11 +1,16 @@
-"""Do two builds of the library compute the same BITS in the fused MLP kernels (K7, K7w, K8, K8w, their reduce / optimizer launches)?
+"""Do two builds of the library compute the same BITS in the fused MLP kernels (K7, K7w, K8, K8w, their reduce / optimizer launches),
+the head kernels (K13, K14) and the layered rollout step?
     AURPPO_LIB=<build> python tools/build_bitdiff.py run OUT.npz     (once per build, each in a process of its own)
     python tools/build_bitdiff.py cmp A.npz B.npz                    (raw bytes of every array; exit 1 + the first that differs)
 `run` drives every build of the step (K7 ids 3, 2; K7w ids 1, 3, 2) with AURPPO_STATIC_TILES=1 (a fixed summation order; the
 counter-dealt order is not reproducible by construction) over the smallest shapes that reach every path, at M = 1, 65 and 70001, and
 stores gradient, scalars and the whole workspace after mlp_ppo_step; parameters, moments, norms, step count and workspace after two
 chained mlp_ppo_minibatch calls (the first names next_idx) and after mlp_ppo_grad + mlp_ppo_apply (K7); the mlp_act outputs.  The
-workspace is zero-filled before each sequence, so that bytes no kernel writes are equal across processes."""
+workspace is zero-filled before each sequence, so that bytes no kernel writes are equal across processes.
+The head kernels run at every threads-per-row build (H = 32, 96, 256, 512, 1024: 8, 32, 64, 128, 256), Gaussian heads of 1 and 16
+actions, Categorical heads of 2 and 16, M = N = 1, 65, 4099: head_ppo with records beside actions and packed (where the action row
+fits a packed record) -- gz of both nets, gradient, scalars, workspace (K13's grid depends on (M, H) only, so its slabs repeat) --
+head_act with noise and for the value alone, and mlp_layered_prepare + mlp_layered_act on layered policies of those widths."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,6 +20,16 @@ K7_SHAPES = [(2, 64, 64, 6, True, False), (2, 64, 17, 3, True, False), (2, 64, 6
 K7W_SHAPES = [(1, 64, 64, 6, True, False), (3, 64, 64, 6, True, False), (3, 128, 64, 6, True, False), (2, 128, 128, 16, True, False),
               (1, 96, 64, 4, False, False)]
 MS, B = (1, 65, 70001), 71000
+HEAD_HS, HEAD_KINDS, HEAD_NS, HEAD_B = (32, 96, 256, 512, 1024), ((1, True), (16, True), (2, False), (16, False)), (1, 65, 4099), 4200
+# (layers, hidden, D): widths no fused kernel takes, or (32, 96) a state no fused kernel takes
+LAYERED_SHAPES = [(2, 32, 144), (1, 96, 144), (2, 256, 16), (1, 512, 16), (1, 1024, 16)]
+
+
+def head_layout(H, pol, bucket, Hd, A, cont):
+    """The layout hip_ops.head_ppo / head_act take for a one-layer policy of any width (the head kernels take every H a multiple of
+    32, whichever kernel owns the policy's update); tools/head_time.py uses it too."""
+    seq, n = H._mlp_structure(pol, bucket)[:2]
+    return dict(offsets=seq, n_params=n, D=pol.actor.net[0].weight.shape[1], A=A, continuous=cont, hidden=Hd, num_layers=1, layered=True)
 
 
 def run(out_path):
@@ -34,13 +49,19 @@ def run(out_path):
         for name, t in tensors.items():
             out[key + name] = t.detach().cpu().contiguous().view(-1).numpy().view(np.uint8).copy()
 
-    def case(tag, NL, Hd, D, A, cont, packed):
+    def policy(D, A, cont, Hd, NL):
         torch.manual_seed(1000 * NL + Hd + D + A)                       # CPU generator: the same inputs in every process
         pol = actor_critic(D, (A,) if cont else A, Hd, NL, 0.0, cont)
         with torch.no_grad():
             for p in pol.parameters():
                 p.add_(0.05 * torch.randn_like(p))
-        bucket = FlatBucket(pol.to(dev).parameters())
+        return pol, FlatBucket(pol.to(dev).parameters())
+
+    def noise_for(N, A, cont):
+        return (torch.randn(N, A) if cont else torch.rand(N)).to(dev)
+
+    def case(tag, NL, Hd, D, A, cont, packed):
+        pol, bucket = policy(D, A, cont, Hd, NL)
         lay = H.mlp_layout(pol, bucket)
         assert lay is not None and lay["wide"] == tag.startswith("k7w"), (tag, lay)
         n, nb, flat = lay["n_params"], bucket.flat_param.numel(), bucket.flat_param
@@ -79,6 +100,45 @@ def run(out_path):
             a_, lp_, v_ = H.mlp_act(obs[:M].contiguous(), (torch.randn(M, A) if cont else torch.rand(M)).to(dev), flat, lay)
             keep(key + "act/", actions=a_, logp=lp_, value=v_)
 
+    def head_case(Hd, A, cont):
+        pol, bucket = policy(16, A, cont, Hd, 1)
+        lay = head_layout(H, pol, bucket, Hd, A, cont)
+        act = (torch.randn(HEAD_B, A) if cont else torch.randint(0, A, (HEAD_B,)).float()).to(dev)
+        rec = torch.stack([-1.0 + 0.3 * torch.randn(HEAD_B), 2 * torch.randn(HEAD_B), torch.randn(HEAD_B), torch.randn(HEAD_B)], 1).contiguous().to(dev)
+        perm = torch.randperm(HEAD_B).int().to(dev)
+        forms = [("", act, rec)] + ([("packed/", None, H.pack_records(rec, act))] if (A if cont else 1) <= 12 else [])
+        for M in HEAD_NS:
+            key = f"head/H{Hd}-A{A}{'' if cont else 'c'}/M{M}/"
+            hA, hC = torch.tanh(torch.randn(M, Hd)).to(dev), torch.tanh(torch.randn(M, Hd)).to(dev)
+            nz = noise_for(M, A, cont)
+            ws_bytes = lib.aurppo_head_ppo_workspace_bytes(M, Hd, A)
+            ws = H._workspace("head", ws_bytes, dev)
+            for form, a_, r_ in forms:
+                ws.zero_()
+                g, gzA, gzC = torch.zeros_like(bucket.flat_grad), torch.zeros_like(hA), torch.zeros_like(hC)
+                sc = H.head_ppo(hA, hC, a_, r_, perm[:M].contiguous(), bucket.flat_param, lay, g, 0.2, 0.01, 0.5, True, 1, gzA=gzA, gzC=gzC)
+                keep(key + "ppo/" + form, gzA=gzA, gzC=gzC, grad=g, scalars=sc, ws=ws[:ws_bytes])
+            a_, lp_, v_ = H.head_act(hA, hC, nz, bucket.flat_param, lay)
+            keep(key + "act/", actions=a_, logp=lp_, value=v_)
+            keep(key + "act/value_only/", value=H.head_act(None, hC, None, bucket.flat_param, lay)[2])
+
+    def layered_case(NL, Hd, D, A, cont):
+        pol, bucket = policy(D, A, cont, Hd, NL)
+        lay = H.mlp_layered_layout(pol, bucket)
+        assert lay is not None, (NL, Hd, D)
+        wop = H.mlp_layered_prepare(bucket.flat_param, lay)
+        for N in HEAD_NS:
+            key = f"layered/{NL}x{Hd}-D{D}-A{A}{'' if cont else 'c'}/N{N}/"
+            obs = torch.randn(N, D).to(dev)
+            a_, lp_, v_ = H.mlp_layered_act(obs, noise_for(N, A, cont), bucket.flat_param, lay, wop=wop)
+            keep(key + "act/", actions=a_, logp=lp_, value=v_)
+            keep(key + "act/value_only/", value=H.mlp_layered_act(obs, None, bucket.flat_param, lay, wop=wop)[2])
+
+    for Hd in HEAD_HS:
+        for A, cont in HEAD_KINDS:
+            head_case(Hd, A, cont)
+    for k, (NL, Hd, D) in enumerate(LAYERED_SHAPES):
+        layered_case(NL, Hd, D, *HEAD_KINDS[k % len(HEAD_KINDS)])
     for knob, shapes in (("AURPPO_K7_VARIANT", K7_SHAPES), ("AURPPO_K7W_VARIANT", K7W_SHAPES)):
         for s in shapes:
             dual = knob == "AURPPO_K7W_VARIANT" and lib.aurppo_k7w_kernel(s[1], s[2]) == 1     # K7w id 1: the knob does not matter
