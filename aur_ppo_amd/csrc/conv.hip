@@ -30,6 +30,47 @@ using namespace bf3;
 namespace {
 
 typedef float f32x16c __attribute__((ext_vector_type(16)));
+
+// One k-step of a convolution's product: the six plane products of bf16x3.h summed from ZERO, smallest first, and the step's sum added
+// to the running accumulator once.  mma32x3 chains all six through the running accumulator; after a few k-steps that sum is so much
+// larger than a third-order product (2^-16 of a term) that the matrix pipe's addition drops it whole: on operands with known positive
+// planes K11 and K12 lost 15 % of the third-order terms at a reduction of 288, 87 % at 2304 (tools/conv_plane_bias.py), and the robot
+// policy's gradients through them sat at 6 x plain fp32 against an fp64 net.  Here each step's small products meet only
+// that step's own a0 * b0, and the accumulator takes one rounded fp32 addition per k-step.
+// NEG: the step is computed as -(sum of (-a) * b).  The matrix pipe cuts the bits below its adder's width off TOWARDS MINUS INFINITY,
+// whatever the sign of the sum: 5e-9 of the sum of |terms| per output, always negative, which a sum over 10^5 pixels (a bias
+// gradient) does not average away.  Every other k-step runs negated, so the cuts of neighbouring steps cancel.
+__device__ __forceinline__ Frag3 neg3(const Frag3& a) {
+    Frag3 r;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        u32x4 v = __builtin_bit_cast(u32x4, a.p[pl]);
+        v = v ^ u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
+        r.p[pl] = __builtin_bit_cast(bf16x8, v);
+    }
+    return r;
+}
+// -DCONV_EXP_NO_ALTERNATE: every k-step with the same sign (a measuring build: tools/conv_plane_bias.py shows the one-sided cut alone)
+__device__ __forceinline__ constexpr bool kStepNeg(int k) {
+#ifdef CONV_EXP_NO_ALTERNATE
+    return false;
+#else
+    return (k & 1) != 0;
+#endif
+}
+template <bool NEG>
+__device__ __forceinline__ f32x16c mma32x3_step(const Frag3& a, const Frag3& b, f32x16c c) {      // NEG: ``a`` comes negated (neg3)
+    f32x16c t;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) t[e] = 0.0f;
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[2], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[2], b.p[0], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[1], b.p[1], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[1], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[1], b.p[0], t, 0, 0, 0);
+    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[0], t, 0, 0, 0);
+    return NEG ? c - t : c + t;
+}
 constexpr int kConvThreads = 256;
 constexpr int kNBW = 4;              // 32-channel blocks per wave
 constexpr int kTileLd = 33;          // floats per row of the epilogue's LDS tile
@@ -200,6 +241,7 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvArgs a) {
                         const u32x4 v = {p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
                         A[mb].p[pl] = __builtin_bit_cast(bf16x8, v);
                     }
+                    if (kStepNeg(kk)) A[mb] = neg3(A[mb]);      // (kk is a constant of the unrolled loop)
                 }
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
@@ -207,7 +249,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvArgs a) {
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) Bf.p[pl] = *reinterpret_cast<const bf16x8*>(bsrc + ((kk * NB + nb) * 3 + pl) * 1024);
 #pragma unroll
-                    for (int mb = 0; mb < kMB; ++mb) acc[mb][nb] = mma32x3(A[mb], Bf, acc[mb][nb]);
+                    for (int mb = 0; mb < kMB; ++mb)
+                        acc[mb][nb] = kStepNeg(kk) ? mma32x3_step<true>(A[mb], Bf, acc[mb][nb]) : mma32x3_step<false>(A[mb], Bf, acc[mb][nb]);
                 }
             }
         }
@@ -656,12 +699,20 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3_wgrad(const ConvWgr
         if (c + 3 < n_chunks) table(c + 3);                 // (slot c % 3: last read by fetch(c), before this chunk's first barrier)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const Frag3 A0 = wg_rows<PL>(s_img, rowA, ks, lane), A1 = wg_rows<PL>(s_img, rowA + 32, ks, lane);
+            Frag3 A0 = wg_rows<PL>(s_img, rowA, ks, lane), A1 = wg_rows<PL>(s_img, rowA + 32, ks, lane);
             const Frag3 B0 = wg_rows<PL>(s_img, rowB, ks, lane), B1 = wg_rows<PL>(s_img, rowB + 32, ks, lane);
-            acc[0][0] = mma32x3(A0, B0, acc[0][0]);
-            acc[0][1] = mma32x3(A0, B1, acc[0][1]);
-            acc[1][0] = mma32x3(A1, B0, acc[1][0]);
-            acc[1][1] = mma32x3(A1, B1, acc[1][1]);
+            if (kStepNeg(ks)) {                              // (ks is a constant of the unrolled loop)
+                A0 = neg3(A0); A1 = neg3(A1);
+                acc[0][0] = mma32x3_step<true>(A0, B0, acc[0][0]);
+                acc[0][1] = mma32x3_step<true>(A0, B1, acc[0][1]);
+                acc[1][0] = mma32x3_step<true>(A1, B0, acc[1][0]);
+                acc[1][1] = mma32x3_step<true>(A1, B1, acc[1][1]);
+            } else {
+                acc[0][0] = mma32x3_step<false>(A0, B0, acc[0][0]);
+                acc[0][1] = mma32x3_step<false>(A0, B1, acc[0][1]);
+                acc[1][0] = mma32x3_step<false>(A1, B0, acc[1][0]);
+                acc[1][1] = mma32x3_step<false>(A1, B1, acc[1][1]);
+            }
         }
     };
     float va[kSlots][4], vb[kSlots][4];

@@ -70,6 +70,9 @@ STEP1_RTOL, STEP1_ATOL = 1e-5, 1e-6
 # heads' outputs, which is the 2e-4 the later steps' scalars are held to (tests/test_parity_fullsize.py derives the same bound
 # for the MLP policy, where the gradient noise is 100x smaller and 1e-5 holds throughout).
 LATER_RTOL, LATER_ATOL = 2e-4, 2e-5
+# Control (tests/test_robot_host.py::test_two_correct_cpu_updates_drift_within_the_later_step_bounds): two correct CPU runs
+# of this update -- fp32 convolutions against fp64 convolutions rounded to fp32 -- use 12 % of this scalar bound at worst, sit 1.65e-4
+# apart in their weights at most (1.2e-3 below) and have 0.058 % of a tensor's weights more than 3e-5 apart (6 % below).
 
 
 def _check_later_steps_and_weights(got, rows, out, p, sd_gpu, sd_cpu):

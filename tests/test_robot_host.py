@@ -163,3 +163,50 @@ def test_reference_format_checkpoint_loads(tmp_path):
         assert torch.equal(x, y), k
     sa, sb = a.optimizer.state_dict()["state"], b.optimizer.state_dict()["state"]
     assert sa.keys() == sb.keys() and all(torch.equal(sa[i]["exp_avg"], sb[i]["exp_avg"]) for i in sa)
+
+
+def test_two_correct_cpu_updates_drift_within_the_later_step_bounds(monkeypatch):
+    """The control for tests/test_robot_gpu.py's later-step bounds: the oracle's robot update (4 optimizer steps, that file's
+    configuration) in fp32, and the same update with every convolution evaluated in fp64 and rounded to fp32 (forward and both
+    gradients), from the same weights, data and seed.  Both are correct; what separates them is what separates any two correct
+    implementations from step 2 on, so they must sit inside LATER_RTOL / LATER_ATOL and the two weight conditions.  Measured:
+    the scalars of steps 2-4 use 12 % of their bound at worst (8 x below it); max |dw| 1.65e-4 (bound 1.2e-3: 7 x below); at most 0.058 %
+    of a tensor's weights moved by more than 3e-5 (bound 6 %: 100 x below).  The constants are not changed here: tightening them needs
+    a GPU run behind it."""
+    from oracle import ppo_oracle as O
+    from tests import ref64_robot as R
+    from tests.test_robot_gpu import LATER_ATOL, LATER_RTOL, _check_later_steps_and_weights
+    C, S = 1, 128
+    p = params_from_args(build_parser().parse_args([]))
+    p.update(num_envs=8, num_steps=8, num_update_epochs=2, num_minibatches=2, clip_vloss=True, entropy_coeff=0.01)
+    first = R.make_policy(C, S)
+    buf, next_state, next_obs = R.make_buffers(first, C, S)
+    flat = R.flat_buffers(first, buf, next_state, next_obs, C, S)
+    real = torch.nn.functional.conv2d
+
+    n_conv64 = []
+
+    def conv64(x, w, b=None, *a, **k):
+        n_conv64.append(1)
+        return real(x.double(), w.double(), None if b is None else b.double(), *a, **k).float()
+
+    runs = []
+    for fp64_convs in (False, True):
+        cpu = R.make_policy(C, S)
+        cpu.load_state_dict(first.state_dict())
+        opt = torch.optim.Adam(cpu.parameters(), lr=p["learning_rate"], eps=1e-5)
+        with monkeypatch.context() as m:
+            if fp64_convs:
+                m.setattr(torch.nn.functional, "conv2d", conv64)
+            rows = O.reference_robot_update(cpu, opt, flat, p, np.random.RandomState(1), 32)
+        runs.append((rows, {k: v.detach().numpy().copy() for k, v in cpu.state_dict().items()}))
+    (r32, sd32), (r64, sd64) = runs
+    assert r32.shape == r64.shape == (4, 7)
+    np.testing.assert_allclose(r32[0, :6], r64[0, :6], rtol=1e-5, atol=1e-6)          # step 1: identical weights
+    used = np.abs(r32[1:, :6] - r64[1:, :6]) / (LATER_RTOL * np.abs(r64[1:, :6]) + LATER_ATOL)
+    dw = {k: np.abs(sd32[k] - sd64[k]) for k in sd32}
+    # the control is only one if the second run really took the fp64 convolutions and ended somewhere else
+    assert len(n_conv64) >= 4 * 2 * 7 and max(d.max() for d in dw.values()) > 0 and not np.array_equal(r32[1:], r64[1:])
+    print(f"\nlater steps: worst scalar difference {used.max():.4f} of its bound; max |dw| {max(d.max() for d in dw.values()):.3e} (bound 1.2e-3); "
+          f"largest share of a tensor's weights moved by more than 3e-5: {max(np.mean(d > 3e-5) for d in dw.values() if d.size >= 1000):.5f} (bound 0.06)")
+    _check_later_steps_and_weights(r32, r64, [None, r32[-1, 2] * p["value_coeff"]], p, sd32, sd64)
