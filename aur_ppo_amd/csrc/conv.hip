@@ -90,8 +90,11 @@ __device__ __forceinline__ int acc_row_c(int e, int lane) { return (e & 3) + 8 *
 // filter -> operand order.  transpose_flip = 0 (forward): B[k = (tap, ci)][n = co] = W[co][ci][tap];
 // 1 (input gradient): the product's "input" channels are the forward pass's OUTPUT channels: B[k = (tap, co)][n = ci] =
 // W[co][ci][8 - tap].  cin_gemm / cout_gemm are the product's own channel counts (cin_gemm a multiple of 16).
-__global__ __launch_bounds__(256) void k_conv_prep(const float* __restrict__ w, int Co_w, int Ci_w, int cin_gemm, int cout_gemm,
-                                                   int transpose_flip, unsigned short* __restrict__ wop, int taps) {
+// KTAIL (k_linear_prep_tail: a linear layer whose inner dimension Ci_w is no multiple of 16, forward only): cin_gemm is Ci_w rounded
+// up to whole k-steps, and the columns k >= Ci_w -- which w does not have -- get zero planes without a read.
+template <bool KTAIL>
+__device__ __forceinline__ void conv_prep_body(const float* __restrict__ w, int Co_w, int Ci_w, int cin_gemm, int cout_gemm,
+                                               int transpose_flip, unsigned short* __restrict__ wop, int taps) {
     const int CG = cin_gemm >> 4, KS = taps * CG, NBLK = (cout_gemm + 31) >> 5;
     const long long total = (long long)NBLK * KS * 64 * 8;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256) void k_conv_prep(const float* __restrict__ w, 
         const int tap = ks / CG, cg = ks - tap * CG;
         const int n = nblk * 32 + (lane & 31), k = cg * 16 + 8 * (lane >> 5) + j;
         float v = 0.0f;
-        if (n < cout_gemm) {
+        if (n < cout_gemm && (!KTAIL || k < Ci_w)) {
             if (!transpose_flip) v = w[((size_t)n * Ci_w + k) * taps + tap];               // W[co = n][ci = k][tap]
             else v = w[((size_t)k * Ci_w + n) * taps + (taps - 1 - tap)];                  // W[co = k][ci = n][flipped tap]
         }
@@ -113,6 +116,14 @@ __global__ __launch_bounds__(256) void k_conv_prep(const float* __restrict__ w, 
         wop[at + 1024] = (unsigned short)p2;
     }
     (void)Co_w;
+}
+__global__ __launch_bounds__(256) void k_conv_prep(const float* __restrict__ w, int Co_w, int Ci_w, int cin_gemm, int cout_gemm,
+                                                   int transpose_flip, unsigned short* __restrict__ wop, int taps) {
+    conv_prep_body<false>(w, Co_w, Ci_w, cin_gemm, cout_gemm, transpose_flip, wop, taps);
+}
+__global__ __launch_bounds__(256) void k_linear_prep_tail(const float* __restrict__ w, int N_w, int K_w, int k_gemm,
+                                                          unsigned short* __restrict__ wop) {
+    conv_prep_body<true>(w, N_w, K_w, k_gemm, N_w, 0, wop, 1);
 }
 
 constexpr int kMB = 2;               // 32-pixel blocks per wave
@@ -299,117 +310,21 @@ struct LinArgs {
 };
 
 // ROWS (layer 0 of the layered PPO step, hip_ops.mlp_layered_step: x through the minibatch index) and GATE (its input gradients:
-// tanh' of the layer below in the epilogue) are template parameters, so the plain instantiations keep their instruction streams
+// tanh' of the layer below in the epilogue) are template parameters, so the plain instantiations keep their instruction streams.
+// KTAIL (k_linear_tail: K is no multiple of 16 -- layer 0 of a policy whose state is 3, 11, 17, 376 floats wide): KS = ceil(K / 16)
+// k-steps against an operand copy whose columns >= K are zero planes (k_linear_prep_tail).  A row is K floats and nothing more: it
+// starts at a 4-byte boundary, what follows it is another row, somebody else's memory or an unmapped page.  So every k-step's A values
+// are eight dword loads per lane, each one issued only where its column is < K, and the columns >= K enter split3 as a selected 0.
+// The two kernel templates share one body text, linear_body.h (it says why a text): KTAIL is a constant of the including kernel.
 template <int NB, bool ROWS = false, bool GATE = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
-    constexpr int kChunkBytes = kKC * NB * 3 * 1024;
-    __shared__ __attribute__((aligned(16))) char s_b[2 * kChunkBytes];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mbq = (int)(blockIdx.x % (unsigned)a.n_mb), ng = (int)(blockIdx.x / (unsigned)a.n_mb);
-    const int h = lane >> 5;
-    const int KS = a.K >> 4;
-    long long m0[kMB];
-    const float* row[kMB];
-    bool valid[kMB];
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb) {
-        m0[mb] = (((long long)mbq * 4 + w) * kMB + mb) * 32;
-        const long long m = m0[mb] + (lane & 31);
-        valid[mb] = m < a.M;
-        if (ROWS) row[mb] = a.x + (size_t)(valid[mb] ? a.rows[m] : 0) * a.K + 8 * h;
-        else row[mb] = a.x + (size_t)(valid[mb] ? m : 0) * a.K + 8 * h;
-    }
-    const char* const wgrp = reinterpret_cast<const char*>(a.wop) + (size_t)(ng * NB) * KS * 3 * 1024;
-    auto stage = [&](int kc, int buf) {
-        char* const dst = s_b + buf * kChunkBytes;
-#pragma unroll
-        for (int f = 0; f < kKC * NB * 3; ++f) {
-            if ((f & 3) != w) continue;
-            const int pl = f % 3, nb = (f / 3) % NB, kk = f / (3 * NB);
-            const int ks = kc * kKC + kk;
-            if (ks < KS) dma16(wgrp + ((size_t)(nb * KS + ks) * 3 + pl) * 1024 + lane * 16, dst + f * 1024);
-        }
-    };
-    f32x16c acc[kMB][NB];
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mb][nb][e] = 0.0f;
-    auto load_a = [&](int ks, float4 (&v)[kMB][2]) {
-#pragma unroll
-        for (int mb = 0; mb < kMB; ++mb) {
-            const float4* p = reinterpret_cast<const float4*>(row[mb] + ks * 16);
-            v[mb][0] = p[0];
-            v[mb][1] = p[1];
-        }
-    };
-    const int n_chunks = (KS + kKC - 1) / kKC;
-    float4 abuf[2][kMB][2];
-    stage(0, 0);
-    load_a(0, abuf[0]);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");       // (the DMA pieces are older than the 4 loads of load_a)
-    __syncthreads();
-    for (int kc = 0; kc < n_chunks; ++kc) {
-        if (kc + 1 < n_chunks) stage(kc + 1, (kc + 1) & 1);
-        const char* const bsrc = s_b + (kc & 1) * kChunkBytes + lane * 16;
-#pragma unroll
-        for (int kk = 0; kk < kKC; ++kk) {
-            const int ks = kc * kKC + kk;
-            if (ks < KS) {
-                float4 (&cur)[kMB][2] = abuf[kk];
-                if (ks + 1 < KS) load_a(ks + 1, abuf[kk ^ 1]);
-                Frag3 A[kMB];
-#pragma unroll
-                for (int mb = 0; mb < kMB; ++mb) {
-                    const float c[8] = {cur[mb][0].x, cur[mb][0].y, cur[mb][0].z, cur[mb][0].w, cur[mb][1].x, cur[mb][1].y, cur[mb][1].z, cur[mb][1].w};
-                    unsigned p[4][3];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) split3(valid[mb] ? c[2 * q] : 0.0f, valid[mb] ? c[2 * q + 1] : 0.0f, p[q][0], p[q][1], p[q][2]);
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        const u32x4 v = {p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
-                        A[mb].p[pl] = __builtin_bit_cast(bf16x8, v);
-                    }
-                }
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    Frag3 Bf;
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) Bf.p[pl] = *reinterpret_cast<const bf16x8*>(bsrc + ((kk * NB + nb) * 3 + pl) * 1024);
-#pragma unroll
-                    for (int mb = 0; mb < kMB; ++mb) acc[mb][nb] = mma32x3(A[mb], Bf, acc[mb][nb]);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int col = (ng * NB + nb) * 32 + (lane & 31);
-            if (col < a.N) {
-                const float bv = a.bias ? a.bias[col] : 0.0f;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const long long r = m0[mb] + acc_row_c(e, lane);
-                    float v = acc[mb][nb][e] + bv;
-                    if (GATE) {
-                        if (r < a.M) {
-                            const float hv = a.h[(size_t)r * a.N + col];
-                            a.y[(size_t)r * a.N + col] = v * (1.0f - hv * hv);
-                        }
-                        continue;
-                    }
-                    if (a.act == 1) v = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * v) + 1.0f);
-                    if (r < a.M) a.y[(size_t)r * a.N + col] = v;
-                }
-            }
-        }
+    constexpr bool KTAIL = false;
+#include "linear_body.h"
+}
+template <int NB, bool ROWS>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_tail(const LinArgs a) {
+    constexpr bool GATE = false, KTAIL = true;
+#include "linear_body.h"
 }
 
 // ---- nn.Linear's weight gradient on the same arithmetic: dW (N, K) = dY^T (N, M) . X (M, K), both operands row-major with the
@@ -427,83 +342,18 @@ struct WgradArgs {
     const int32_t* rows;             // ROWS builds: (M,) row m of the product reads x row rows[m]; dy stays in minibatch order
 };
 
+// KTAIL (k_linear_wgrad_tail: K is no multiple of 4 -- layer 0's weight gradient at a ragged state width): an X row is K floats
+// at a 4-byte boundary, so its piece of a chunk is four dword loads, each issued only where its column is < K; the columns >= K
+// are staged as a selected 0 (and the stores to `part` leave them out, as they always did).
 template <bool ROWS = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
-    __shared__ __attribute__((aligned(16))) char s_img[2 * 2 * 3 * kXPlane];      // [dY | X][64-column half][3 planes][32 rows x 128 B]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tile = (int)(blockIdx.x % (unsigned)(a.n_tiles_n * a.n_tiles_k)), s = (int)(blockIdx.x / (unsigned)(a.n_tiles_n * a.n_tiles_k));
-    const int n0 = (tile / a.n_tiles_k) * 128, k0 = (tile % a.n_tiles_k) * 128;
-    const long long m_lo = (long long)s * a.rows_per_slice;
-    long long m_hi = m_lo + a.rows_per_slice;
-    if (m_hi > a.M) m_hi = a.M;
-    char* const imgA = s_img;                               // dY columns n0 .. n0 + 127
-    char* const imgB = s_img + 2 * 3 * kXPlane;            // X columns k0 .. k0 + 127
-    const int wn = w >> 1, wk = w & 1;                      // this wave's 64 x 64 quarter
-    // staging: a chunk = 32 rows x 128 columns of each operand = 1024 float4 per operand, four per thread
-    const int r_of = tid >> 5, c4 = (tid & 31) * 4;         // + 8 rows per further slot
-    f32x16c acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    float pa[4][4], pb[4][4];
-    unsigned pok = 0u;               // bit u: dY piece u is real; bit 4 + u: X piece u (the zeroing waits until the chunk is staged)
-    auto fetch = [&](long long m0) {
-        pok = 0u;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long r = m0 + r_of + 8 * u;
-            const bool okr = r < m_hi;
-            const bool oka = okr && n0 + c4 < a.N, okb = okr && k0 + c4 < a.K;      // (N and K are multiples of 4)
-            const float4 va = *reinterpret_cast<const float4*>(a.dy + (oka ? (size_t)r * a.N + n0 + c4 : (size_t)0));
-            const size_t xr = ROWS ? (size_t)(okb ? a.rows[r] : 0) : (size_t)r;
-            const float4 vb = *reinterpret_cast<const float4*>(a.x + (okb ? xr * a.K + k0 + c4 : (size_t)0));
-            pa[u][0] = va.x; pa[u][1] = va.y; pa[u][2] = va.z; pa[u][3] = va.w;
-            pb[u][0] = vb.x; pb[u][1] = vb.y; pb[u][2] = vb.z; pb[u][3] = vb.w;
-            pok |= (oka ? 1u : 0u) << u;
-            pok |= (okb ? 1u : 0u) << (4 + u);
-        }
-    };
-    fetch(m_lo);
-    for (long long m0 = m_lo; m0 < m_hi; m0 += 32) {
-        __syncthreads();                                    // the previous chunk's fragments have been read
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int r = r_of + 8 * u;
-            const bool oka = (pok >> u) & 1u, okb = (pok >> (4 + u)) & 1u;
-            store_x4(imgA + (c4 >> 6) * 3 * kXPlane, r, c4 & 63, oka ? pa[u][0] : 0.0f, oka ? pa[u][1] : 0.0f, oka ? pa[u][2] : 0.0f,
-                     oka ? pa[u][3] : 0.0f);
-            store_x4(imgB + (c4 >> 6) * 3 * kXPlane, r, c4 & 63, okb ? pb[u][0] : 0.0f, okb ? pb[u][1] : 0.0f, okb ? pb[u][2] : 0.0f,
-                     okb ? pb[u][3] : 0.0f);
-        }
-        __syncthreads();
-        if (m0 + 32 < m_hi) fetch(m0 + 32);                 // the next chunk's rows, behind this chunk's products
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const Frag3 A0 = x_cols(imgA + wn * 3 * kXPlane, ks, 0, lane), A1 = x_cols(imgA + wn * 3 * kXPlane, ks, 32, lane);
-            const Frag3 B0 = x_cols(imgB + wk * 3 * kXPlane, ks, 0, lane), B1 = x_cols(imgB + wk * 3 * kXPlane, ks, 32, lane);
-            acc[0][0] = mma32x3(A0, B0, acc[0][0]);
-            acc[0][1] = mma32x3(A0, B1, acc[0][1]);
-            acc[1][0] = mma32x3(A1, B0, acc[1][0]);
-            acc[1][1] = mma32x3(A1, B1, acc[1][1]);
-        }
-    }
-    // C[m = dY column][n = X column]: the lane holds the X column, its registers the dY columns -- rows of `part` are contiguous over the lanes
-    float* const out = a.part + (size_t)s * a.N * a.K;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = k0 + wk * 64 + j * 32 + (lane & 31);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = n0 + wn * 64 + i * 32 + acc_row_c(e, lane);
-                if (row < a.N && col < a.K) out[(size_t)row * a.K + col] = acc[i][j][e];
-            }
-        }
+    constexpr bool KTAIL = false;
+#include "linear_wgrad_body.h"
+}
+template <bool ROWS>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const WgradArgs a) {
+    constexpr bool KTAIL = true;
+#include "linear_wgrad_body.h"
 }
 
 
@@ -763,7 +613,7 @@ __global__ __launch_bounds__(256) void k_fold_slices(const float* __restrict__ p
 
 extern "C" size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm) {
     const size_t nblk = (size_t)((cout_gemm + 31) / 32 + kNBW);      // (+ one group of slack: a wave reads whole groups)
-    return nblk * 9 * (size_t)(cin_gemm / 16) * 3 * 1024 + 64;
+    return nblk * 9 * (size_t)((cin_gemm + 15) / 16) * 3 * 1024 + 64;      // (whole k-steps: a linear product's K may be ragged)
 }
 
 // mode 0: z = conv2d(x, w, padding = pad)                      x (B, Ci, H, W), w (Co, Ci, 3, 3), z (B, Co, H + 2 pad - 2, ...)
@@ -815,7 +665,7 @@ extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int 
     return AURPPO_OK;
 }
 
-// mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T      -- nn.Linear without its bias; K_w a multiple of 16
+// mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T      -- nn.Linear without its bias; any K_w >= 1 (no multiple of 16: the tail builds)
 // mode 1: y (M, K_w) = x (M, N_w) . w (N_w, K_w)         -- the gradient with respect to the input (x is dY); N_w a multiple of 16
 // wop_ws: aurppo_conv3x3_wop_bytes(product's K, product's N) / 9 bytes suffice; the same function's size is accepted.
 static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
@@ -855,6 +705,11 @@ extern "C" int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const 
 // call; the layered rollout step (aurppo_mlp_layered_prep_f32 / aurppo_linear_prepared) builds the copies once per rollout.
 static int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s) {
     const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
+    if (K % 16 != 0) {               // (mode 0 only: the callers hold mode 1's inner dimension to 16)
+        hipLaunchKernelGGL(k_linear_prep_tail, dim3(64), dim3(256), 0, s, w, N_w, K_w, (K_w + 15) / 16 * 16, wop);
+        AURPPO_LAUNCH_CHECK("k_linear_prep_tail");
+        return AURPPO_OK;
+    }
     hipLaunchKernelGGL(k_conv_prep, dim3(64), dim3(256), 0, s, w, N_w, K_w, K, N, mode, wop, 1);
     AURPPO_LAUNCH_CHECK("k_conv_prep");
     return AURPPO_OK;
@@ -872,7 +727,16 @@ static int linear_launch(const float* x, const unsigned short* wop, const float*
     AURPPO_REQUIRE(n_mb * n_ng < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_f32: grid too large");
     a.n_mb = (int)n_mb;
     const dim3 g((unsigned)(n_mb * n_ng)), blk(kConvThreads);
-    if (h) {
+    if (K % 16 != 0) {
+        AURPPO_REQUIRE(!h, AURPPO_ESHAPE, "aurppo_linear_f32: the input gradient's inner dimension %d (a multiple of 16)", K);
+        if (rows) {
+            if (NB == 4) hipLaunchKernelGGL((k_linear_tail<4, true>), g, blk, 0, s, a);
+            else if (NB == 2) hipLaunchKernelGGL((k_linear_tail<2, true>), g, blk, 0, s, a);
+            else hipLaunchKernelGGL((k_linear_tail<1, true>), g, blk, 0, s, a);
+        } else if (NB == 4) hipLaunchKernelGGL((k_linear_tail<4, false>), g, blk, 0, s, a);
+        else if (NB == 2) hipLaunchKernelGGL((k_linear_tail<2, false>), g, blk, 0, s, a);
+        else hipLaunchKernelGGL((k_linear_tail<1, false>), g, blk, 0, s, a);
+    } else if (h) {
         if (NB == 4) hipLaunchKernelGGL((k_linear<4, false, true>), g, blk, 0, s, a);
         else if (NB == 2) hipLaunchKernelGGL((k_linear<2, false, true>), g, blk, 0, s, a);
         else hipLaunchKernelGGL((k_linear<1, false, true>), g, blk, 0, s, a);
@@ -892,8 +756,8 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
     AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
     const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && K % 16 == 0, AURPPO_ESHAPE,
-                   "aurppo_linear_f32: M=%lld, inner dimension %d (a multiple of 16), %d columns", M, K, N);
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && (mode == 0 || K % 16 == 0), AURPPO_ESHAPE,
+                   "aurppo_linear_f32: M=%lld, inner dimension %d (mode 1: a multiple of 16), %d columns", M, K, N);
     AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL, "aurppo_linear_f32: x / workspace not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
@@ -906,21 +770,20 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
 // steps of a rollout, so the operand-order copies of the 2 L hidden-layer matrices are built once, into a caller-owned buffer:
 // [net][layer], each copy aurppo_linear_wop_bytes(its K, hidden) bytes.
 // Bytes of one forward operand copy: the blocks k_conv_prep writes and one group of slack, as a workgroup reads whole groups.
-size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + kNBW) * (size_t)(K / 16) * 3 * 1024; }
+size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + kNBW) * (size_t)((K + 15) / 16) * 3 * 1024; }
 
 // y (M, N) = act(x (M, K) . B + bias) from the operand copy `wop` of a (N, K) weight: linear_impl without its k_conv_prep launch.
 int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
                            void* stream) {
     AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_prepared: null pointer");
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && K % 16 == 0, AURPPO_ESHAPE,
-                   "aurppo_linear_prepared: M=%lld, inner dimension %d (a multiple of 16), %d columns", M, K, N);
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
     AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_prepared: x / operand copy not 16-byte aligned");
     AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_prepared: act %d", act);
     return linear_launch(x, reinterpret_cast<const unsigned short*>(wop), bias, act, y, M, K, N, (hipStream_t)stream, nullptr, nullptr);
 }
 
 static bool layered_hidden_ok(int D, int hidden, int num_layers) {
-    return D > 0 && D % 16 == 0 && hidden >= 32 && hidden <= 1024 && hidden % 32 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers;
+    return D > 0 && hidden >= 32 && hidden <= 1024 && hidden % 32 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers;
 }
 
 extern "C" size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers) {
@@ -932,7 +795,7 @@ extern "C" int aurppo_mlp_layered_prep_f32(const float* params, const int* offse
                                            void* wop, void* stream) {
     AURPPO_REQUIRE(params && offsets && wop, AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: null pointer");
     AURPPO_REQUIRE(layered_hidden_ok(D, hidden, num_layers), AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_prep_f32: D=%d (a multiple of 16), hidden=%d (a multiple of 32, 32..1024), %d layers (1..%d)", D, hidden,
+                   "aurppo_mlp_layered_prep_f32: D=%d (1 or more), hidden=%d (a multiple of 32, 32..1024), %d layers (1..%d)", D, hidden,
                    num_layers, kLayeredMaxLayers);
     AURPPO_REQUIRE(aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: operand buffer not 16-byte aligned");
     const int per = 2 * (num_layers + 1);
@@ -982,7 +845,8 @@ extern "C" size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     return (size_t)linear_wgrad_slices(M, N, K) * (size_t)N * (size_t)K * sizeof(float) + 64;
 }
-// dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N and K multiples of 4, 16-byte aligned operands)
+// dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N a multiple of 4, any K >= 1 -- no multiple of 4:
+// the tail builds; 16-byte aligned operands)
 extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream) {
     return aurppo_linear_wgrad_rows_f32(dy, x, nullptr, dw, M, N, K, ws, stream);
 }
@@ -990,8 +854,7 @@ extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* d
 extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K,
                                             void* ws, void* stream) {
     AURPPO_REQUIRE(dy && x && dw && ws, AURPPO_EINVAL, "aurppo_linear_wgrad_f32: null pointer");
-    AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, AURPPO_ESHAPE,
-                   "aurppo_linear_wgrad_f32: M=%lld N=%d K=%d (N, K multiples of 4)", M, N, K);
+    AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: M=%lld N=%d (a multiple of 4) K=%d", M, N, K);
     AURPPO_REQUIRE(aligned_to(dy, 16) && aligned_to(x, 16) && aligned_to(ws, 16), AURPPO_EINVAL,
                    "aurppo_linear_wgrad_f32: operands / workspace not 16-byte aligned");
     const int S0 = linear_wgrad_slices(M, N, K);
@@ -1006,7 +869,10 @@ extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, con
     const long long grid = (long long)a.n_tiles_n * a.n_tiles_k * S;
     AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+    if (K % 4 != 0) {
+        if (rows) hipLaunchKernelGGL(k_linear_wgrad_tail<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+        else hipLaunchKernelGGL(k_linear_wgrad_tail<false>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+    } else if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
     else hipLaunchKernelGGL(k_linear_wgrad<false>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
     AURPPO_LAUNCH_CHECK("k_linear_wgrad");
     const long long n = (long long)N * K;

@@ -737,8 +737,8 @@ extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, 
                                           float* logp, float* value, const void* wop, void* workspace, void* stream) {
     AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL,
                    "aurppo_mlp_layered_act_f32: null pointer");
-    AURPPO_REQUIRE(N > 0 && D > 0 && D % 16 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_act_f32: N=%d, D=%d (a multiple of 16), %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_act_f32: N=%d, D=%d, %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
     AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
                    "aurppo_mlp_layered_act_f32: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", hidden, A);
     AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,

@@ -1,0 +1,123 @@
+// The body of k_linear and k_linear_tail (conv.hip), included INSIDE each of the two kernel templates: NB, ROWS, GATE and KTAIL are
+// compile-time constants of the including kernel, `a` its LinArgs.  One text, so the two cannot drift; compiled in place, so the
+// aligned kernels keep their names and their instruction streams (through a shared __device__ function they kept neither).
+    static_assert(!(GATE && KTAIL), "the input gradient's inner dimension is a hidden width");
+    constexpr int kChunkBytes = kKC * NB * 3 * 1024;
+    __shared__ __attribute__((aligned(16))) char s_b[2 * kChunkBytes];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mbq = (int)(blockIdx.x % (unsigned)a.n_mb), ng = (int)(blockIdx.x / (unsigned)a.n_mb);
+    const int h = lane >> 5;
+    const int KS = KTAIL ? (a.K + 15) >> 4 : a.K >> 4;
+    long long m0[kMB];
+    const float* row[kMB];
+    bool valid[kMB];
+#pragma unroll
+    for (int mb = 0; mb < kMB; ++mb) {
+        m0[mb] = (((long long)mbq * 4 + w) * kMB + mb) * 32;
+        const long long m = m0[mb] + (lane & 31);
+        valid[mb] = m < a.M;
+        if (ROWS) row[mb] = a.x + (size_t)(valid[mb] ? a.rows[m] : 0) * a.K + 8 * h;
+        else row[mb] = a.x + (size_t)(valid[mb] ? m : 0) * a.K + 8 * h;
+    }
+    const char* const wgrp = reinterpret_cast<const char*>(a.wop) + (size_t)(ng * NB) * KS * 3 * 1024;
+    auto stage = [&](int kc, int buf) {
+        char* const dst = s_b + buf * kChunkBytes;
+#pragma unroll
+        for (int f = 0; f < kKC * NB * 3; ++f) {
+            if ((f & 3) != w) continue;
+            const int pl = f % 3, nb = (f / 3) % NB, kk = f / (3 * NB);
+            const int ks = kc * kKC + kk;
+            if (ks < KS) dma16(wgrp + ((size_t)(nb * KS + ks) * 3 + pl) * 1024 + lane * 16, dst + f * 1024);
+        }
+    };
+    f32x16c acc[kMB][NB];
+#pragma unroll
+    for (int mb = 0; mb < kMB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[mb][nb][e] = 0.0f;
+    auto load_a = [&](int ks, float4 (&v)[kMB][2]) {
+#pragma unroll
+        for (int mb = 0; mb < kMB; ++mb) {
+            if constexpr (KTAIL) {
+                const float* p = row[mb] + ks * 16;
+                const int live = a.K - ks * 16 - 8 * h;        // how many of this lane's eight columns the row has
+                float c[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) c[j] = j < live ? p[j] : 0.0f;
+                v[mb][0] = float4{c[0], c[1], c[2], c[3]};
+                v[mb][1] = float4{c[4], c[5], c[6], c[7]};
+            } else {
+                const float4* p = reinterpret_cast<const float4*>(row[mb] + ks * 16);
+                v[mb][0] = p[0];
+                v[mb][1] = p[1];
+            }
+        }
+    };
+    const int n_chunks = (KS + kKC - 1) / kKC;
+    float4 abuf[2][kMB][2];
+    stage(0, 0);
+    load_a(0, abuf[0]);
+    if constexpr (KTAIL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (a tail lane may have issued fewer than 4 loads, or none)
+    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // (the DMA pieces are older than the 4 loads of load_a)
+    __syncthreads();
+    for (int kc = 0; kc < n_chunks; ++kc) {
+        if (kc + 1 < n_chunks) stage(kc + 1, (kc + 1) & 1);
+        const char* const bsrc = s_b + (kc & 1) * kChunkBytes + lane * 16;
+#pragma unroll
+        for (int kk = 0; kk < kKC; ++kk) {
+            const int ks = kc * kKC + kk;
+            if (ks < KS) {
+                float4 (&cur)[kMB][2] = abuf[kk];
+                if (ks + 1 < KS) load_a(ks + 1, abuf[kk ^ 1]);
+                Frag3 A[kMB];
+#pragma unroll
+                for (int mb = 0; mb < kMB; ++mb) {
+                    const float c[8] = {cur[mb][0].x, cur[mb][0].y, cur[mb][0].z, cur[mb][0].w, cur[mb][1].x, cur[mb][1].y, cur[mb][1].z, cur[mb][1].w};
+                    unsigned p[4][3];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) split3(valid[mb] ? c[2 * q] : 0.0f, valid[mb] ? c[2 * q + 1] : 0.0f, p[q][0], p[q][1], p[q][2]);
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) {
+                        const u32x4 v = {p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
+                        A[mb].p[pl] = __builtin_bit_cast(bf16x8, v);
+                    }
+                }
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    Frag3 Bf;
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) Bf.p[pl] = *reinterpret_cast<const bf16x8*>(bsrc + ((kk * NB + nb) * 3 + pl) * 1024);
+#pragma unroll
+                    for (int mb = 0; mb < kMB; ++mb) acc[mb][nb] = mma32x3(A[mb], Bf, acc[mb][nb]);
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+#pragma unroll
+    for (int mb = 0; mb < kMB; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) {
+            const int col = (ng * NB + nb) * 32 + (lane & 31);
+            if (col < a.N) {
+                const float bv = a.bias ? a.bias[col] : 0.0f;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const long long r = m0[mb] + acc_row_c(e, lane);
+                    float v = acc[mb][nb][e] + bv;
+                    if (GATE) {
+                        if (r < a.M) {
+                            const float hv = a.h[(size_t)r * a.N + col];
+                            a.y[(size_t)r * a.N + col] = v * (1.0f - hv * hv);
+                        }
+                        continue;
+                    }
+                    if (a.act == 1) v = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * v) + 1.0f);
+                    if (r < a.M) a.y[(size_t)r * a.N + col] = v;
+                }
+            }
+        }

@@ -341,18 +341,19 @@ def mlp_layout(policy, bucket):
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, wide=not fast)
 
 
-def mlp_layered_layout(policy, bucket):
+def mlp_layered_layout(policy, bucket, any_state=False):
     """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
-    kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, a state of a
-    multiple of 16 floats, at most 16 actions.  Offsets as K7w's: {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no
-    device."""
+    kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, at most 16 actions,
+    and a state of a multiple of 16 floats -- or, with ``any_state=True``, of any width (Hopper's 11, HalfCheetah's 17, Humanoid's
+    376: layer 0's three products then run on the tail builds of k_linear / k_linear_wgrad, csrc/conv.hip).  Offsets as K7w's:
+    {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no device."""
     if mlp_layout(policy, bucket) is not None:
         return None
     st = _mlp_structure(policy, bucket)
     if st is None:
         return None
     seq, pos, D, A, cont, NL, Hd = st
-    if Hd % 32 != 0 or Hd > MLP_LAYERED_MAX_HIDDEN or D % 16 != 0:
+    if Hd % 32 != 0 or Hd > MLP_LAYERED_MAX_HIDDEN or (D % 16 != 0 and not any_state):
         return None
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, layered=True)
 
@@ -911,7 +912,8 @@ def linear_ok(x, in_features, out_features):
 
 def linear_nobias(x, w, mode=0):
     """mode 0: ``x @ w.T``; mode 1: ``x @ w`` (the gradient of mode 0 with respect to its input, x being dY) -- fp32 products formed
-    from three-way bf16 splits on the MFMA pipe (csrc/conv.hip::k_linear)."""
+    from three-way bf16 splits on the MFMA pipe (csrc/conv.hip::k_linear).  The inner dimension: mode 0 any width (no multiple of 16:
+    k_linear_tail, which reads nothing past a row's floats), mode 1 a multiple of 16."""
     lib = _lib_or_raise()
     x, w = x.contiguous(), w.contiguous()
     M = x.shape[0]
@@ -942,7 +944,8 @@ def _linear_wgrad(gy, x, rows):
 
 def linear_wgrad(gy, x):
     """``gy.T @ x`` -- nn.Linear's weight gradient -- on the bf16 matrix pipe (csrc/conv.hip::k_linear_wgrad: both operands split
-    once per workgroup through LDS, the rows cut into slices that are summed in slice order)."""
+    once per workgroup through LDS, the rows cut into slices that are summed in slice order).  ``gy``'s width a multiple of 4; ``x`` of
+    any width (no multiple of 4: k_linear_wgrad_tail)."""
     return _linear_wgrad(gy, x, None)
 
 
@@ -967,7 +970,8 @@ def _linear_bias_act(x, rows, w, bias, act):
 
 
 def linear_bias_act(x, w, bias, act=0):
-    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/conv.hip::k_linear with the layer's tail in its epilogue."""
+    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/conv.hip::k_linear with the layer's tail in its epilogue.
+    ``x`` of any width (``linear_nobias``, mode 0)."""
     return _linear_bias_act(x, None, w, bias, act)
 
 

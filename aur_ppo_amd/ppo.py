@@ -152,14 +152,14 @@ class ppo(FlatAdamMixin):
         self._mlp_layered = None
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_layout")
                 and os.environ.get("AURPPO_LAYERED_STEP", LAYERED_STEP_DEFAULT) != "0"):
-            self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket)
+            self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
         # The same policies' rollout step and bootstrap: k_linear from operand copies prepared once per rollout + K14
         # (ops.mlp_layered_act) in place of policy.evaluate / policy.value.  Opt-in (AURPPO_LAYERED_ACT=1), independent of the
         # update's switch above; ``_mlp`` stays None.
         self._mlp_layered_act = None
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_act")
                 and os.environ.get("AURPPO_LAYERED_ACT", LAYERED_ACT_DEFAULT) != "0"):
-            self._mlp_layered_act = ops.mlp_layered_layout(self.policy, self.bucket)
+            self._mlp_layered_act = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
         self._act_wop = None       # the rollout's prepared operand copies (layered act), None outside _rollout_steps
         # the flat bucket holds the MLP policy and nothing else (up to alignment padding): K7 + clip + Adam can chain
         self._bucket_is_policy = self._mlp is not None and self.bucket.numel == self._mlp["n_params"]

@@ -251,14 +251,20 @@ int aurppo_mlp_ppo_apply_parts_f32(float* params, float* grads, float* exp_avg, 
  * mode 1: the gradient with respect to the input: x is the OUTPUT gradient (B, Co, H, W), z the input gradient
  * (B, Ci, H + 2 - 2 pad, W + 2 - 2 pad), w the same (Co, Ci, 3, 3) filter, pad the forward padding.  The product's input
  * channel count (Ci in mode 0, Co in mode 1) must be a multiple of 16.  wop_ws: aurppo_conv3x3_wop_bytes(input channels,
- * output channels of the product) bytes of scratch for the filter in operand order.  (The weight gradient: aurppo_conv3x3_wgrad_f32.) */
+ * output channels of the product) bytes of scratch for the filter in operand order (an input channel count that is no multiple
+ * of 16 -- a linear product's ragged inner dimension, below -- is rounded up to whole 16-column steps).  (The weight gradient:
+ * aurppo_conv3x3_wgrad_f32.) */
 size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm);
 int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w, int Co_w, int H, int W, int pad, int mode,
                        void* wop_ws, void* stream);
 
 /* nn.Linear without its bias on the same arithmetic (the MLP policies wider than the fused steps cover, hidden_dim > 128:
- * src/nets/nets.py:21-27,33-39,45-51 per layer).  mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T, K_w a multiple of 16;
+ * src/nets/nets.py:21-27,33-39,45-51 per layer).  mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T, any K_w >= 1;
  * mode 1 (gradient with respect to the input; x is dY): y (M, K_w) = x (M, N_w) . w, N_w a multiple of 16.  Row-major fp32.
+ * x must be 16-byte aligned at its base.  With K_w a multiple of 16 every row is, and a row's 16 columns of a step are two
+ * 16-byte loads; any other K_w (a state of 3, 11, 17, 376 floats in a policy's first layer) takes the tail builds: rows need 4-byte
+ * alignment only, every column is a load of its own that is issued only for columns < K_w, and nothing past a row's K_w
+ * floats is read -- x may end at the end of a mapping.
  * wop_ws: aurppo_conv3x3_wop_bytes(inner dimension, columns) bytes. */
 int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,
                       void* stream);
@@ -268,7 +274,9 @@ int aurppo_linear_bias_act_f32(const float* x, const float* w, const float* bias
                                int act, void* wop_ws, void* stream);
 /* nn.Linear's weight gradient on the same arithmetic: dw (N, K) = dy (M, N)^T . x (M, K) (what loss.backward() leaves in
  * <layer>.weight.grad, src/ppo.py:266).  Both operands are split once per workgroup through LDS; the minibatch's rows are cut
- * into slices whose partial products are summed in slice order (deterministic).  N, K multiples of 4; ws:
+ * into slices whose partial products are summed in slice order (deterministic).  N a multiple of 4, any K >= 1; dy and x
+ * 16-byte aligned at their bases.  With K a multiple of 4 the x rows are read in 16-byte pieces; any other K takes the tail
+ * builds (rows 4-byte aligned, one guarded load per column, nothing read past a row's K floats).  ws:
  * aurppo_linear_wgrad_ws_bytes(M, N, K) bytes. */
 size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K);
 int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream);
@@ -332,8 +340,9 @@ int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC
  *   aurppo_head_act_f32: K14 alone, from the last hidden activations hA, hC (N, H), 16-byte aligned (hA may be NULL without
  *     noise); layout_h: 5 float offsets {actor head weight (A, H), actor head bias, critic head weight (1, H), critic head bias,
  *     actor_logstd (ignored for the Categorical head)}.
- * Limits (AURPPO_ESHAPE otherwise): hidden / H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16), D a multiple of 16,
- * num_layers 1..16. */
+ * Limits (AURPPO_ESHAPE otherwise): hidden / H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16), any D >= 1 (no
+ * multiple of 16: layer 0 on the tail builds of aurppo_linear_f32, its operand copy padded with zero planes to whole 16-column
+ * steps; obs rows then need 4-byte alignment only, the base still 16), num_layers 1..16. */
 size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers);
 int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers, void* wop,
                                 void* stream);
