@@ -12,7 +12,9 @@
 // per pooled element) and 1.3 X backward (read dY and the mask, write dX; the bias sums fall out of the same loads).
 //
 // torch semantics kept: max-pool takes the FIRST maximum of a window in row-major scan order (ties); ReLU passes no
-// gradient at x <= 0; an odd trailing row / column is dropped by the pool (floor) and gets a zero gradient.
+// gradient at x <= 0; an odd trailing row / column is dropped by the pool (floor) and gets a zero gradient.  NaN propagates
+// as it does through torch's relu and max_pool2d: a NaN in a window wins the scan (`v > m || v != v`: the LAST NaN, and no finite
+// value displaces it), counts as alive (`!(m <= 0)`), so y is NaN there and the backward routes the gradient to that element.
 #include <type_traits>
 
 #include "common.h"
@@ -63,8 +65,8 @@ __global__ __launch_bounds__(kPoolThreads) void k_brp_fwd(const float* __restric
                 int k = 0;
 #pragma unroll
                 for (int u = 1; u < 4; ++u)
-                    if (v[e][u] > m) { m = v[e][u]; k = u; }      // strict: the first maximum wins, as torch's scan does
-                const bool alive = m > 0.0f;
+                    if (v[e][u] > m || v[e][u] != v[e][u]) { m = v[e][u]; k = u; }      // strict: the first maximum wins, as in torch's scan; a NaN always wins (header note)
+                const bool alive = !(m <= 0.0f);
                 yp[(size_t)ho * Wo + 2 * wq + e] = alive ? m : 0.0f;
                 mp[(size_t)ho * Wo + 2 * wq + e] = alive ? (uint8_t)k : (uint8_t)4;
             }
@@ -79,9 +81,9 @@ __global__ __launch_bounds__(kPoolThreads) void k_brp_fwd(const float* __restric
         for (int u = 0; u < 4; ++u) {
             const size_t o = (size_t)(2 * ho + (u >> 1)) * W + 2 * wo + (u & 1);
             const float v = xp[o] + (pp ? sv * pp[o] : 0.0f) + bv;
-            if (u == 0 || v > m) { m = v; k = u; }
+            if (u == 0 || v > m || v != v) { m = v; k = u; }
         }
-        const bool alive = m > 0.0f;
+        const bool alive = !(m <= 0.0f);
         yp[q] = alive ? m : 0.0f;
         mp[q] = alive ? (uint8_t)k : (uint8_t)4;
     }
@@ -224,7 +226,7 @@ extern "C" int aurppo_weighted_batch_sum_f32(const float* x, const float* w, flo
 // convolution is no matrix product worth an MFMA tile); weights come through scalar loads (uniform per workgroup).
 //
 // Semantics are those of conv2d(cat[obs, state plane]) + bias -> ReLU -> MaxPool2d(2): first maximum in scan order, nothing
-// through x <= 0.  The input needs no gradient (it is data), so the backward is complete with dW, db.
+// through x <= 0, NaN kept (the select and the alive test of K9 above).  The input needs no gradient (it is data), so the backward is complete with dW, db.
 namespace {
 
 constexpr int kFbThreads = 256;
@@ -303,9 +305,9 @@ __global__ __launch_bounds__(kFbThreads) void k_first_block_fwd(const float* __r
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float v = (acc[u] + sv * pl[u]) + bv;
-            if (u == 0 || v > m) { m = v; k = u; }
+            if (u == 0 || v > m || v != v) { m = v; k = u; }
         }
-        const bool alive = m > 0.0f;
+        const bool alive = !(m <= 0.0f);
         if (live) {
             const size_t o = (((size_t)b * Co + c) * Ho + ho) * Wo + wo;
             y[o] = alive ? m : 0.0f;
@@ -349,6 +351,7 @@ __global__ __launch_bounds__(kFbBwdThreads) void k_first_block_bwd(const float* 
     // nine scattered dword gathers per position and channel.  A window row is three consecutive floats, so it is ONE 12-byte
     // load from a column base clamped into the image; the border cases pick their taps out of it with selects.
     typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));
+    float nf = 0.0f;
     for (int q = lane; q < Ho * Wo; q += kWave) {
         const int mk = mp[q];
         const float g = mk < 4 ? gp[q] : 0.0f;
@@ -370,6 +373,7 @@ __global__ __launch_bounds__(kFbBwdThreads) void k_first_block_bwd(const float* 
                 a[ci * 9 + kh * 3 + 0] = fmaf(gk[0], x0, a[ci * 9 + kh * 3 + 0]);
                 a[ci * 9 + kh * 3 + 1] = fmaf(gk[1], x1, a[ci * 9 + kh * 3 + 1]);
                 a[ci * 9 + kh * 3 + 2] = fmaf(gk[2], x2, a[ci * 9 + kh * 3 + 2]);
+                nf = fmaf(0.0f, (v.x + v.y) + v.z, nf);              // NaN once a loaded value is not finite (see below)
             }
         }
         float* sg = a + CI * 9;
@@ -379,6 +383,35 @@ __global__ __launch_bounds__(kFbBwdThreads) void k_first_block_bwd(const float* 
         wo += dqw; ho += dqh;
         if (wo >= Wo) { wo -= Wo; ++ho; }
     }
+    // torch's dense weight gradient multiplies the gradient of EVERY convolution position -- zero at all but the pooled maxima -- with
+    // its input window, so a non-finite observation value makes every tap that reaches it NaN (0 * NaN, 0 * Inf); the walk above visits
+    // the maxima alone.  Its 3 x 3 loads cover every pooled window whole (the maximum sits inside its window), so `nf` has seen every
+    // value but an odd trailing row / column, which is read here.  Only when something was not finite -- never, in a healthy run -- does
+    // the wave look at every value and mark the taps that hold a 0 * x term of a position the walk did not visit (the visited one:
+    // mask & 3); a marked sum is NaN whatever else it holds.
+    if (H & 1)
+        for (int i = lane; i < CI * W; i += kWave) nf = fmaf(0.0f, ob[(size_t)(i / W) * H * W + (size_t)(H - 1) * W + i % W], nf);
+    if (W & 1)
+        for (int i = lane; i < CI * H; i += kWave) nf = fmaf(0.0f, ob[(size_t)(i / H) * H * W + (size_t)(i % H) * W + W - 1], nf);
+    const float nf_wave = wave_sum_dpp(nf);                 // (the same in every lane)
+    unsigned poisoned = 0u;                                 // bit ci * 9 + tap: the sum holds a 0 * (non-finite) term, so it is NaN
+    if (nf_wave != 0.0f) {
+        unsigned pm = 0u;
+        for (int i = lane; i < CI * H * W; i += kWave) {
+            if ((__float_as_uint(ob[i]) & 0x7f800000u) != 0x7f800000u) continue;
+            const int ci = i / (H * W), r = i - ci * H * W, qy = r / W, qx = r - qy * W;
+            for (int kh = 0; kh < 3; ++kh)
+                for (int kw = 0; kw < 3; ++kw) {
+                    const int py = qy - (kh - 1), px = qx - (kw - 1);      // the convolution position whose tap (kh, kw) reads the value
+                    if (py < 0 || py >= H || px < 0 || px >= W) continue;
+                    const int wy = py >> 1, wx = px >> 1;
+                    const bool visited = wy < Ho && wx < Wo && (mp[wy * Wo + wx] & 3) == (((py & 1) << 1) | (px & 1));
+                    if (!visited) pm |= 1u << (ci * 9 + kh * 3 + kw);
+                }
+        }
+        for (int t = 0; t < CI * 9; ++t)
+            if (__builtin_amdgcn_ballot_w64(((pm >> t) & 1u) != 0u)) poisoned |= 1u << t;
+    }
     const size_t g_ = (size_t)b * gridDim.y + cg;
     float red[NA];
 #pragma unroll
@@ -386,7 +419,7 @@ __global__ __launch_bounds__(kFbBwdThreads) void k_first_block_bwd(const float* 
     if (lane == 0) {
         float* dst = dw_part + (g_ * kFbCo + cc) * NT;
 #pragma unroll
-        for (int t = 0; t < CI * 9; ++t) dst[t] = red[t];
+        for (int t = 0; t < CI * 9; ++t) dst[t] = ((poisoned >> t) & 1u) ? __builtin_nanf("") : red[t];
         const float* G = red + CI * 9;         // all, top, bottom, left, right, tl, tr, bl, br
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
