@@ -30,8 +30,6 @@ AurppoKnobs parse_knobs() {
     k.k2_one_stream = env_int("AURPPO_K2_ONE_STREAM", 0);
     k.k2_link_wgs = env_int("AURPPO_K2_LINK_WGS", 48);
     k.k2_resolve_wgs = env_int("AURPPO_K2_RESOLVE_WGS", 256);
-    k.k2_post_stream = env_int("AURPPO_K2_POST_STREAM", 1);
-    k.k2_accept = env_int("AURPPO_K2_ACCEPT", 3) == 1 ? 1 : 3;       // 1 = k_fy_accept, anything else = the default k_fy_accept3
     k.k2_accept3_wgs = env_int("AURPPO_K2_ACCEPT3_WGS", 6);
     k.k2_starve = env_int("AURPPO_TEST_K2_STARVE", 0);
     k.gather_unroll = env_int("AURPPO_GATHER_UNROLL", 0);

@@ -82,13 +82,11 @@ struct AurppoKnobs {
     int k7_spare_cus;      // AURPPO_MLP_SPARE_CUS: CUs K7 / K7w leave to the side stream's shuffle kernels (default 8)
     int static_tiles;      // AURPPO_STATIC_TILES=1: K7 / K7w deal tiles by static stride instead of through the counter, which
                            // fixes the order of every sum (bit-reproducible gradients; tests/test_determinism.py)
-    int k2_one_stream;     // AURPPO_K2_ONE_STREAM=1: twist and resolves on the caller's stream (everything serial)
+    int k2_one_stream;     // AURPPO_K2_ONE_STREAM=1: the twist on the caller's stream (serial with the accepts; link + resolve keep their own)
     int k2_link_wgs;       // AURPPO_K2_LINK_WGS: workgroups of k_fy_link (default 48; 0 = one per 256 positions)
     int k2_resolve_wgs;    // AURPPO_K2_RESOLVE_WGS: workgroups of k_fy_resolve (default 256; 0 = one per 256 positions)
-    int k2_post_stream;    // AURPPO_K2_POST_STREAM: 1 (default since round 3) = link + resolve on a third stream of the handle; 0 = behind accept / fill
     int k2_starve;         // AURPPO_TEST_K2_STARVE (tests): the twist keeps this per cent of one shuffle's draws in stock, so shuffles run dry
     int k2_accept3_wgs;    // AURPPO_K2_ACCEPT3_WGS: workgroups of k_fy_accept3's relay (default 6)
-    int k2_accept;         // AURPPO_K2_ACCEPT: 3 (default) = k_fy_accept3 (relay between workgroups), 1 = k_fy_accept (one workgroup, rounds); always one of the two
     int gather_unroll;     // AURPPO_GATHER_UNROLL (0 = by row width)
     int gather_rows;       // AURPPO_GATHER_ROWS (0 = by row width)
 };

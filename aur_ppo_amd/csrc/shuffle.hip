@@ -12,17 +12,16 @@
 //      output, a register), two phases share a barrier, and eight helper waves store the words -- UNTEMPERED: the consumers
 //      temper what they read -- to a ring in HBM one barrier behind the four that twist.  It runs one shuffle ahead of its
 //      consumer on the handle's own stream.
-//   1b. k_fy_accept3 (default; k_fy_accept is the one-workgroup build it grew from, AURPPO_K2_ACCEPT=1) -- turns the draws into
-//      accept/reject decisions.  Whether draw p is accepted depends on the index i it is tried against, i.e. on how
-//      many earlier draws were accepted -- a triangular system.  A thread resolves its own consecutive draws exactly
+//   1b. k_fy_accept3 -- turns the draws into accept/reject decisions.  Whether draw p is accepted depends on the index i
+//      it is tried against, i.e. on how many earlier draws were accepted -- a triangular system.  A thread resolves its own consecutive draws exactly
 //      given its starting index; inside a workgroup the starting indices are the fixed point of
 //      "i_t = i0 - (#accepts of earlier threads)", iterated with prefix sums until no count changes; BETWEEN workgroups
 //      only the index at a chunk boundary is handed on, and a workgroup has solved its 16 384-draw chunk from a guessed
 //      index -- and listed the few hundred draws the true one can change -- before its predecessor's word arrives.
 //      Output: the swap targets j[1..n).
 //   2. k_fy_link / k_fy_resolve -- given j, the final content of every position is found in
-//      parallel with no swaps at all (link behind the accept; resolve on the fill stream, beside the NEXT accept).  Step s writes old x[s] into position j_s, so "what sits in
-//      position q just before step t" is "what step min{s>t : j_s=q} put there", recursively.
+//      parallel with no swaps at all (both on a third stream of the handle, beside the NEXT accept and the NEXT fill).
+//      Step s writes old x[s] into position j_s, so "what sits in position q just before step t" is "what step min{s>t : j_s=q} put there", recursively.
 //      Linked lists per target (atomicExch) give those predecessor sets; chains are O(log n) and
 //      almost always empty, so each element resolves with a handful of L2-resident loads.
 // The generator state (key[624], pos) stays on the device between calls, like numpy's global stream.
@@ -37,7 +36,7 @@ struct aurppo_rng {
     uint32_t* d_last;    // [624] untempered form of the last block written to the ring
     uint32_t* d_ring;    // ring of tempered draws; stream word g lives at d_ring[g % ring_cap]
     long long* d_pos;    // [0] words written (stream offset), [1] words consumed (read cursor), [2] sticky error
-    // Shuffle e's accept + link run on the caller's stream while shuffle e-1's resolve runs on the fill stream, so the
+    // Shuffle e's accept runs on the caller's stream while shuffle e-1's link + resolve run on the post stream, so the
     // per-shuffle scratch is multi-buffered: swap targets and list links by parity, list heads three deep (the accept
     // of shuffle e clears the heads shuffle e+1 will link into while shuffle e-1's resolve may still read its own).
     int32_t* d_j[2];     // swap targets
@@ -49,10 +48,9 @@ struct aurppo_rng {
     int max_n;
     size_t head_cap;     // entries per d_head buffer (max_n rounded up to whole clear chunks)
     size_t ring_cap;     // words, a multiple of 624
-    hipStream_t fill_stream;   // the twist runs one shuffle ahead of its consumer on this stream; resolves follow it there
-    hipStream_t post_stream;   // AURPPO_K2_POST_STREAM=1: link + resolve run here, beside the next accept AND the next fill
-    int use_post;
-    hipEvent_t ev_fill[2], ev_acc[2], ev_link[2], ev_post[2], ev_res, ev_sync;
+    hipStream_t fill_stream;   // the twist runs one shuffle ahead of its consumer on this stream, which carries nothing else
+    hipStream_t post_stream;   // link + resolve run here, beside the next accept AND the next fill
+    hipEvent_t ev_fill[2], ev_acc[2], ev_post[2], ev_res, ev_sync;
     unsigned long long* d_relay;   // k_fy_accept3: one word per chunk of draws {launch tag, index after the chunk} + the `done` word
     int relay_cap;
     unsigned acc_gen;    // launch tag of the next k_fy_accept3 (never reset: a stale word of an earlier shuffle must not match)
@@ -236,19 +234,12 @@ __global__ __launch_bounds__(kFillThreads) void k_state_at_cursor(const uint32_t
     if (tid == 0) out[kMtN] = (uint32_t)pos;
 }
 
-// Diagnostic build only (tools/accept_stamps.py, -DAURPPO_ACC_STAMPS): thread 0 accumulates cycles per section of
-// a step into posv[8..]; the product library is built without it.
+// Diagnostic build only (tools/accept_stamps.py, -DAURPPO_ACC_STAMPS): thread 0 of one k_fy_accept3 workgroup accumulates
+// cycles per section of a chunk, written to posv[8..] at the end; the product library is built without it.
 #ifdef AURPPO_ACC_STAMPS
-#define ASTAMP(k)                                                      \
-    do {                                                               \
-        if (tid == 0) {                                                \
-            const unsigned long long t__ = __builtin_readcyclecounter(); \
-            st_acc[k] += t__ - st_last;                                \
-            st_last = t__;                                             \
-        }                                                              \
-    } while (0)
+#define TST(k) do { if (tid == 0) { const unsigned long long t__ = __builtin_readcyclecounter(); t_cyc[k] += t__ - t_last; t_last = t__; } } while (0)
 #else
-#define ASTAMP(k) do { } while (0)
+#define TST(k) do { } while (0)
 #endif
 
 // Wave-wide inclusive prefix sum with DPP moves only (no LDS): row_shr 1/2/4/8 inside each row of 16 lanes, then
@@ -271,236 +262,145 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
-// kWpt = draws per thread per step.
-//
-// One step: every thread owns kWpt consecutive draws.  Whether a draw is accepted depends on the index it is
-// tried against, i.e. on the number of accepts before it; a thread resolves its own draws exactly given its
-// starting index i0, and the starting indices are the fixed point of "i0 = i_cur - (#accepts of earlier threads)".
-// Round: publish the per-wave accept counts (+ "did any of my counts change in the last evaluation"), ONE
-// barrier, every wave rebuilds its base from the 16 wave sums; when nobody changed, (excl, cnt) is the solution.
-// Common case per evaluation (count_fast): all of a thread's draws sit in one mask octave and none falls in the
+// Expected index `draws` draws after index i0: di/dp = -(i + 1) / (mask + 1), integrated octave by octave (the mask halves
+// where i crosses a power of two).
+__device__ __forceinline__ int expected_index(int i0, float draws) {
+    float fi = (float)(i0 + 1);
+    float m1 = (float)(0xffffffffu >> __clz(i0 | 1)) + 1.0f;
+    for (int k = 0; k < 32; ++k) {
+        const float to_edge = m1 * __logf(fi / (0.5f * m1));      // draws until i + 1 reaches the bottom of this octave
+        if (draws <= to_edge || m1 <= 2.0f) {
+            fi *= __expf(-draws / m1);
+            break;
+        }
+        draws -= to_edge;
+        fi = 0.5f * m1;
+        m1 *= 0.5f;
+    }
+    return (int)fi - 1;
+}
+
+// One lane's share of the accept stage: kWpt consecutive draws.  Whether a draw is accepted depends on the index it is
+// tried against, i.e. on the number of accepts before it; a lane resolves its own draws exactly given its starting index
+// i0, and the starting indices are the fixed point of "i0 = i_start - (#accepts of earlier lanes)" (k_fy_accept3's rounds).
+// Common case per evaluation (the shortcut count): all of a lane's draws sit in one mask octave and none falls in the
 // window (i0 - kWpt, i0] the index moves through, so "#draws <= i0 - kWpt" is the count -- ~5 VALU ops per draw.
 // Anything else (octave edge, tail of the shuffle, a draw inside the window) sends the whole wave through the
 // literal per-draw loop behind a wave-uniform branch, so the fast path never pays for it.
-template <int kAccThreads, int kWpt>
-__global__ __launch_bounds__(kAccThreads) void k_fy_accept(const uint32_t* __restrict__ ring, long long ring_cap,
-                                                           int32_t* __restrict__ j, int n,
-                                                           long long* __restrict__ posv, int done_slot) {
-    constexpr int kAccStep = kAccThreads * kWpt;
-    constexpr int kWaves = kAccThreads / kWave;   // <= 16: one row of lanes reads all wave sums
-    static_assert(kWaves >= 1 && kWaves <= 16, "wave sums are combined inside one DPP row");
-    __shared__ int s_wsum[2][kWaves];
-    __shared__ int s_chg[2][kWaves];
-    __shared__ int s_end;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    long long cursor = posv[1];               // stream offset of the next unread draw
-    const long long avail = posv[0];          // draws written so far (the fill for this shuffle has completed)
-    long long rpos = cursor % ring_cap;       // cursor's slot in the ring, kept incrementally
-    int i_cur = n - 1;                        // next index to draw a target for
-    float rate = 0.72f;                        // acceptance rate guess, refreshed every step
-    int par = 0;                              // exchange-buffer parity (runs on across steps)
-    // this step's draws are fetched one step ahead (every step but the last consumes exactly kAccStep)
-    uint32_t ynext[kWpt];
-    // Branch-free: draws past `avail` are fetched from some valid ring slot and never looked at (nhave below),
-    // so the loads are straight-line code and the wait at the top of the next step is for exactly these loads.
-    // A thread's kWpt consecutive words come as 16-byte vector loads (4-byte aligned: the cursor is arbitrary);
-    // dword loads at this stride cost one cache-line access per lane per word -- the vector memory pipe, not the
-    // arithmetic, was what a step waited for.  The ring's mirrored head makes the run contiguous at the wrap.
-    static_assert(kWpt % 4 == 0 && kWpt <= kRingMirror, "draws are fetched four at a time from a mirrored ring");
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));
-    auto fetch = [&](long long rp) {
-        long long r0 = rp + (long long)tid * kWpt;
-        if (r0 >= ring_cap) r0 -= ring_cap;
-        if (r0 >= ring_cap) r0 = 0;
-        const u32x4u* src = reinterpret_cast<const u32x4u*>(ring + r0);
-#pragma unroll
-        for (int q = 0; q < kWpt / 4; ++q) {
-            const u32x4u v = src[q];
-            ynext[4 * q + 0] = v.x; ynext[4 * q + 1] = v.y; ynext[4 * q + 2] = v.z; ynext[4 * q + 3] = v.w;
-        }
-    };
-    fetch(rpos);
-#ifdef AURPPO_ACC_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_readcyclecounter(), n_steps = 0, n_iters = 0;
-#endif
-    while (i_cur >= 1 && cursor < avail) {
-        const long long base = cursor + (long long)tid * kWpt;
-        uint32_t y[kWpt];
-        int nhave = 0;                             // my draws that exist (a prefix of the kWpt)
+template <int kWpt>
+struct AcceptLane {
+    uint32_t y[kWpt];        // my draws, tempered
+    int nhave;               // my draws that exist (a prefix of the kWpt)
+    int cnt, incl;           // #accepted at the last evaluation, and its inclusive prefix sum over the wave
+    uint32_t dn, up;         // slack of the shortcut count (eval)
+    bool sure;               // my draws allow the shortcut
+    int ref_i0;              // where (cnt, dn, up) were evaluated
+    bool wave_fast;          // every lane of this wave is on the shortcut
+
+    // the literal rule for my draws from starting index i0: #accepted; optionally stages targets (index i at stage[top - i]) / #consumed
+    __device__ __forceinline__ int walk(int i0, bool emit, int& consumed, int32_t* stage = nullptr, int top = 0) const {
+        int i = i0, acc = 0;
+        consumed = 0;
 #pragma unroll
         for (int u = 0; u < kWpt; ++u) {
-            y[u] = mt_temper(ynext[u]);     // the ring holds the untempered words
-            nhave += (base + u) < avail ? 1 : 0;
-        }
-        ASTAMP(0);   // draws of this step in registers (waits for the fetch issued one step ago)
-        {
-            long long rn = rpos + kAccStep;
-            if (rn >= ring_cap) rn -= ring_cap;
-            fetch(rn);
-        }
-        ASTAMP(1);   // next fetch issued
-        // the literal rule for my draws from starting index i0: #accepted; optionally emits targets / #consumed
-        auto walk = [&](int i0, bool emit, int& consumed) -> int {
-            int i = i0, acc = 0;
-            consumed = 0;
-#pragma unroll
-            for (int u = 0; u < kWpt; ++u) {
-                if (u < nhave && i >= 1) {
-                    const uint32_t v = y[u] & (0xffffffffu >> __clz(i));
-                    ++consumed;
-                    if (v <= (uint32_t)i) {
-                        if (emit) j[i] = (int32_t)v;
-                        --i;
-                        ++acc;
-                    }
+            if (u < nhave && i >= 1) {
+                const uint32_t v = y[u] & (0xffffffffu >> __clz(i));
+                ++consumed;
+                if (v <= (uint32_t)i) {
+                    if (emit) stage[top - i] = (int32_t)v;
+                    --i;
+                    ++acc;
                 }
             }
-            return acc;
-        };
-        // Shortcut evaluation at starting index i0.  Returns #draws <= i0 - kWpt and the slack of that count: it
-        // stays the same (and the shortcut stays valid) while i0 moves up by at most `up - kWpt` or down by at most
-        // `dn` -- the distances from i0 - kWpt to the nearest draw above / at-or-below it.
-        uint32_t dn = 0, up = 0;
-        bool sure = false;
-        int ref_i0 = 0;          // where (cnt, dn, up) were evaluated
-        bool wave_fast = false;  // every lane of this wave is on the shortcut
-        auto eval = [&](int i0) -> int {
-            const bool shape = nhave == kWpt && i0 > kWpt && __clz(i0) == __clz(i0 - kWpt);
+        }
+        return acc;
+    }
+    // Shortcut evaluation at starting index i0.  Returns #draws <= i0 - kWpt and keeps the slack of that count: it
+    // stays the same (and the shortcut stays valid) while i0 moves up by at most `up - kWpt` or down by at most
+    // `dn` -- the distances from i0 - kWpt to the nearest draw above / at-or-below it.
+    __device__ __forceinline__ int eval(int i0) {
+        const bool shape = nhave == kWpt && i0 > kWpt && __clz(i0) == __clz(i0 - kWpt);
+        const uint32_t mask = 0xffffffffu >> __clz(i0 | 1);
+        const uint32_t lo = (uint32_t)(i0 - kWpt);
+        int c = 0;
+        uint32_t d = 0xffffffffu, p = 0xffffffffu;
+#pragma unroll
+        for (int u = 0; u < kWpt; ++u) {
+            const uint32_t v = y[u] & mask;
+            const bool le = v <= lo;
+            c += le ? 1 : 0;
+            d = le ? min(d, lo - v) : d;
+            p = le ? p : min(p, v - lo - 1u);
+        }
+        dn = d;
+        up = p;
+        sure = shape && p >= (uint32_t)kWpt;      // no draw inside the window (i0 - kWpt, i0] the index moves through
+        ref_i0 = i0;
+        wave_fast = __builtin_amdgcn_ballot_w64(!sure) == 0ull;
+        if (!wave_fast) {   // wave-uniform and rare: the literal rule for everybody
+            int consumed;
+            c = walk(i0, false, consumed);
+        }
+        return c;
+    }
+    // is (cnt, shortcut) evaluated at ref_i0 still right at i0?
+    __device__ __forceinline__ bool still_ok(int i0) const {
+        const int delta = i0 - ref_i0;
+        const bool shape = i0 > kWpt && __clz(i0) == __clz(i0 - kWpt) && __clz(i0) == __clz(ref_i0);
+        const bool room = delta >= 0 ? up >= (uint32_t)(kWpt + delta) : dn >= (uint32_t)(-delta);
+        return delta == 0 || (sure && shape && room);
+    }
+    __device__ __forceinline__ void count(int i0) {
+        cnt = eval(i0);
+        incl = wave_incl_scan(cnt);
+    }
+    // My starting index moved to i0.  A lane recounts only if its index left the slack of its last evaluation; a wave whose
+    // lanes all stay inside keeps its counts and its scan (typical: one or two waves per round redo).  Did any count move?
+    __device__ __forceinline__ bool recount(int i0) {
+        if (__builtin_amdgcn_ballot_w64(!still_ok(i0)) == 0ull) return false;
+        const int before = cnt;
+        count(i0);
+        return __builtin_amdgcn_ballot_w64(cnt != before) != 0ull;
+    }
+    // Decisions are final: my targets from starting index i0, staged in index order (index i at stage[top - i]).  Returns #consumed.
+    __device__ __forceinline__ int emit(int i0, bool literal, int32_t* stage, int top) const {
+        int consumed = kWpt;
+        if (literal) {
+            (void)walk(i0, true, consumed, stage, top);
+        } else {
             const uint32_t mask = 0xffffffffu >> __clz(i0 | 1);
             const uint32_t lo = (uint32_t)(i0 - kWpt);
-            int c = 0;
-            uint32_t d = 0xffffffffu, p = 0xffffffffu;
+            int i = i0;
 #pragma unroll
             for (int u = 0; u < kWpt; ++u) {
                 const uint32_t v = y[u] & mask;
-                const bool le = v <= lo;
-                c += le ? 1 : 0;
-                d = le ? min(d, lo - v) : d;
-                p = le ? p : min(p, v - lo - 1u);
-            }
-            dn = d;
-            up = p;
-            sure = shape && p >= (uint32_t)kWpt;      // no draw inside the window (i0 - kWpt, i0] the index moves through
-            ref_i0 = i0;
-            wave_fast = __builtin_amdgcn_ballot_w64(!sure) == 0ull;
-            if (!wave_fast) {   // wave-uniform and rare: the literal rule for everybody
-                int consumed;
-                c = walk(i0, false, consumed);
-            }
-            return c;
-        };
-        // is (cnt, shortcut) evaluated at ref_i0 still right at i0?
-        auto still_ok = [&](int i0) -> bool {
-            const int delta = i0 - ref_i0;
-            const bool shape = i0 > kWpt && __clz(i0) == __clz(i0 - kWpt) && __clz(i0) == __clz(ref_i0);
-            const bool room = delta >= 0 ? up >= (uint32_t)(kWpt + delta) : dn >= (uint32_t)(-delta);
-            return delta == 0 || (sure && shape && room);
-        };
-        int cur_i0 = i_cur - (int)(rate * (float)(tid * kWpt));   // first guess of my starting index
-        int cnt = eval(cur_i0);
-        int incl = wave_incl_scan(cnt);
-        bool wchg = true;                                // forces the first exchange
-        int total = 0;
-        ASTAMP(2);   // first guess
-        for (;;) {
-#ifdef AURPPO_ACC_STAMPS
-            ++n_iters;
-#endif
-            if (lane == kWave - 1) {
-                s_wsum[par][wave] = incl;
-                s_chg[par][wave] = wchg ? 1 : 0;
-            }
-            ASTAMP(6);   // (inside the loop) publish
-            __syncthreads();
-            ASTAMP(7);   // (inside the loop) barrier
-            const int ws = lane < kWaves ? s_wsum[par][lane] : 0;
-            const int wc = lane < kWaves ? s_chg[par][lane] : 0;
-            par ^= 1;
-            const int pre = row_incl_scan(ws);                          // lanes 0..15: prefix over the wave sums
-            total = __builtin_amdgcn_readlane(pre, kWaves - 1);
-            const int wbase = wave > 0 ? __builtin_amdgcn_readlane(pre, wave > 0 ? wave - 1 : 0) : 0;
-            const bool any = __builtin_amdgcn_ballot_w64(wc != 0) != 0ull;
-            if (!any) break;     // no wave's counts moved in the last evaluation: (cur_i0, cnt) is the fixed point
-            cur_i0 = i_cur - (wbase + incl - cnt);
-            // A lane recounts only if its index left the slack of its last evaluation; a wave whose lanes all
-            // stay inside keeps its counts, its scan and its published sum (typical: one or two waves per step redo).
-            if (__builtin_amdgcn_ballot_w64(!still_ok(cur_i0)) == 0ull) {
-                wchg = false;
-            } else {
-                const int cnt2 = eval(cur_i0);
-                wchg = __builtin_amdgcn_ballot_w64(cnt2 != cnt) != 0ull;
-                cnt = cnt2;
-                incl = wave_incl_scan(cnt);
+                if (v <= lo) stage[top - (i--)] = (int32_t)v;
             }
         }
-        ASTAMP(3);   // fixed point reached
-        // decisions are final: emit the targets
-        int consumed = kWpt;
-        if (!wave_fast) {
-            (void)walk(cur_i0, true, consumed);
-        } else {
-            const uint32_t mask = 0xffffffffu >> __clz(cur_i0 | 1);
-            const uint32_t lo = (uint32_t)(cur_i0 - kWpt);
-            int i = cur_i0;
-#pragma unroll
-            for (int u = 0; u < kWpt; ++u) {
-                const uint32_t v = y[u] & mask;
-                if (v <= lo) j[i--] = (int32_t)v;
-            }
-        }
-        ASTAMP(4);   // targets emitted
-        long long step_words = avail - cursor < kAccStep ? avail - cursor : kAccStep;
-        if (total >= i_cur) {
-            // last step: words consumed = everything up to and including the draw that filled i = 1
-            const int my_end_i = cur_i0 - cnt;          // index after my draws
-            if (tid == 0) s_end = -1;
-            __syncthreads();
-            if (cnt > 0 && my_end_i == 0) s_end = tid * kWpt + consumed;   // unique thread
-            __syncthreads();
-            step_words = s_end;
-        }
-        rate = step_words > 0 ? (float)total / (float)step_words : rate;
-        i_cur -= total;
-        cursor += step_words;
-        rpos += step_words;
-        if (rpos >= ring_cap) rpos -= ring_cap;
-        ASTAMP(5);   // step bookkeeping
-#ifdef AURPPO_ACC_STAMPS
-        ++n_steps;
-#endif
+        return consumed;
     }
-#ifdef AURPPO_ACC_STAMPS
-    if (tid == 0) {
-        for (int k = 0; k < 8; ++k) posv[8 + k] = (long long)st_acc[k];
-        posv[16] = (long long)n_steps;
-        posv[17] = (long long)n_iters;
-    }
-#endif
-    if (tid == 0) {
-        posv[1] = cursor;
-        posv[done_slot] = cursor;      // this shuffle's final cursor, for the fill two shuffles later
-        if (i_cur >= 1) posv[2] = 1;   // ran out of draws before the shuffle finished: sticky error
-    }
-}
+};
 
-// k_fy_accept3 -- a relay between WORKGROUPS, with k_fy_accept's fixed point inside each.  (A relay between the WAVES of one
-// workgroup, k_fy_accept2, was bit-exact and slower -- 515 us per shuffle against 394 -- and was retired in round 4: DESIGN 4.2c.)
+// k_fy_accept3 -- a relay between WORKGROUPS, with the lanes' fixed point inside each.  (Both kernels it replaced were bit-exact
+// and were retired, DESIGN 4.2c: k_fy_accept2, a relay between the WAVES of one workgroup, 515 us per shuffle against 394; and
+// k_fy_accept, one workgroup walking the draw stream 8192 draws at a time: ~89 steps of ~4.6 us per 524 288-element shuffle,
+// every one on the chain -- in-situ 437 us per shuffle, four per update: the longest pipeline of the update in round 3.)
 //
-// k_fy_accept is one workgroup walking the draw stream 8192 draws at a time: ~89 steps of ~4.6 us per 524 288-element shuffle,
-// every one on the chain (in-situ 437 us per shuffle, four per update: the longest pipeline of the update in round 3).  What a
-// stretch of draws needs from everything before it is ONE number, the index it starts at; where it starts in the stream is
-// known beforehand, because every chunk but the last consumes all of its draws.  So:
-//   * G workgroups (one per spare CU) own chunks g, g + G, ... of 1024 x kWpt consecutive draws (32 768 at kWpt = 32: 23 chunks
-//     per shuffle of 524 288);
-//   * a workgroup solves its chunk AHEAD of time from a guessed starting index (expected trajectory from the latest chunk anybody
-//     has confirmed), with k_fy_accept's rounds -- one workgroup barrier each --, and forms the window [LO, HI] of starting indices
-//     for which every lane's count stands;
-//   * thread 0 then polls its predecessor's word {launch tag, index after the chunk} (coherent loads); inside the window it
-//     publishes its own word at once -- the chain per chunk is then one cross-workgroup hop --, otherwise the workgroup re-runs
-//     the rounds from the true index (the lanes whose slack was exceeded recount) and publishes after;
-//   * targets are emitted after the word is out.  The workgroup that ends the shuffle (or runs out of draws) writes the cursor
-//     and raises the `done` word, on which everybody still waiting leaves.
+// What a stretch of draws needs from everything before it is ONE number, the index it starts at; where it starts in the stream
+// is known beforehand, because every chunk but the last consumes all of its draws.  So:
+//   * fetch: G workgroups (one per spare CU) own chunks g, g + G, ... of 1024 x kWpt consecutive draws (16 384 at kWpt = 16: 45
+//     chunks per shuffle of 524 288), each fetched one chunk ahead;
+//   * guess, solve: a workgroup solves its chunk AHEAD of time from a guessed starting index (expected trajectory from the latest
+//     chunk anybody has confirmed) by rounds -- publish the per-wave accept counts (+ "did any of my counts change in the last
+//     evaluation"), ONE workgroup barrier, every wave rebuilds its base from the 16 wave sums; when nobody changed, the lanes'
+//     (starting index, count) are the solution;
+//   * list: the few hundred draws whose decision the true starting index can change go into a list in LDS;
+//   * relay: thread 0 then polls its predecessor's word {launch tag, index after the chunk} (coherent loads); one wave walks the
+//     list from the true index and publishes the workgroup's own word at once -- the chain per chunk is then one cross-workgroup
+//     hop --; if the guess was too far off for the list, the word goes out after the next step instead;
+//   * redo: the rounds again from the true index (only the lanes whose slack was exceeded recount);
+//   * emit: targets are staged and stored after the word is out.  The workgroup that ends the shuffle (or runs out of draws)
+//     writes the cursor and raises the `done` word, on which everybody still waiting leaves.
 // Decisions and the words consumed are exactly numpy's: the same literal rule decides wherever a shortcut does not apply.
 template <int kAccThreads, int kWpt>
 __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __restrict__ ring, long long ring_cap,
@@ -536,7 +436,11 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
     uint32_t ynext[kWpt];
     long long r_next = (cursor0 + (long long)blockIdx.x * kChunk + (long long)tid * kWpt) % ring_cap;
     const long long r_step = ((long long)G * kChunk) % ring_cap;
-    auto fetch = [&]() {             // branch-free: draws past `avail` come from some valid slot and are never looked at
+    // A chunk's draws are fetched one chunk ahead.  Branch-free: draws past `avail` come from some valid slot and are never looked
+    // at (nhave), so the loads are straight-line code.  A thread's kWpt consecutive words come as 16-byte vector loads (4-byte
+    // aligned: the cursor is arbitrary); dword loads at this stride cost one cache-line access per lane per word -- the vector
+    // memory pipe, not the arithmetic, was what a step waited for.  The ring's mirrored head makes the run contiguous at the wrap.
+    auto fetch = [&]() {
         const long long r0 = r_next;
         r_next += r_step;
         if (r_next >= ring_cap) r_next -= ring_cap;
@@ -549,77 +453,20 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
     };
     fetch();
     int par = 0;                                      // exchange-buffer parity (runs on across chunks)
-#ifdef AURPPO_ACC_STAMPS   // tools/accept_stamps.py: thread 0 of workgroup 1 (a steady-state member of the relay), cycles per section
+#ifdef AURPPO_ACC_STAMPS   // TST: thread 0 of workgroup 1 (a steady-state member of the relay), cycles per section
     unsigned long long t_cyc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_last = __builtin_readcyclecounter();
     unsigned long long t_chunks = 0, t_fast = 0, t_list = 0, t_ent = 0, t_delta = 0, t_rounds = 0, t_w = 0;
-#define TST(k) do { if (tid == 0) { const unsigned long long t__ = __builtin_readcyclecounter(); t_cyc[k] += t__ - t_last; t_last = t__; } } while (0)
-#else
-#define TST(k) do { } while (0)
 #endif
     for (int c = blockIdx.x; c < relay_cap; c += G) {
         const long long cbase = cursor0 + (long long)c * kChunk;
-        uint32_t y[kWpt];
-        int nhave = 0;                                // my draws that exist (a prefix of the kWpt)
+        AcceptLane<kWpt> me;
+        me.nhave = 0;
 #pragma unroll
         for (int u = 0; u < kWpt; ++u) {
-            y[u] = mt_temper(ynext[u]);     // the ring holds the untempered words
-            nhave += (cbase + (long long)tid * kWpt + u) < avail ? 1 : 0;
+            me.y[u] = mt_temper(ynext[u]);     // the ring holds the untempered words
+            me.nhave += (cbase + (long long)tid * kWpt + u) < avail ? 1 : 0;
         }
         fetch();
-        int stage_top = 0;                            // the chunk's first index (set before anything is emitted)
-        // the literal rule for my draws from starting index i0: #accepted; optionally stages targets / #consumed
-        auto walk = [&](int i0, bool emit, int& consumed) -> int {
-            int i = i0, acc = 0;
-            consumed = 0;
-#pragma unroll
-            for (int u = 0; u < kWpt; ++u) {
-                if (u < nhave && i >= 1) {
-                    const uint32_t v = y[u] & (0xffffffffu >> __clz(i));
-                    ++consumed;
-                    if (v <= (uint32_t)i) {
-                        if (emit) s_stage[stage_top - i] = (int32_t)v;
-                        --i;
-                        ++acc;
-                    }
-                }
-            }
-            return acc;
-        };
-        uint32_t dn = 0, up = 0;
-        bool sure = false;
-        int ref_i0 = 0;
-        bool wave_fast = false;
-        auto eval = [&](int i0) -> int {          // as in k_fy_accept: #draws <= i0 - kWpt, and the slack of that count
-            const bool shape = nhave == kWpt && i0 > kWpt && __clz(i0) == __clz(i0 - kWpt);
-            const uint32_t mask = 0xffffffffu >> __clz(i0 | 1);
-            const uint32_t lo = (uint32_t)(i0 - kWpt);
-            int cc = 0;
-            uint32_t d = 0xffffffffu, pp = 0xffffffffu;
-#pragma unroll
-            for (int u = 0; u < kWpt; ++u) {
-                const uint32_t v = y[u] & mask;
-                const bool le = v <= lo;
-                cc += le ? 1 : 0;
-                d = le ? min(d, lo - v) : d;
-                pp = le ? pp : min(pp, v - lo - 1u);
-            }
-            dn = d;
-            up = pp;
-            sure = shape && pp >= (uint32_t)kWpt;
-            ref_i0 = i0;
-            wave_fast = __builtin_amdgcn_ballot_w64(!sure) == 0ull;
-            if (!wave_fast) {
-                int consumed;
-                cc = walk(i0, false, consumed);
-            }
-            return cc;
-        };
-        auto still_ok = [&](int i0) -> bool {
-            const int delta = i0 - ref_i0;
-            const bool shape = i0 > kWpt && __clz(i0) == __clz(i0 - kWpt) && __clz(i0) == __clz(ref_i0);
-            const bool room = delta >= 0 ? up >= (uint32_t)(kWpt + delta) : dn >= (uint32_t)(-delta);
-            return delta == 0 || (sure && shape && room);
-        };
         // ---- where to start from: the chunk before mine if it is confirmed already, else a guess from the latest confirmed one
         int i_start = n - 1;
         bool have_start = c == 0;
@@ -648,33 +495,25 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
                 i_start = i_ref;
                 have_start = true;
             } else {
-                // expected trajectory: di/dp = -(i + 1) / (mask + 1), octave by octave (the mask halves where i crosses a power of two)
-                float fi = (float)(i_ref + 1), between = (float)(c - 1 - c_ref) * (float)kChunk;
-                float m1 = (float)(0xffffffffu >> __clz(i_ref | 1)) + 1.0f;
-                for (int k = 0; k < 32; ++k) {
-                    const float to_edge = m1 * __logf(fi / (0.5f * m1));      // draws until i + 1 reaches the bottom of this octave
-                    if (between <= to_edge || m1 <= 2.0f) {
-                        fi *= __expf(-between / m1);
-                        break;
-                    }
-                    between -= to_edge;
-                    fi = 0.5f * m1;
-                    m1 *= 0.5f;
-                }
-                i_start = (int)fi - 1;
+                i_start = expected_index(i_ref, (float)(c - 1 - c_ref) * (float)kChunk);
             }
         }
         TST(0);      // draws in registers, next fetch issued, reference for the guess read
-        // ---- k_fy_accept's fixed point over the chunk, from starting index i_cur (first call: from the expected trajectory)
-        int cur_i0, cnt, incl, total = 0, wbase = 0;
-        bool wchg = true;
+        // ---- the lanes' fixed point over the chunk, from starting index i_cur (first call: from the expected trajectory)
+        int cur_i0, total = 0, wbase = 0;
+        bool wchg = true;                                // forces the first exchange
+        // the chunk starts at i_from: my starting index from the counts before me, and my own count there if it has to be redone
+        auto restart = [&](int i_from) {
+            cur_i0 = i_from - (wbase + me.incl - me.cnt);
+            wchg = me.recount(cur_i0);
+        };
         auto rounds = [&](int i_cur) {
             for (;;) {
 #ifdef AURPPO_ACC_STAMPS
                 ++t_rounds;
 #endif
                 if (lane == kWave - 1) {
-                    s_wsum[par][wave] = incl;
+                    s_wsum[par][wave] = me.incl;
                     s_chg[par][wave] = wchg ? 1 : 0;
                 }
                 __syncthreads();
@@ -686,36 +525,14 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
                 wbase = wave > 0 ? __builtin_amdgcn_readlane(pre, wave > 0 ? wave - 1 : 0) : 0;
                 const bool any = __builtin_amdgcn_ballot_w64(wc != 0) != 0ull;
                 if (!any) break;     // no wave's counts moved in the last evaluation: (cur_i0, cnt) is the fixed point
-                cur_i0 = i_cur - (wbase + incl - cnt);
-                if (__builtin_amdgcn_ballot_w64(!still_ok(cur_i0)) == 0ull) {
-                    wchg = false;
-                } else {
-                    const int cnt2 = eval(cur_i0);
-                    wchg = __builtin_amdgcn_ballot_w64(cnt2 != cnt) != 0ull;
-                    cnt = cnt2;
-                    incl = wave_incl_scan(cnt);
-                }
+                restart(i_cur);
             }
         };
-        {
-            // expected index at my first draw (same trajectory, tid * kWpt draws on)
-            float fi = (float)(i_start + 1), between = (float)(tid * kWpt);
-            float m1 = (float)(0xffffffffu >> __clz(i_start | 1)) + 1.0f;
-            for (int k = 0; k < 32; ++k) {
-                const float to_edge = m1 * __logf(fi / (0.5f * m1));
-                if (between <= to_edge || m1 <= 2.0f) {
-                    fi *= __expf(-between / m1);
-                    break;
-                }
-                between -= to_edge;
-                fi = 0.5f * m1;
-                m1 *= 0.5f;
-            }
-            cur_i0 = i_start >= 1 ? (int)fi - 1 : i_start;
-            cnt = eval(cur_i0);
-            incl = wave_incl_scan(cnt);
-            rounds(i_start);
-        }
+        // expected index at my first draw (same trajectory, tid * kWpt draws on)
+        const int i_guess = expected_index(i_start, (float)(tid * kWpt));
+        cur_i0 = i_start >= 1 ? i_guess : i_start;
+        me.count(cur_i0);
+        rounds(i_start);
         TST(1);      // solved from the guess (or from the confirmed start)
         if (!have_start) {
             // ---- what the true starting index can change: the SENSITIVE draws.  Along the guessed solution draw p is tried against
@@ -732,15 +549,15 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
                 int i = cur_i0;
 #pragma unroll
                 for (int u = 0; u < kWpt; ++u) {
-                    const bool live = u < nhave;
+                    const bool live = u < me.nhave;
                     const bool pos = i >= 1;
                     const uint32_t mask = 0xffffffffu >> __clz(i | 1);
-                    const uint32_t v = y[u] & mask;
+                    const uint32_t v = me.y[u] & mask;
                     const bool acc = live && pos && v <= (uint32_t)i;
                     const bool same_oct = i - W >= 1 && __clz(i - W) == __clz(i + W);
                     const bool fixed = same_oct && (v + (uint32_t)W <= (uint32_t)i || v > (uint32_t)(i + W));
                     if (live && !fixed) {
-                        const unsigned long long e = ((unsigned long long)y[u] << 32) | ((unsigned long long)(unsigned)(i & 0x7fffffff) << 1) | (acc ? 1ull : 0ull);
+                        const unsigned long long e = ((unsigned long long)me.y[u] << 32) | ((unsigned long long)(unsigned)(i & 0x7fffffff) << 1) | (acc ? 1ull : 0ull);
                         // i may be <= 0 past the end of the shuffle: kept as a 31-bit two's complement
 #pragma unroll
                         for (int q = 0; q < kWpt / 4; ++q)
@@ -752,8 +569,8 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
             }
             const int e_incl = wave_incl_scan(n_ent);
             if (lane == kWave - 1) s_lo[wave] = e_incl;
-            const bool lane_over = n_ent > kWpt / 4;
-            if (__builtin_amdgcn_ballot_w64(lane_over) != 0ull && lane == 0) s_hi[wave] = 1; else if (lane == 0) s_hi[wave] = 0;
+            const int wave_over = __builtin_amdgcn_ballot_w64(n_ent > kWpt / 4) != 0ull ? 1 : 0;
+            if (lane == 0) s_hi[wave] = wave_over;
             __syncthreads();
             int e_base = 0, e_total = 0, over = 0;
             for (int w = 0; w < kWaves; ++w) {
@@ -850,15 +667,7 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
             const bool fast = s_fast != 0;
             if (i_exact < 1) break;                   // the shuffle ended before this chunk
             if (i_exact != i_start) {
-                cur_i0 = i_exact - (wbase + incl - cnt);
-                if (__builtin_amdgcn_ballot_w64(!still_ok(cur_i0)) == 0ull) {
-                    wchg = false;
-                } else {
-                    const int cnt2 = eval(cur_i0);
-                    wchg = __builtin_amdgcn_ballot_w64(cnt2 != cnt) != 0ull;
-                    cnt = cnt2;
-                    incl = wave_incl_scan(cnt);
-                }
+                restart(i_exact);
                 rounds(i_exact);
             }
             i_start = i_exact;
@@ -875,20 +684,7 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
             if (last || dry) cstore(done_word, pack(1));
         }
         // ---- off the chain: the targets, staged in index order, then stored as whole lines
-        int consumed = kWpt;
-        stage_top = i_start;
-        if (!wave_fast || last) {
-            (void)walk(cur_i0, true, consumed);
-        } else {
-            const uint32_t mask = 0xffffffffu >> __clz(cur_i0 | 1);
-            const uint32_t lo = (uint32_t)(cur_i0 - kWpt);
-            int i = cur_i0;
-#pragma unroll
-            for (int u = 0; u < kWpt; ++u) {
-                const uint32_t v = y[u] & mask;
-                if (v <= lo) s_stage[stage_top - (i--)] = (int32_t)v;
-            }
-        }
+        const int consumed = me.emit(cur_i0, !me.wave_fast || last, s_stage, i_start);
         __syncthreads();
         {
             const int n_out = last ? i_start : total;         // indices i_start .. i_start - n_out + 1
@@ -897,7 +693,7 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
         TST(6);      // targets emitted
         if (last) {
             // words consumed = everything up to and including the draw that filled i = 1 (unique thread)
-            if (cnt > 0 && cur_i0 - cnt == 0) {
+            if (me.cnt > 0 && cur_i0 - me.cnt == 0) {
                 const long long end = cbase + (long long)tid * kWpt + consumed;
                 posv[1] = end;
                 posv[done_slot] = end;
@@ -921,7 +717,6 @@ __global__ __launch_bounds__(kAccThreads) void k_fy_accept3(const uint32_t* __re
         posv[19] = (long long)t_delta; posv[20] = (long long)t_rounds; posv[21] = (long long)t_w;
     }
 #endif
-#undef TST
 }
 
 // Side job: clr[0 .. clr_n) = -1 (clr_n a multiple of 4, 16-B aligned) -- the list heads the NEXT shuffle links into.
@@ -1033,14 +828,11 @@ static double expected_draws(int n) {
 // sticky error flag instead of producing a wrong permutation.
 static double need_words(int n) { return expected_draws(n) + 12.0 * sqrt(2.0 * (double)n) + 2.0 * kMtN; }
 
-// k_mt_fill and k_fy_accept are single-workgroup latency chains that run side by side for most of an update.  The
-// dispatcher is free to put both on the same CU, where the 16 accept waves take four issue slots in five from the
-// twist (rocprof in-situ: k_mt_fill 640 us alone, 850-910 us next to the accept kernel).  Each therefore asks for
-// more than half a CU's LDS (unused), which no two of them can get together.
-#ifndef AURPPO_ACC_WPT
-#define AURPPO_ACC_WPT 8      // draws per thread per accept step (A/B knob)
-#endif
-constexpr int kAccWpt = AURPPO_ACC_WPT;
+// k_mt_fill and the accept stage are latency chains that run side by side for most of an update.  The dispatcher is
+// free to put a fill and an accept workgroup on the same CU, where the 16 accept waves take four issue slots in five from
+// the twist (rocprof in-situ: k_mt_fill 640 us alone, 850-910 us next to the accept kernel).  Each therefore asks for
+// more than half a CU's LDS (k_mt_fill's is unused; k_fy_accept3's holds the chunk's targets), which no two of them can
+// get together.
 #ifndef AURPPO_ACC3_WPT
 #define AURPPO_ACC3_WPT 16    // draws per thread and chunk of the workgroup relay (k_fy_accept3): 16 384 per chunk (32: the kernel spills)
 #endif
@@ -1052,10 +844,6 @@ static hipError_t own_cu_setup() {
     if (done) return hipSuccess;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_mt_fill), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)kOwnCuLds);
-
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fy_accept<1024, kAccWpt>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOwnCuLds);
     if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fy_accept3<1024, kAcc3Wpt>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int32_t) * kAcc3Chunk));
@@ -1063,8 +851,9 @@ static hipError_t own_cu_setup() {
     return e;
 }
 
-// Diagnostic knob AURPPO_K2_ONE_STREAM=1: the twist and the resolves run on the caller's stream too (everything serial) -- used
-// to tell how much of the main stream's slowdown comes from HOW MANY streams are busy rather than from what runs on them.
+// Diagnostic knob AURPPO_K2_ONE_STREAM=1: the twist runs on the caller's stream too (serial with the accepts; link + resolve stay
+// on the post stream) -- used to tell how much of the main stream's slowdown comes from HOW MANY streams are busy rather than from
+// what runs on them.
 static hipStream_t fill_stream_of(aurppo_rng* rng, hipStream_t s) {
     return aurppo_knobs().k2_one_stream == 1 ? s : rng->fill_stream;
 }
@@ -1076,16 +865,22 @@ static long long fill_target(double need) {
     return (long long)(starve > 0 ? need * (double)starve / 100.0 : 2.0 * need);
 }
 
-static int enqueue_fill(aurppo_rng* rng, double need, hipStream_t after, int slot, int cur_slot) {
-    const hipStream_t fs = fill_stream_of(rng, after);
-    // inventory target 2*need: one shuffle may be consuming while the next one's draws are produced
-    AURPPO_HIP_TRY(hipEventRecord(rng->ev_sync, after));
-    AURPPO_HIP_TRY(hipStreamWaitEvent(fs, rng->ev_sync, 0));
+// One twist on stream fs, up to the inventory target 2*need (one shuffle may be consuming while the next one's draws are
+// produced) counted from the cursor in posv[cur_slot].  The caller orders it and records what follows it.
+static int launch_fill(aurppo_rng* rng, hipStream_t fs, double need, int cur_slot) {
     const int nblk_max = (int)(2.0 * need / kMtN) + 2;
     AURPPO_HIP_TRY(own_cu_setup());
     hipLaunchKernelGGL(k_mt_fill, dim3(1), dim3(kFillAll), kOwnCuLds, fs, rng->d_last, rng->d_ring,
                        (long long)rng->ring_cap, rng->d_pos, fill_target(need), nblk_max, cur_slot);
     AURPPO_LAUNCH_CHECK("k_mt_fill");
+    return AURPPO_OK;
+}
+
+static int enqueue_fill(aurppo_rng* rng, double need, hipStream_t after, int slot, int cur_slot) {
+    const hipStream_t fs = fill_stream_of(rng, after);
+    AURPPO_HIP_TRY(hipEventRecord(rng->ev_sync, after));
+    AURPPO_HIP_TRY(hipStreamWaitEvent(fs, rng->ev_sync, 0));
+    if (int rc = launch_fill(rng, fs, need, cur_slot)) return rc;
     AURPPO_HIP_TRY(hipEventRecord(rng->ev_fill[slot], fs));
     return AURPPO_OK;
 }
@@ -1110,17 +905,16 @@ int permute_once(aurppo_rng* rng, const int32_t* in, int32_t* out, int n, hipStr
     }
     AURPPO_HIP_TRY(hipStreamWaitEvent(s, rng->ev_fill[slot], 0));
     AURPPO_HIP_TRY(own_cu_setup());
-    // where link + resolve run: behind the accept on the caller's stream / the fill stream (default), or both on a third
-    // stream of the handle, so that the accept chain and the fill chain carry nothing else
-    hipStream_t ls = rng->use_post ? rng->post_stream : s;
-    if (rng->use_post && rng->seq >= 2)       // this accept overwrites the swap targets shuffle seq-2's resolve read
+    // link + resolve run on a third stream of the handle, so that the accept chain and the fill chain carry nothing else
+    const hipStream_t ps = rng->post_stream;
+    if (rng->seq >= 2)       // this accept overwrites the swap targets shuffle seq-2's resolve read
         AURPPO_HIP_TRY(hipStreamWaitEvent(s, rng->ev_post[slot], 0));
     if (rng->head_clean[h] < n) {
         // first shuffle after a (re)start, or a larger n than the previous call prepared: clear here (rare path)
-        AURPPO_HIP_TRY(hipMemsetAsync(rng->d_head[h], 0xff, sizeof(int32_t) * (size_t)n, ls));
+        AURPPO_HIP_TRY(hipMemsetAsync(rng->d_head[h], 0xff, sizeof(int32_t) * (size_t)n, ps));
         rng->head_clean[h] = n;
     }
-    if (aurppo_knobs().k2_accept == 3) {
+    {
         // G workgroups, one per CU (each asks for more than half a CU's LDS): as many as K7 leaves free beside the twist, and no
         // more than the shuffle has chunks
         int G = aurppo_knobs().k2_accept3_wgs;
@@ -1131,13 +925,11 @@ int permute_once(aurppo_rng* rng, const int32_t* in, int32_t* out, int n, hipStr
         if (rng->acc_gen == 0) rng->acc_gen = 1;     // (0 is what the buffer is cleared to)
         hipLaunchKernelGGL((k_fy_accept3<1024, kAcc3Wpt>), dim3(G), dim3(1024), sizeof(int32_t) * kAcc3Chunk, s, rng->d_ring, (long long)rng->ring_cap,
                            rng->d_j[slot], n, rng->d_pos, 4 + slot, rng->d_relay, rng->relay_cap, rng->acc_gen);
-    } else
-        hipLaunchKernelGGL((k_fy_accept<1024, kAccWpt>), dim3(1), dim3(1024), kOwnCuLds, s, rng->d_ring, (long long)rng->ring_cap,
-                           rng->d_j[slot], n, rng->d_pos, 4 + slot);
+    }
     AURPPO_LAUNCH_CHECK("k_fy_accept");
     AURPPO_HIP_TRY(hipEventRecord(rng->ev_acc[slot], s));
     // the link kernel also clears the heads of the NEXT shuffle (same n assumed; a larger one takes the path above).
-    // Their last reader, the resolve of shuffle seq-2, precedes the fill this shuffle's accept waited for.
+    // Their last reader, the resolve of shuffle seq-2, precedes this link on the post stream.
     const int clr_n = (int)(((size_t)n + kClrChunk - 1) / kClrChunk * kClrChunk);
     rng->head_clean[hn] = n;
     rng->head_clean[h] = 0;      // about to be linked into
@@ -1147,42 +939,32 @@ int permute_once(aurppo_rng* rng, const int32_t* in, int32_t* out, int n, hipStr
     // 256 positions (2048 of them at B = 524 288) cost every K7 launch it overlapped 8-10 us (rocprof,
     // tools/k7_overlap.sh): 2.73 -> 2.68 ms per update with 48.  AURPPO_K2_LINK_WGS overrides (0 = one per 256).
     const int link_wgs = aurppo_knobs().k2_link_wgs;
-    if (rng->use_post) AURPPO_HIP_TRY(hipStreamWaitEvent(ls, rng->ev_acc[slot], 0));
-    hipLaunchKernelGGL(k_fy_link, dim3(link_wgs > 0 && link_wgs < grid ? link_wgs : grid), dim3(256), 0, ls, rng->d_j[slot],
+    AURPPO_HIP_TRY(hipStreamWaitEvent(ps, rng->ev_acc[slot], 0));
+    hipLaunchKernelGGL(k_fy_link, dim3(link_wgs > 0 && link_wgs < grid ? link_wgs : grid), dim3(256), 0, ps, rng->d_j[slot],
                        rng->d_head[h], rng->d_next[slot], n, rng->d_head[hn], clr_n, rng->d_pos);
     AURPPO_LAUNCH_CHECK("k_fy_link");
-    AURPPO_HIP_TRY(hipEventRecord(rng->ev_link[slot], ls));
-    // Fill stream, in this order: the NEXT shuffle's draws (assumed the same size; ordered after the PREVIOUS accept,
-    // ev_acc of the other slot, so the cursor it reads is at most one shuffle stale -- what the 2*need target
-    // covers), then THIS shuffle's resolve.  The caller's stream is then free for the next accept while the resolve
-    // runs: per shuffle the two streams carry {accept, link} and {fill, resolve} instead of {accept, memset, link,
-    // resolve} and {fill}.
+    // Fill stream: the NEXT shuffle's draws (assumed the same size; ordered after the PREVIOUS accept, ev_acc of the other
+    // slot, so the cursor it reads is at most one shuffle stale -- what the 2*need target covers).  The caller's stream is
+    // free for the next accept meanwhile: per shuffle the three streams carry {accept}, {fill} and {link, resolve}.
     if (rng->seq > 0) AURPPO_HIP_TRY(hipStreamWaitEvent(fs, rng->ev_acc[slot ^ 1], 0));
-    {
-        const int nblk_max = (int)(2.0 * need / kMtN) + 2;
-        hipLaunchKernelGGL(k_mt_fill, dim3(1), dim3(kFillAll), kOwnCuLds, fs, rng->d_last, rng->d_ring,
-                           (long long)rng->ring_cap, rng->d_pos, fill_target(need), nblk_max,
-                           rng->seq > 0 ? 4 + (slot ^ 1) : 1);   // cursor after the PREVIOUS shuffle (done: waited above)
-        AURPPO_LAUNCH_CHECK("k_mt_fill");
-        AURPPO_HIP_TRY(hipEventRecord(rng->ev_fill[slot ^ 1], fs));
-    }
-    hipStream_t rs = rng->use_post ? rng->post_stream : fs;
-    if (!rng->use_post) AURPPO_HIP_TRY(hipStreamWaitEvent(rs, rng->ev_link[slot], 0));
+    // cursor after the PREVIOUS shuffle (done: waited above)
+    if (int rc = launch_fill(rng, fs, need, rng->seq > 0 ? 4 + (slot ^ 1) : 1)) return rc;
+    AURPPO_HIP_TRY(hipEventRecord(rng->ev_fill[slot ^ 1], fs));
     // default 256 workgroups striding over the positions (0 = one per 256 positions, 2048 of them at B = 524 288).
     // Round 1 had no slack on the shuffle streams to pay for a slower resolve; with 0.5 ms of it (round 2) a bounded
     // grid is affordable: 64 / 128 / 192 / 256 / 512 workgroups -> main stream +17 % (shuffle-bound) / -1.2 % (slack 0)
     // / -0.9 % (slack 0.17 ms) / -0.6 % (0.28 ms) / -0.6 % (0.37 ms), alternating runs on one box.
     const int resolve_wgs = aurppo_knobs().k2_resolve_wgs;
-    hipLaunchKernelGGL(k_fy_resolve, dim3(resolve_wgs > 0 && resolve_wgs < grid ? resolve_wgs : grid), dim3(256), 0, rs,
+    hipLaunchKernelGGL(k_fy_resolve, dim3(resolve_wgs > 0 && resolve_wgs < grid ? resolve_wgs : grid), dim3(256), 0, ps,
                        rng->d_j[slot], rng->d_head[h], rng->d_next[slot], in, out, n, rng->d_pos);
     AURPPO_LAUNCH_CHECK("k_fy_resolve");
-    AURPPO_HIP_TRY(hipEventRecord(rng->ev_res, rs));
-    if (rng->use_post) AURPPO_HIP_TRY(hipEventRecord(rng->ev_post[slot], rs));
+    AURPPO_HIP_TRY(hipEventRecord(rng->ev_res, ps));
+    AURPPO_HIP_TRY(hipEventRecord(rng->ev_post[slot], ps));
     rng->seq += 1;
     return AURPPO_OK;
 }
 
-// The caller's stream sees the permutations only after the last resolve (which ran on the fill stream).
+// The caller's stream sees the permutations only after the last resolve (which ran on the post stream).
 static int join_resolves(aurppo_rng* rng, hipStream_t s) {
     AURPPO_HIP_TRY(hipStreamWaitEvent(s, rng->ev_res, 0));
     return AURPPO_OK;
@@ -1235,12 +1017,10 @@ extern "C" int aurppo_mt19937_create(aurppo_rng** out, uint32_t seed, int max_n,
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         e = hipStreamCreateWithPriority(&r->fill_stream, hipStreamNonBlocking, hi);
         if (e == hipSuccess) e = hipStreamCreateWithPriority(&r->post_stream, hipStreamNonBlocking, hi);
-        r->use_post = aurppo_knobs().k2_post_stream == 1 ? 1 : 0;
     }
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
         e = hipEventCreateWithFlags(&r->ev_fill[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_acc[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_link[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_post[k], hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r->ev_res, hipEventDisableTiming);
@@ -1273,7 +1053,6 @@ extern "C" int aurppo_mt19937_destroy(aurppo_rng* rng) {
     for (int k = 0; k < 2; ++k) {
         if (rng->ev_fill[k]) (void)hipEventDestroy(rng->ev_fill[k]);
         if (rng->ev_acc[k]) (void)hipEventDestroy(rng->ev_acc[k]);
-        if (rng->ev_link[k]) (void)hipEventDestroy(rng->ev_link[k]);
         if (rng->ev_post[k]) (void)hipEventDestroy(rng->ev_post[k]);
     }
     if (rng->ev_res) (void)hipEventDestroy(rng->ev_res);

@@ -158,20 +158,21 @@ def test_shuffle_inplace_matches_numpy_any_seed(H, seed, n):
     assert pos == st[2]
 
 
-@pytest.mark.parametrize("accept,wgs", [("1", "6"), ("3", "1"), ("3", "2"), ("3", "6"), ("3", "8")])
-def test_shuffle_every_accept_kernel_matches_numpy(H, accept, wgs, monkeypatch):
-    """The two builds of the accept stage (k_fy_accept: one workgroup, rounds; k_fy_accept3: relay between workgroups, the default) and the relay's widths, over sizes from below one 16 384-draw chunk to dozens of them, the stream carried
-    across consecutive shuffles: permutations and the generator state afterwards equal numpy's."""
-    monkeypatch.setenv("AURPPO_K2_ACCEPT", accept)
+@pytest.mark.parametrize("wgs", ["1", "2", "6", "8"])
+def test_shuffle_every_relay_width_matches_numpy(H, wgs, monkeypatch):
+    """The accept stage (k_fy_accept3: a relay between workgroups) at several relay widths -- one workgroup, which never waits for
+    another, up to more than the default six --, over sizes from a shuffle that is all tail and below one 16 384-draw chunk to
+    dozens of chunks, the stream carried across consecutive shuffles: permutations and the generator state afterwards equal
+    numpy's.  At n = 2^k + 1 the first index is exactly a power of two, so the very first lanes' windows straddle a mask octave."""
     monkeypatch.setenv("AURPPO_K2_ACCEPT3_WGS", wgs)
-    for n in (2, 11, 1000, 11500, 12000, 23500, 40000, 70000, 300000, 524288):
+    for n in (2, 3, 11, 1000, 4097, 11500, 12000, 16385, 23500, 40000, 65537, 70000, 300000, 524288):
         rs = np.random.RandomState(7)
         rng = H.MT19937(7, n)
         got = rng.shuffle_epochs(n, 3).cpu().numpy()
         idx = np.arange(n)
         for e in range(3):
             rs.shuffle(idx)
-            np.testing.assert_array_equal(got[e], idx, err_msg=f"accept {accept}, {wgs} workgroups, n={n}, shuffle {e}")
+            np.testing.assert_array_equal(got[e], idx, err_msg=f"{wgs} workgroups, n={n}, shuffle {e}")
         key, pos = rng.get_state()
         st = rs.get_state()
         np.testing.assert_array_equal(key, st[1])
@@ -181,13 +182,13 @@ def test_shuffle_every_accept_kernel_matches_numpy(H, accept, wgs, monkeypatch):
         assert float(status) == 0.0
 
 
-@pytest.mark.parametrize("accept", ["1", "3"])
-def test_shuffle_that_runs_out_of_draws_raises_the_sticky_flag_and_reseeding_recovers(H, accept, monkeypatch):
+@pytest.mark.parametrize("wgs", ["1", "6"])
+def test_shuffle_that_runs_out_of_draws_raises_the_sticky_flag_and_reseeding_recovers(H, wgs, monkeypatch):
     """np.random.shuffle cannot fail; the device twin works from pre-generated draws (expectation + 12 sigma) and says so if a
-    shuffle ever needs more: every accept kernel must then stop (no hang: the relay's workgroups leave on the `done` word), raise
-    the flag aurppo_mt19937_status_f32 reports, and a reseed must clear it.  AURPPO_TEST_K2_STARVE makes the twist keep 60 % of
-    one shuffle's draws in stock."""
-    monkeypatch.setenv("AURPPO_K2_ACCEPT", accept)
+    shuffle ever needs more: the accept kernel must then stop -- a lone workgroup (width 1) without any cross-workgroup wait, the
+    default relay with its workgroups leaving on the `done` word: no hang --, raise the flag aurppo_mt19937_status_f32 reports,
+    and a reseed must clear it.  AURPPO_TEST_K2_STARVE makes the twist keep 60 % of one shuffle's draws in stock."""
+    monkeypatch.setenv("AURPPO_K2_ACCEPT3_WGS", wgs)
     n = 200000
     monkeypatch.setenv("AURPPO_TEST_K2_STARVE", "60")
     rng = H.MT19937(3, n)

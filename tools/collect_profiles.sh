@@ -60,9 +60,9 @@ for v in 3 2; do AURPPO_K7_VARIANT=$v run 300 python3 $R/tools/mlp_stamps.py > $
 : > $O/k7_time.txt
 for m in 131072 16384; do for v in 3 2; do K7_M=$m AURPPO_K7_VARIANT=$v run 300 python3 $R/tools/k7_time.py > $O/.step.txt 2>&1; tail -1 $O/.step.txt >> $O/k7_time.txt; done; done
 : > $O/k2_time.txt
-for a in 3 1; do AURPPO_K2_ACCEPT=$a run 300 python3 $R/tools/k2_time.py > $O/.step.txt 2>&1; tail -1 $O/.step.txt >> $O/k2_time.txt; done
+run 300 python3 $R/tools/k2_time.py > $O/.step.txt 2>&1; tail -1 $O/.step.txt >> $O/k2_time.txt
 : > $O/k2_stamps.txt
-for a in 3 1; do AURPPO_K2_ACCEPT=$a run 300 python3 $R/tools/accept_stamps.py > $O/.step.txt 2>&1; tail -10 $O/.step.txt >> $O/k2_stamps.txt; done
+run 300 python3 $R/tools/accept_stamps.py > $O/.step.txt 2>&1; tail -10 $O/.step.txt >> $O/k2_stamps.txt
 K7_M=16384 AURPPO_K7_VARIANT=3 run 300 python3 $R/tools/mlp_stamps.py > $O/.step.txt 2>&1; tail -20 $O/.step.txt > $O/k7_stamps_v3_M16384.txt
 rm -f $O/.step.txt
 cd /tmp

@@ -1,4 +1,4 @@
-"""Stress: the shuffle pipeline (default accept kernel, random relay widths) against numpy over random sizes and seeds, several
+"""Stress: the shuffle pipeline (random relay widths) against numpy over random sizes and seeds, several
 shuffles per handle so the stream carries over -- looks for the rare paths of k_fy_accept3 (a true index outside the window, a list
 that overflows, octave edges on chunk boundaries, the tail octaves) and for hangs (run it under `timeout`)."""
 import os, sys, random

@@ -1,5 +1,5 @@
 """Stand-alone time of the E = 4 epoch shuffles of one update (B = 524 288) and bit-exactness against numpy;
-AURPPO_K2_ACCEPT=1|2|3 selects the accept kernel (default 3)."""
+AURPPO_K2_ACCEPT3_WGS sets the accept relay's width (default 6), AURPPO_LIB loads another build of the library."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,4 +25,4 @@ for _ in range(12):
     rng.shuffle_epochs(B, E, out=out)
     torch.cuda.synchronize()
     ts.append((time.perf_counter() - t0) * 1e3)
-print(f"accept kernel {os.environ.get('AURPPO_K2_ACCEPT', 'default')}: bit-exact vs numpy: {ok}; {E} shuffles of {B}: median {np.median(ts[2:]):.3f} ms (min {min(ts[2:]):.3f})")
+print(f"accept relay of {os.environ.get('AURPPO_K2_ACCEPT3_WGS', '6')} workgroups: bit-exact vs numpy: {ok}; {E} shuffles of {B}: median {np.median(ts[2:]):.3f} ms (min {min(ts[2:]):.3f})")
