@@ -24,6 +24,8 @@ SYMBOLS = (
     "aurppo_head_ppo_workspace_bytes", "aurppo_head_ppo_f32",
     "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_prep_f32", "aurppo_mlp_layered_act_workspace_bytes", "aurppo_mlp_layered_act_f32",
     "aurppo_head_act_f32",
+    "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_linear_wgrad_bias_f32", "aurppo_mlp_layered_step_workspace_bytes",
+    "aurppo_mlp_layered_step_f32", "aurppo_mlp_layered_minibatch_f32",
 )
 
 _lib = None
@@ -116,6 +118,12 @@ def _declare(lib):
     lib.aurppo_mlp_layered_act_workspace_bytes.argtypes = [i32, i32]
     lib.aurppo_mlp_layered_act_f32.argtypes = [vp, vp] + [i32] * 6 + [vp, pi32, i32, vp, vp, vp, vp] + ws_stream
     lib.aurppo_head_act_f32.argtypes = [vp, vp, vp] + [i32] * 4 + [vp, pi32, i32, vp, vp, vp, vp]
+    # the layered update step
+    lib.aurppo_linear_wgrad_bias_ws_bytes.argtypes = [C.c_longlong, i32, i32]
+    lib.aurppo_linear_wgrad_bias_f32.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32] + ws_stream
+    lib.aurppo_mlp_layered_step_workspace_bytes.argtypes = [i32] * 5
+    lib.aurppo_mlp_layered_step_f32.argtypes = step_prefix(2) + ws_stream
+    lib.aurppo_mlp_layered_minibatch_f32.argtypes = step_prefix(2) + adam_tail + ws_stream
     lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
     lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
     # the one-shot exchange
@@ -145,6 +153,7 @@ def _declare(lib):
     # everything returns int except the error string and the size_t workspace plans
     sized = ("aurppo_loss_workspace_bytes", "aurppo_clip_workspace_bytes", "aurppo_mlp_workspace_bytes", "aurppo_conv3x3_wop_bytes",
              "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
-             "aurppo_head_ppo_workspace_bytes", "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_act_workspace_bytes")
+             "aurppo_head_ppo_workspace_bytes", "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_act_workspace_bytes",
+             "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes")
     for name in SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

@@ -340,6 +340,7 @@ struct WgradArgs {
     long long M;
     int N, K, rows_per_slice, n_tiles_n, n_tiles_k;
     const int32_t* rows;             // ROWS builds: (M,) row m of the product reads x row rows[m]; dy stays in minibatch order
+    double* bpart;                   // BIAS builds: (S, N) the slices' column sums of dy, behind `part` (the other builds never read it)
 };
 
 // KTAIL (k_linear_wgrad_tail: K is no multiple of 4 -- layer 0's weight gradient at a ragged state width): an X row is K floats
@@ -347,10 +348,22 @@ struct WgradArgs {
 // are staged as a selected 0 (and the stores to `part` leave them out, as they always did).
 template <bool ROWS = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
-    constexpr bool KTAIL = false;
+    constexpr bool KTAIL = false, BIAS = false;
 #include "linear_wgrad_body.h"
 }
 template <bool ROWS>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const WgradArgs a) {
+    constexpr bool KTAIL = true, BIAS = false;
+#include "linear_wgrad_body.h"
+}
+// The builds that also leave the layer's bias gradient, the column sums of dy (linear_wgrad_body.h).  They are overloads with a
+// second template parameter, not a defaulted one on the templates above: those keep their symbols and their instruction streams.
+template <bool ROWS, bool BIAS>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
+    constexpr bool KTAIL = false;
+#include "linear_wgrad_body.h"
+}
+template <bool ROWS, bool BIAS>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const WgradArgs a) {
     constexpr bool KTAIL = true;
 #include "linear_wgrad_body.h"
@@ -592,10 +605,8 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3_wgrad(const ConvWgr
         }
 }
 
-// out[i] = part[0][i] + part[1][i] + ... in slice order; with `cols` > 0 also colsum[j] = the same sum over a (S, cols) array
-__global__ __launch_bounds__(256) void k_fold_slices(const float* __restrict__ part, int S, long long n, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+// part[0][i] + part[1][i] + ... in slice order
+__device__ __forceinline__ float fold_slices_at(const float* __restrict__ part, int S, long long n, long long i) {
     float t = 0.0f;
     int sl = 0;
     for (; sl + 8 <= S; sl += 8) {
@@ -606,7 +617,29 @@ __global__ __launch_bounds__(256) void k_fold_slices(const float* __restrict__ p
         for (int k = 0; k < 8; ++k) t += x[k];
     }
     for (; sl < S; ++sl) t += part[(size_t)sl * n + i];
-    out[i] = t;
+    return t;
+}
+__global__ __launch_bounds__(256) void k_fold_slices(const float* __restrict__ part, int S, long long n, float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fold_slices_at(part, S, n, i);
+}
+// k_fold_slices with the BIAS builds' partial column sums behind it: the workgroups past the last of the fold add bpart (S, N) in
+// slice order, still in fp64, and round once into db (N,).
+__global__ __launch_bounds__(256) void k_fold_slices_bias(const float* __restrict__ part, int S, long long n, float* __restrict__ out,
+                                                          const double* __restrict__ bpart, int N, float* __restrict__ db) {
+    const long long n_fold = (n + 255) / 256;
+    if ((long long)blockIdx.x >= n_fold) {
+        const long long j = ((long long)blockIdx.x - n_fold) * 256 + threadIdx.x;
+        if (j >= N) return;
+        double t = 0.0;
+        for (int sl = 0; sl < S; ++sl) t += bpart[(size_t)sl * N + j];
+        db[j] = (float)t;
+        return;
+    }
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fold_slices_at(part, S, n, i);
 }
 
 }  // namespace
@@ -845,14 +878,11 @@ extern "C" size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     return (size_t)linear_wgrad_slices(M, N, K) * (size_t)N * (size_t)K * sizeof(float) + 64;
 }
-// dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N a multiple of 4, any K >= 1 -- no multiple of 4:
-// the tail builds; 16-byte aligned operands)
-extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream) {
-    return aurppo_linear_wgrad_rows_f32(dy, x, nullptr, dw, M, N, K, ws, stream);
-}
-// the same with row m of the product reading x row rows[m] (rows == NULL: the plain call); same slice rule, same workspace
-extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K,
-                                            void* ws, void* stream) {
+// bytes of the (S, N, K) partial products, rounded to where the BIAS builds' (S, N) fp64 partial column sums begin
+static size_t linear_wgrad_part_bytes(int S, int N, int K) { return ((size_t)S * (size_t)N * (size_t)K * sizeof(float) + 15) & ~(size_t)15; }
+// The weight-gradient launches; db != nullptr: the BIAS builds and their fold (rows or K a multiple of 4: no plain BIAS tail build)
+static int linear_wgrad_impl(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N, int K,
+                             void* ws, void* stream) {
     AURPPO_REQUIRE(dy && x && dw && ws, AURPPO_EINVAL, "aurppo_linear_wgrad_f32: null pointer");
     AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: M=%lld N=%d (a multiple of 4) K=%d", M, N, K);
     AURPPO_REQUIRE(aligned_to(dy, 16) && aligned_to(x, 16) && aligned_to(ws, 16), AURPPO_EINVAL,
@@ -860,6 +890,7 @@ extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, con
     const int S0 = linear_wgrad_slices(M, N, K);
     WgradArgs a;
     a.dy = dy; a.x = x; a.part = reinterpret_cast<float*>(ws); a.M = M; a.N = N; a.K = K; a.rows = rows;
+    a.bpart = db ? reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + linear_wgrad_part_bytes(S0, N, K)) : nullptr;
     const long long rps = ((M + S0 - 1) / S0 + 31) / 32 * 32;           // whole 32-row chunks per slice
     const long long S = (M + rps - 1) / rps;
     AURPPO_REQUIRE(S >= 1 && S <= S0 && rps < (1ll << 30), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: slice size");
@@ -869,16 +900,45 @@ extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, con
     const long long grid = (long long)a.n_tiles_n * a.n_tiles_k * S;
     AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (K % 4 != 0) {
-        if (rows) hipLaunchKernelGGL(k_linear_wgrad_tail<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
-        else hipLaunchKernelGGL(k_linear_wgrad_tail<false>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
-    } else if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
-    else hipLaunchKernelGGL(k_linear_wgrad<false>, dim3((unsigned)grid), dim3(kConvThreads), 0, st, a);
+    const dim3 g((unsigned)grid), blk(kConvThreads);
+    if (db) {
+        if (K % 4 != 0) hipLaunchKernelGGL((k_linear_wgrad_tail<true, true>), g, blk, 0, st, a);
+        else if (rows) hipLaunchKernelGGL((k_linear_wgrad<true, true>), g, blk, 0, st, a);
+        else hipLaunchKernelGGL((k_linear_wgrad<false, true>), g, blk, 0, st, a);
+    } else if (K % 4 != 0) {
+        if (rows) hipLaunchKernelGGL(k_linear_wgrad_tail<true>, g, blk, 0, st, a);
+        else hipLaunchKernelGGL(k_linear_wgrad_tail<false>, g, blk, 0, st, a);
+    } else if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, g, blk, 0, st, a);
+    else hipLaunchKernelGGL(k_linear_wgrad<false>, g, blk, 0, st, a);
     AURPPO_LAUNCH_CHECK("k_linear_wgrad");
-    const long long n = (long long)N * K;
-    hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, (int)S, n, dw);
+    const long long n = (long long)N * K, n_fold = (n + 255) / 256;
+    if (db) hipLaunchKernelGGL(k_fold_slices_bias, dim3((unsigned)(n_fold + (N + 255) / 256)), dim3(256), 0, st, a.part, (int)S, n, dw, a.bpart, N, db);
+    else hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)n_fold), dim3(256), 0, st, a.part, (int)S, n, dw);
     AURPPO_LAUNCH_CHECK("k_fold_slices");
     return AURPPO_OK;
+}
+// dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N a multiple of 4, any K >= 1 -- no multiple of 4:
+// the tail builds; 16-byte aligned operands)
+extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream) {
+    return linear_wgrad_impl(dy, x, nullptr, dw, nullptr, M, N, K, ws, stream);
+}
+// the same with row m of the product reading x row rows[m] (rows == NULL: the plain call); same slice rule, same workspace
+extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K,
+                                            void* ws, void* stream) {
+    return linear_wgrad_impl(dy, x, rows, dw, nullptr, M, N, K, ws, stream);
+}
+// ... and with the layer's bias gradient db (N,) = the column sums of dy, taken in the product's kernel: the slices' partial sums
+// (fp64) lie behind the partial products in the workspace
+extern "C" size_t aurppo_linear_wgrad_bias_ws_bytes(long long M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    const int S = linear_wgrad_slices(M, N, K);
+    return linear_wgrad_part_bytes(S, N, K) + (size_t)S * (size_t)N * sizeof(double) + 64;
+}
+extern "C" int aurppo_linear_wgrad_bias_f32(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N,
+                                            int K, void* ws, void* stream) {
+    AURPPO_REQUIRE(db && aligned_to(db, 4), AURPPO_EINVAL, "aurppo_linear_wgrad_bias_f32: db null or not 4-byte aligned");
+    AURPPO_REQUIRE(rows || K % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_bias_f32: K=%d (a multiple of 4 without rows)", K);
+    return linear_wgrad_impl(dy, x, rows, dw, db, M, N, K, ws, stream);
 }
 
 // K12: dw (Co, Ci, 3, 3) = the gradient of conv2d(x (B, Ci, H, W), w, padding = pad) with respect to w, given the output gradient

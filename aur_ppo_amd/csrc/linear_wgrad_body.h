@@ -1,5 +1,7 @@
-// The body of k_linear_wgrad and k_linear_wgrad_tail (conv.hip), included INSIDE each of the two kernel templates: ROWS and KTAIL are
-// compile-time constants of the including kernel, `a` its WgradArgs (see linear_body.h for why it is a text and not a function).
+// The body of k_linear_wgrad and k_linear_wgrad_tail (conv.hip), included INSIDE each of the kernel templates: ROWS, KTAIL and BIAS
+// are compile-time constants of the including kernel, `a` its WgradArgs (see linear_body.h for why it is a text and not a function).
+// BIAS: the workgroups of k-tile 0 also sum the dY pieces they fetch anyway over the slice's rows, per column, in fp64 (a thread's
+// rows in ascending order, then the eight row groups in order), and leave one partial vector of N doubles per slice in a.bpart.
     __shared__ __attribute__((aligned(16))) char s_img[2 * 2 * 3 * kXPlane];      // [dY | X][64-column half][3 planes][32 rows x 128 B]
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -21,6 +23,8 @@
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
     float pa[4][4], pb[4][4];
+    [[maybe_unused]] double bs[4] = {0.0, 0.0, 0.0, 0.0};   // BIAS: this thread's column sums of dY columns n0 + c4 .. + 3
+    [[maybe_unused]] const bool bias_wg = BIAS && k0 == 0;
     unsigned pok = 0u;               // bit u: dY piece u is real; bit 4 + u: X piece u (the zeroing waits until the chunk is staged)
     auto fetch = [&](long long m0) {
         pok = 0u;
@@ -52,6 +56,12 @@
         for (int u = 0; u < 4; ++u) {
             const int r = r_of + 8 * u;
             const bool oka = (pok >> u) & 1u, okb = (pok >> (4 + u)) & 1u;
+            if constexpr (BIAS) {
+                if (bias_wg && oka) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) bs[j] += (double)pa[u][j];
+                }
+            }
             store_x4(imgA + (c4 >> 6) * 3 * kXPlane, r, c4 & 63, oka ? pa[u][0] : 0.0f, oka ? pa[u][1] : 0.0f, oka ? pa[u][2] : 0.0f,
                      oka ? pa[u][3] : 0.0f);
             store_x4(imgB + (c4 >> 6) * 3 * kXPlane, r, c4 & 63, okb ? pb[u][0] : 0.0f, okb ? pb[u][1] : 0.0f, okb ? pb[u][2] : 0.0f,
@@ -82,3 +92,19 @@
                 if (row < a.N && col < a.K) out[(size_t)row * a.K + col] = acc[i][j][e];
             }
         }
+    if constexpr (BIAS) {
+        // the eight row groups' sums of a column meet in LDS (the images are done with) and thread n < 128 adds them in group order
+        double* const s_bs = reinterpret_cast<double*>(s_img);           // [8 row groups][128 columns]
+        __syncthreads();                                    // the last chunk's fragments have been read
+        if (bias_wg) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_bs[r_of * 128 + c4 + j] = bs[j];
+        }
+        __syncthreads();
+        if (bias_wg && tid < 128 && n0 + tid < a.N) {
+            double t = 0.0;
+#pragma unroll
+            for (int g = 0; g < 8; ++g) t += s_bs[g * 128 + tid];
+            a.bpart[(size_t)s * a.N + n0 + tid] = t;
+        }
+    }

@@ -992,6 +992,24 @@ def linear_wgrad_rows(gy, x, rows):
     return _linear_wgrad(gy, x, rows)
 
 
+def linear_wgrad_bias(gy, x, rows=None):
+    """``(gy.T @ x, gy.sum(0))`` (``x[rows]`` with an index) -- a layer's weight and bias gradient -- from one pass over ``gy``:
+    k_linear_wgrad's BIAS builds sum the ``gy`` pieces they stage, in fp64, rounded once.  ``dw`` is ``linear_wgrad``'s bit for bit.
+    Without ``rows`` the width of ``x`` must be a multiple of 4."""
+    lib = _lib_or_raise()
+    gy, x = gy.contiguous(), x.contiguous()
+    M, N = gy.shape
+    K = x.shape[1]
+    if rows is not None and rows.numel() != M:
+        raise ValueError("linear_wgrad_bias: one index per row of gy")
+    ws = _workspace("wgrad", lib.aurppo_linear_wgrad_bias_ws_bytes(M, N, K), x.device)
+    dw = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    db = torch.empty(N, dtype=torch.float32, device=x.device)
+    _check(lib.aurppo_linear_wgrad_bias_f32(_ptr(gy), _ptr(x), _optr(rows, torch.int32), _ptr(dw), _ptr(db), M, N, K, *_ws_stream(ws)),
+           "aurppo_linear_wgrad_bias_f32")
+    return dw, db
+
+
 def linear_dx_tanh(gz, w, h, out=None):
     """``(gz @ w) * (1 - h * h)``: a hidden layer's input gradient with tanh' of the layer below in the product's epilogue.
     ``out`` may be ``h``."""
@@ -1101,6 +1119,48 @@ def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip
                    "aurppo_linear_dx_tanh_f32")
             torch.sum(h[l - 1], 0, out=flat_grad[o[2 * l - 1]:o[2 * l - 1] + Hd])
         _check(lib.aurppo_linear_wgrad_rows_f32(_ptr(h[0]), obs_p, idx_p, at(g0, o[0]), M, Hd, D, wgw, st), "aurppo_linear_wgrad_rows_f32")
+    return out_scalars
+
+
+def _layered_native(lib, who, obs, actions, rec, idx, flat_param, layout, *buckets):
+    """The checks and the three argument runs the two native layered calls share: layout array, shape, workspace."""
+    if not layout.get("layered") or not _mlp_buffers_ok(obs, actions, rec, layout):
+        raise ValueError(f"{who}: buffer shapes do not match the policy")
+    _bucket_fits(layout["n_params"], flat_param, *buckets, who=who)
+    lay, shape = _layout_shape(layout, idx.numel())
+    nb = lib.aurppo_mlp_layered_step_workspace_bytes(shape[0], layout["D"], layout["A"], layout["hidden"], layout["num_layers"])
+    if nb == 0:
+        raise RuntimeError(f"aur_ppo_amd: {who} does not take this shape")
+    return lay, shape, _workspace("layered_step", nb, obs.device)
+
+
+def mlp_layered_step_native(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv=True,
+                            vloss_mode=VLOSS_CLIPPED, out_scalars=None):
+    """``mlp_layered_step`` as one native call (aurppo_mlp_layered_step_f32): the same products and K13 in the same order from one
+    workspace, and the lower layers' bias gradients out of the weight-gradient kernel (fp64 sums, rounded once) instead of a column
+    sum per layer.  Everything but those bias gradients is ``mlp_layered_step``'s bit for bit."""
+    lib = _lib_or_raise()
+    lay, shape, ws = _layered_native(lib, "mlp_layered_step_native", obs, actions, rec, idx, flat_param, layout, flat_grad)
+    if out_scalars is None:
+        out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=obs.device)
+    _check(lib.aurppo_mlp_layered_step_f32(
+        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
+                      vloss_mode, out_scalars), *_ws_stream(ws)), "aurppo_mlp_layered_step_f32")
+    return out_scalars
+
+
+def mlp_layered_minibatch(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv, vloss_mode,
+                          out_scalars, exp_avg, exp_avg_sq, lr_dev, step_dev, max_norm, betas, eps, out_norm):
+    """``mlp_layered_step_native`` + ``clip_grad_norm_`` + ``Adam.step`` over ``[0, n_params)`` in one native call
+    (aurppo_mlp_layered_minibatch_f32): one whole minibatch (src/ppo.py:219-269) of a layered policy.  Single process only."""
+    lib = _lib_or_raise()
+    lay, shape, ws = _layered_native(lib, "mlp_layered_minibatch", obs, actions, rec, idx, flat_param, layout, flat_grad, exp_avg,
+                                     exp_avg_sq)
+    _check(lib.aurppo_mlp_layered_minibatch_f32(
+        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
+                      vloss_mode, out_scalars),
+        *_adam_tail(exp_avg, exp_avg_sq, max_norm, lr_dev, step_dev, betas, eps, out_norm), *_ws_stream(ws)),
+        "aurppo_mlp_layered_minibatch_f32")
     return out_scalars
 
 

@@ -60,6 +60,7 @@ class torch_buffer:
 
 LAYERED_STEP_DEFAULT = "0"      # AURPPO_LAYERED_STEP when the environment does not set it
 LAYERED_ACT_DEFAULT = "0"       # AURPPO_LAYERED_ACT when the environment does not set it
+LAYERED_NATIVE_DEFAULT = "0"    # AURPPO_LAYERED_NATIVE when the environment does not set it
 
 
 class ppo(FlatAdamMixin):
@@ -153,6 +154,11 @@ class ppo(FlatAdamMixin):
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_layout")
                 and os.environ.get("AURPPO_LAYERED_STEP", LAYERED_STEP_DEFAULT) != "0"):
             self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
+        # AURPPO_LAYERED_NATIVE=1 (opt-in, read only where the layered update is on): the step as one native call
+        # (ops.mlp_layered_step_native), and with a single process, fused Adam and a bucket that holds exactly the policy, clip + Adam
+        # behind it in the same call (ops.mlp_layered_minibatch)
+        self._layered_native = (self._mlp_layered is not None
+                                and os.environ.get("AURPPO_LAYERED_NATIVE", LAYERED_NATIVE_DEFAULT) != "0")
         # The same policies' rollout step and bootstrap: k_linear from operand copies prepared once per rollout + K14
         # (ops.mlp_layered_act) in place of policy.evaluate / policy.value.  Opt-in (AURPPO_LAYERED_ACT=1), independent of the
         # update's switch above; ``_mlp`` stays None.
@@ -458,7 +464,7 @@ class ppo(FlatAdamMixin):
         return self.buffer.actions.reshape((-1,) + self.buffer.action_shape), self._rec
 
     def _update_route(self, packed):
-        """Which of the six ways one minibatch is stepped; decided once per update."""
+        """Which of the eight ways one minibatch is stepped; decided once per update."""
         ops = self.ops
         # single process, MLP policy, fused Adam over exactly the policy's bucket: K7 + clip + Adam chained, three
         # launches per minibatch (each call also prepares the statistics of the slice that follows it)
@@ -472,6 +478,13 @@ class ppo(FlatAdamMixin):
             return "halves_p2p" if self._p2p is not None else "halves_allreduce"
         if packed and self._mlp is not None:
             return "fused_step"         # one fused launch: rows are read through the permutation, gradients land in the bucket
+        if packed and self._mlp_layered is not None and self._layered_native:
+            # the native layered step; clip + Adam ride in the same call where nothing has to happen between the two
+            if (not self._dp and self._fused_adam and self.bucket.numel == self._mlp_layered["n_params"]
+                    and hasattr(ops, "mlp_layered_minibatch")):
+                return "layered_minibatch"
+            if hasattr(ops, "mlp_layered_step_native"):
+                return "layered_native_step"
         if packed and self._mlp_layered is not None:
             return "layered_step"       # rows through the permutation in the first product, the loss behind the last one
         return "autograd"
@@ -496,12 +509,13 @@ class ppo(FlatAdamMixin):
         route = self._update_route(packed)
         # what a fused step takes before its index slice (head), and between the slice and its row of scalars (mid)
         k7_act, k7_rec = self._step_pair()
-        layout = self._mlp_layered if route == "layered_step" else self._mlp
+        layout = self._mlp_layered if route.startswith("layered_") else self._mlp
         head = (b_obs, k7_act, k7_rec)
         mid = (bk.flat_param, layout, bk.flat_grad, self.clip_coeff, self.entropy_coeff, self.value_coeff, self.norm_adv, vmode)
-        if route in ("fused_step", "layered_step"):
-            step_fn = ops.mlp_ppo_step if route == "fused_step" else ops.mlp_layered_step
-        if route in ("chained", "halves_allreduce", "halves_p2p"):
+        if route in ("fused_step", "layered_step", "layered_native_step"):
+            step_fn = (ops.mlp_ppo_step if route == "fused_step" else ops.mlp_layered_step if route == "layered_step"
+                       else ops.mlp_layered_step_native)
+        if route in ("chained", "halves_allreduce", "halves_p2p", "layered_minibatch"):
             g = self.optimizer.param_groups[0]
             adam = (self._lr_tensor, self._adam_t, self.max_grad_norm, g["betas"], g["eps"])
 
@@ -537,7 +551,9 @@ class ppo(FlatAdamMixin):
                         probe_first_grad(self.world)
                         ops.mlp_ppo_apply(bk.flat_param, bk.flat_grad, self._adam_m, self._adam_v, self._mlp, *adam, norm,
                                           grad_scale=1.0 / self.world, rec=k7_rec, next_idx=nxt)
-                elif route in ("fused_step", "layered_step"):
+                elif route == "layered_minibatch":
+                    ops.mlp_layered_minibatch(*head, mb_inds, *mid, sc, self._adam_m, self._adam_v, *adam, norm)
+                elif route in ("fused_step", "layered_step", "layered_native_step"):
                     step_fn(*head, mb_inds, *mid, sc)
                     D.allreduce_mean_(bk.flat_grad, self.world, force=self._dp)
                     probe_first_grad()

@@ -297,6 +297,16 @@ int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t*
                                  void* stream);
 int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const float* h, float* out, long long M, int K_w, int N_w,
                               void* wop_ws, void* stream);
+/* aurppo_linear_wgrad_rows_f32 that also leaves the layer's bias gradient, db (N,) = the column sums of dy (what loss.backward()
+ * leaves in <layer>.bias.grad, src/ppo.py:266), taken from the dy values the product's kernel holds anyway: no second pass over dy.
+ * The sums are accumulated in fp64 -- per thread, across a workgroup's row groups, across the slices in slice order -- and rounded
+ * to fp32 once; no floating-point atomics: two calls give the same bits.  dw is bit for bit aurppo_linear_wgrad_rows_f32's.
+ * Limits and alignment as aurppo_linear_wgrad_rows_f32, except that K no multiple of 4 needs rows (AURPPO_ESHAPE with rows == NULL:
+ * that build does not exist); db needs 4-byte alignment.  ws: aurppo_linear_wgrad_bias_ws_bytes(M, N, K) bytes (the partial products,
+ * then the slices' partial column sums), 16-byte aligned. */
+size_t aurppo_linear_wgrad_bias_ws_bytes(long long M, int N, int K);
+int aurppo_linear_wgrad_bias_f32(const float* dy, const float* x, const int32_t* rows /* may be NULL */, float* dw, float* db,
+                                 long long M, int N, int K, void* ws, void* stream);
 
 /* ---- K13: heads + distribution + PPO loss + their backward for the MLP policies the fused steps do not cover -------------
  * For hidden_dim > 128 (or a state of more than 128 floats) the hidden layers of src/nets/nets.py:19-53 run a layer at a time
@@ -353,6 +363,38 @@ int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int 
 int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
                         const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
                         void* stream);
+
+/* ---- the layered update step: aurppo_mlp_ppo_step_f32's contract for the MLP policies the fused steps do not cover ---------
+ * One minibatch of src/ppo.py:219-266 (gather, policy.evaluate, the loss, loss.backward()) for hidden_dim > 128 or a state of more
+ * than 128 floats, in one call that owns its launch sequence: per net layer 0 through idx and layers 1 .. L - 1
+ * (aurppo_linear_rows_bias_act_f32 / aurppo_linear_bias_act_f32, tanh in the epilogue), K13 (aurppo_head_ppo_f32, in place of the
+ * last activations), then per net from the last layer down the weight gradient and aurppo_linear_dx_tanh_f32.  The weight gradient
+ * of every layer below the last is aurppo_linear_wgrad_bias_f32 (layer 0 through idx), which leaves that layer's bias gradient; K13
+ * writes the last layers'.  12 L - 1 launches on the caller's stream; no allocation, no host synchronisation (capturable into a
+ * hipGraph); no floating-point atomics: two calls give the same bits.
+ *   obs / actions / rec / idx, the loss knobs and out_scalars: as aurppo_mlp_ppo_step_f32 (the three record forms: actions + (B, 4)
+ *     records, Categorical indices + records, or actions == NULL and (B, 16) packed records).  obs and rec 16-byte aligned.
+ *   offsets: the layered layout as aurppo_mlp_layered_act_f32 takes it, 4 * (num_layers + 1) + 1 entries, each range-checked.
+ *   grads: [0, n_params) is overwritten -- every float of it that belongs to the policy -- and nothing past it.
+ *   workspace: aurppo_mlp_layered_step_workspace_bytes(M, D, A, hidden, num_layers) bytes (0: shape not supported), 64-byte aligned,
+ *     caller-owned: the 2 L activation arrays, the operand copy, the weight-gradient slices, K13's workspace and clip + Adam's.  A
+ *     smaller buffer cannot be told from a bare pointer: the size function is the contract.
+ *   aurppo_mlp_layered_minibatch_f32: the step, then aurppo_clip_adam_f32's two launches over [0, n_params) (clip_n = n_params) on
+ *     the same stream -- src/ppo.py:219-269 -- with the same bits in params, moments, step count and norm as the two calls in turn.
+ *     Single process only: nothing all-reduces the gradient in between.
+ * Limits (AURPPO_ESHAPE before any launch otherwise): M >= 1, any D >= 1, hidden a multiple of 32 in 32..1024, A in 1..16
+ * (Categorical 2..16; packed records A <= 12), num_layers 1..16. */
+size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers);
+int aurppo_mlp_layered_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
+                                int continuous, int hidden, int num_layers, const float* params, const int* offsets, int n_params,
+                                float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
+                                float* out_scalars, void* workspace, void* stream);
+int aurppo_mlp_layered_minibatch_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
+                                     int A, int continuous, int hidden, int num_layers, float* params, const int* offsets,
+                                     int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                     int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
+                                     const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
+                                     void* workspace, void* stream);
 
 /* K12 -- the weight gradient of the 3x3 convolution of aurppo_conv3x3_f32 (src/nets/base_cnns.py:32-45, src/nets/equiv.py:12-62;
  * what loss.backward() leaves in <conv>.weight.grad, src/robot_ppo.py:389): dw (Co, Ci, 3, 3) from x (B, Ci, H, W) and the
