@@ -26,6 +26,7 @@ SYMBOLS = (
     "aurppo_head_act_f32",
     "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_linear_wgrad_bias_f32", "aurppo_mlp_layered_step_workspace_bytes",
     "aurppo_mlp_layered_step_f32", "aurppo_mlp_layered_minibatch_f32",
+    "aurppo_conv3x3_pool_f32",
 )
 
 _lib = None
@@ -103,6 +104,7 @@ def _declare(lib):
     # K11, the linear products, K13, K12
     lib.aurppo_conv3x3_wop_bytes.argtypes = [i32, i32]
     lib.aurppo_conv3x3_f32.argtypes = [vp, vp, vp] + [i32] * 7 + ws_stream
+    lib.aurppo_conv3x3_pool_f32.argtypes = [vp] * 5 + [i32] * 6 + ws_stream
     lib.aurppo_linear_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
     lib.aurppo_linear_bias_act_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
     lib.aurppo_linear_wgrad_ws_bytes.argtypes = [C.c_longlong, i32, i32]

@@ -50,6 +50,7 @@ class base_encoder(nn.Module):
     fused_pool = True      # K9 on CUDA tensors (False: the stock torch ops everywhere, for A/B runs)
     fused_conv = os.environ.get("AURPPO_NO_K11") != "1"      # K11 for the hidden 3x3 convolutions on CUDA tensors (False / AURPPO_NO_K11=1: torch / MIOpen, for A/B runs)
     fused_first = True     # K10 for the first block when it runs in split form on CUDA tensors
+    fused_block = os.environ.get("AURPPO_K11_POOL") == "1"   # K11p: a hidden block's convolution, bias, ReLU and pool in one launch (opt-in)
 
     def _blocks(self, x, start, scale=None, plane=None, first_weight=None):
         """Run self.conv[start:] on x; on the GPU every (Conv2d, ReLU, MaxPool2d(2)) triple becomes convolution without bias
@@ -66,6 +67,11 @@ class base_encoder(nn.Module):
                       and mods[i + 2].stride in (2, (2, 2)) and mods[i + 2].padding in (0, (0, 0)))
             if use and triple:
                 w = first_weight if (i == start and first_weight is not None) else m.weight
+                own_tail = i == start and (scale is not None or plane is not None)      # the split first block's state plane: K9's
+                if self.fused_block and self.fused_conv and w is m.weight and not own_tail and H.conv3x3_pool_supported(x, m):
+                    x = H.conv3x3_pool(x, m.weight, m.bias, m.padding[0])       # K11p: z is never written
+                    i += 3
+                    continue
                 if self.fused_conv and w is m.weight and H.conv3x3_supported(x, m):
                     z = H.conv3x3(x, w, m.padding[0])
                 else:

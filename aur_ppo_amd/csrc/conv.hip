@@ -18,7 +18,8 @@
 //     neighbouring pixel blocks of the same channel group and share its lines in L1);
 //   * epilogue: the 32 x 32 accumulator blocks go through a padded LDS tile so that the stores are 128-byte rows of an output
 //     plane instead of 16-byte pieces of 64 planes.
-// Output is the convolution without bias (the block's bias + ReLU + max-pool tail is K9, csrc/pool.hip).
+// Output is the convolution without bias (the block's bias + ReLU + max-pool tail is K9, csrc/pool.hip) -- or, in the POOL builds
+// (K11p, aurppo_conv3x3_pool_f32), the whole block's pooled output and K9's mask, that tail taken in the epilogue.
 #include <stdio.h>
 
 #pragma clang fp contract(fast)
@@ -85,6 +86,15 @@ struct ConvArgs {
     int n_mb4;                       // workgroups along M (4 waves x kMB pixel blocks each)
 };
 
+// K11p (the POOL builds): the same product whose epilogue adds the bias and takes ReLU + the 2 x 2 max-pool of K9 (csrc/pool.hip), so
+// the full-resolution pre-activation is never stored.
+struct ConvPoolArgs {
+    ConvArgs c;                      // the product, with Ho x Wo the POOLED map ((H + 2 pad - 2) >> 1, ...), z (B, Cout, Ho, Wo) the
+                                     // block's pooled output and M = 4 * B * Ho * Wo, the four positions of every window
+    const float* bias;               // (Cout,) or nullptr
+    uint8_t* mask;                   // (B, Cout, Ho, Wo): K9's byte
+};
+
 __device__ __forceinline__ int acc_row_c(int e, int lane) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
 
 // filter -> operand order.  transpose_flip = 0 (forward): B[k = (tap, ci)][n = co] = W[co][ci][tap];
@@ -145,151 +155,20 @@ __device__ __forceinline__ void dma16(const void* src, void* dst_wave_uniform) {
 // 48 matrix instructions, and the two barely overlap (SQ_VALU_MFMA_COEXEC_CYCLES 7 % of the matrix time, profiles/r04).
 template <int NB, bool BUF>      // NB: 32-channel blocks of the channel group (1, 2 or 4)
 __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvArgs a) {
-    constexpr int kChunkBytes = kKC * NB * 3 * 1024;
-    constexpr int kLdsBytes = 2 * kChunkBytes > (kConvThreads / kWave) * 32 * kTileLd * 4 ? 2 * kChunkBytes
-                                                                                        : (kConvThreads / kWave) * 32 * kTileLd * 4;
-    __shared__ __attribute__((aligned(16))) char s_b[kLdsBytes];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int mb8 = (int)(blockIdx.x % (unsigned)a.n_mb4), ng = (int)(blockIdx.x / (unsigned)a.n_mb4);
-    const int h = lane >> 5;
-    const int HWo = a.Ho * a.Wo, HW = a.H * a.W;
-    const int CG = a.CG, KS = 9 * CG;
-    bool valid[kMB];
-    int yy[kMB], xx[kMB];
-    size_t img[kMB], out_px[kMB];
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb) {
-        const long long m = (((long long)mb8 * 4 + w) * kMB + mb) * 32 + (lane & 31);
-        valid[mb] = m < a.M;
-        int b = 0, y = 0, x = 0;
-        if (valid[mb]) {
-            b = (int)(m / HWo);
-            const int r = (int)(m - (long long)b * HWo);
-            y = r / a.Wo;
-            x = r - y * a.Wo;
-        }
-        yy[mb] = y; xx[mb] = x;
-        img[mb] = (size_t)b * a.Cin * HW;
-        out_px[mb] = (size_t)b * a.Cout * HWo + (size_t)(y * a.Wo + x);
-    }
-    // the filter of this channel group: [nb][k-step][plane][lane][16 B]; a chunk = k-steps kc*kKC .. of every nb
-    const char* const wgrp = reinterpret_cast<const char*>(a.wop) + (size_t)(ng * NB) * KS * 3 * 1024;
-    // fragment f of a chunk (f = (kk * NB + nb) * 3 + plane): wave w brings fragments w, w + 4, ...
-    auto stage = [&](int kc, int buf) {
-        char* const dst = s_b + buf * kChunkBytes;
-#pragma unroll
-        for (int f = 0; f < kKC * NB * 3; ++f) {
-            if ((f & 3) != w) continue;              // (wave-uniform)
-            const int pl = f % 3, nb = (f / 3) % NB, kk = f / (3 * NB);
-            const int ks = kc * kKC + kk;
-            if (ks < KS) dma16(wgrp + ((size_t)(nb * KS + ks) * 3 + pl) * 1024 + lane * 16, dst + f * 1024);
-        }
-    };
-
-    f32x16c acc[kMB][NB];
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mb][nb][e] = 0.0f;
-
-    // the A values of one k-step: this lane's 8 channels of the tap's input pixel, for both pixel blocks
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a.x), 0, BUF ? (unsigned)((size_t)a.B * a.Cin * HW * 4) : 0u, 0x00020000);
-    unsigned pix_off[kMB];           // BUF: byte offset of (b, channel 8 h, y - pad, x - pad) -- may wrap below zero, used with a valid tap only
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb)
-        pix_off[mb] = (unsigned)((img[mb] + (size_t)(8 * h) * HW) * 4) + (unsigned)(((yy[mb] - a.pad) * a.W + (xx[mb] - a.pad)) * 4);
-    auto load_a = [&](int ks, float (&v)[kMB][8]) {
-        const int tap = ks / CG, cg = ks - tap * CG;
-        const int ky = tap / 3, kx = tap - 3 * ky;
-#pragma unroll
-        for (int mb = 0; mb < kMB; ++mb) {
-            const int iy = yy[mb] + ky - a.pad, ix = xx[mb] + kx - a.pad;
-            const bool inb = valid[mb] && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            if (BUF) {
-                const unsigned vo = inb ? pix_off[mb] + (unsigned)((ky * a.W + kx) * 4) : 0xfffffff0u;     // past the buffer: reads 0
-                const int so0 = cg * 16 * HW * 4;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    v[mb][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, vo, so0 + j * HW * 4, 0));
-            } else {
-                const size_t at = img[mb] + (size_t)(cg * 16 + 8 * h) * HW + (size_t)(inb ? iy * a.W + ix : 0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float t = a.x[inb ? at + (size_t)j * HW : 0];
-                    v[mb][j] = inb ? t : 0.0f;
-                }
-            }
-        }
-    };
-    const int n_chunks = (KS + kKC - 1) / kKC;
-    float abuf[2][kMB][8];           // k-step ks computes from abuf[ks & 1] while abuf[(ks + 1) & 1] is in flight (kKC = 2: the parity is kk's)
-    static_assert(kKC == 2, "the A registers ping-pong on the k-step's position inside its chunk");
-    stage(0, 0);
-    load_a(0, abuf[0]);
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");      // (the DMA pieces are older than the 16 loads of load_a)
-    __syncthreads();
-    for (int kc = 0; kc < n_chunks; ++kc) {
-        if (kc + 1 < n_chunks) stage(kc + 1, (kc + 1) & 1);
-        const char* const bsrc = s_b + (kc & 1) * kChunkBytes + lane * 16;
-#pragma unroll
-        for (int kk = 0; kk < kKC; ++kk) {
-            const int ks = kc * kKC + kk;
-            if (ks < KS) {
-                float (&cur)[kMB][8] = abuf[kk];
-                if (ks + 1 < KS) load_a(ks + 1, abuf[kk ^ 1]);
-                Frag3 A[kMB];
-#pragma unroll
-                for (int mb = 0; mb < kMB; ++mb) {
-                    unsigned p[4][3];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) split3(cur[mb][2 * q], cur[mb][2 * q + 1], p[q][0], p[q][1], p[q][2]);
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        const u32x4 v = {p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
-                        A[mb].p[pl] = __builtin_bit_cast(bf16x8, v);
-                    }
-                    if (kStepNeg(kk)) A[mb] = neg3(A[mb]);      // (kk is a constant of the unrolled loop)
-                }
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) {
-                    Frag3 Bf;
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) Bf.p[pl] = *reinterpret_cast<const bf16x8*>(bsrc + ((kk * NB + nb) * 3 + pl) * 1024);
-#pragma unroll
-                    for (int mb = 0; mb < kMB; ++mb)
-                        acc[mb][nb] = kStepNeg(kk) ? mma32x3_step<true>(A[mb], Bf, acc[mb][nb]) : mma32x3_step<false>(A[mb], Bf, acc[mb][nb]);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the next chunk's DMA pieces (and the A values) have landed
-        __syncthreads();
-    }
-
-    // ---- epilogue: per 32 x 32 block, accumulator -> LDS tile [n][pixel] -> 128-byte rows of the output planes
-    float* const tile = reinterpret_cast<float*>(s_b) + w * 32 * kTileLd;
-#pragma unroll
-    for (int mb = 0; mb < kMB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int n0 = (ng * NB + nb) * 32;
-            if (n0 < a.Cout) {       // wave-uniform
-#pragma unroll
-                for (int e = 0; e < 16; ++e) tile[(lane & 31) * kTileLd + acc_row_c(e, lane)] = acc[mb][nb][e];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own stores (no other wave touches this tile)
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int n = h + 2 * i;
-                    if (valid[mb] && n0 + n < a.Cout) a.z[out_px[mb] + (size_t)(n0 + n) * HWo] = tile[n * kTileLd + (lane & 31)];
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
+    constexpr bool POOL = false;
+    constexpr const float* pool_bias = nullptr;
+    constexpr uint8_t* pool_mask = nullptr;
+#include "conv3x3_body.h"
+}
+// The POOL builds (K11p, conv3x3_body.h says what they are) are an overload with a third template parameter and their own argument
+// block, not a defaulted parameter on the template above: that one keeps its symbols and its instruction streams.
+template <int NB, bool BUF, bool POOL>
+__global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvPoolArgs p) {
+    static_assert(POOL, "the plain builds are k_conv3x3<NB, BUF>");
+    const ConvArgs& a = p.c;
+    const float* const pool_bias = p.bias;
+    uint8_t* const pool_mask = p.mask;
+#include "conv3x3_body.h"
 }
 
 // ---- the same product for nn.Linear (src/nets/nets.py:21-27,33-39,45-51 with hidden_dim > 128, which the fused K7 / K7w steps do not
@@ -695,6 +574,54 @@ extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int 
         else hipLaunchKernelGGL((k_conv3x3<1, false>), g, blk, 0, s, a);
     }
     AURPPO_LAUNCH_CHECK("k_conv3x3");
+    return AURPPO_OK;
+}
+
+// K11p: y, mask = max_pool2d(relu(conv2d(x, w, padding = pad) + bias[c]), 2) with K9's semantics; x (B, Ci, H, W), w (Co, Ci, 3, 3),
+// y / mask (B, Co, (H + 2 pad - 2) >> 1, (W + 2 pad - 2) >> 1).  Refuses what mode 0 above refuses, and a map without a whole window.
+extern "C" int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci,
+                                       int Co, int H, int W, int pad, void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(x && w && y && mask && wop_ws, AURPPO_EINVAL, "aurppo_conv3x3_pool_f32: null pointer");
+    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: pad=%d (0..2)", pad);
+    AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0 && Ci % 16 == 0, AURPPO_ESHAPE,
+                   "aurppo_conv3x3_pool_f32: B=%d H=%d W=%d, %d input channels (a multiple of 16), %d output channels", B, H, W, Ci, Co);
+    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+    AURPPO_REQUIRE(Ho > 0 && Wo > 0, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: empty output (%d x %d)", Ho, Wo);
+    const int Hp = Ho >> 1, Wp = Wo >> 1;
+    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
+    AURPPO_REQUIRE((size_t)B * Ci * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
+                   "aurppo_conv3x3_pool_f32: operand too large / workspace not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
+    ConvPoolArgs pa;
+    pa.bias = bias; pa.mask = mask;
+    ConvArgs& a = pa.c;
+    a.x = x; a.wop = wop; a.z = y;
+    a.B = B; a.Cin = Ci; a.H = H; a.W = W; a.Cout = Co; a.Ho = Hp; a.Wo = Wp; a.pad = pad;
+    a.M = 4ll * B * Hp * Wp;
+    a.CG = Ci / 16;
+    const long long n_mb4 = (a.M + 32 * 4 * kMB - 1) / (32 * 4 * kMB);     // workgroups along M: 4 waves x kMB blocks of 8 windows
+    AURPPO_REQUIRE(n_mb4 < (1ll << 30), AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: too many pixel blocks");
+    a.n_mb4 = (int)n_mb4;
+    const int nblk = (Co + 31) / 32;
+    const int NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
+    const int n_ng = (nblk + NB - 1) / NB;
+    const long long grid = n_mb4 * n_ng;
+    AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: grid too large");
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, wop, 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    const bool buf = (size_t)B * Ci * H * W * 4 < ((size_t)1 << 32) - ((size_t)1 << 20);       // (as in aurppo_conv3x3_f32)
+    const dim3 g((unsigned)grid), blk(kConvThreads);
+    if (buf) {
+        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, true, true>), g, blk, 0, s, pa);
+        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, true, true>), g, blk, 0, s, pa);
+        else hipLaunchKernelGGL((k_conv3x3<1, true, true>), g, blk, 0, s, pa);
+    } else {
+        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, false, true>), g, blk, 0, s, pa);
+        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, false, true>), g, blk, 0, s, pa);
+        else hipLaunchKernelGGL((k_conv3x3<1, false, true>), g, blk, 0, s, pa);
+    }
+    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool)");
     return AURPPO_OK;
 }
 

@@ -98,9 +98,16 @@ class _Block(nn.Module):
         super().__init__()
         self.conv, self.pool = conv, pool
 
+    fused_block = os.environ.get("AURPPO_K11_POOL") == "1"   # K11p: convolution, bias, ReLU and pool in one launch (opt-in)
+
     def forward(self, x):
         if self.pool == 2 and x.is_cuda and getattr(self, "fused_pool", True):
             from . import hip_ops as H
+            conv = self.conv
+            if self.fused_block and conv.fused_conv and conv.kernel_size == 3:
+                w = conv.expanded_weight()
+                if H.conv3x3_pool_ok(x, w.shape[1], w.shape[0], conv.padding):
+                    return H.conv3x3_pool(x, w, conv.expanded_bias(), conv.padding)
             return H.bias_relu_pool2(self.conv(x, with_bias=False), self.conv.expanded_bias())
         y = F.relu(self.conv(x))
         return F.max_pool2d(y, self.pool) if self.pool else y

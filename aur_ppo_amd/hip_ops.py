@@ -818,29 +818,35 @@ class _Conv3x3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib_or_raise()
         x, w = ctx.saved_tensors
-        g = g.contiguous()
-        B, Ci, Hh, Ww = x.shape
-        Co, pad = w.shape[0], ctx.pad
-        dx = dw = None
-        if ctx.needs_input_grad[0] and Ci % 32 != 0 and os.environ.get("AURPPO_K11_DGRAD16") != "1":
-            # an input gradient with 16 output channels would leave half of every 32-wide matrix block empty: the library's kernel
-            dx = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
-                                                     [True, False, False])[0]
-        elif ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x)
-            ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Co, Ci), x.device)
-            _check(lib.aurppo_conv3x3_f32(_ptr(g), _ptr(w.detach()), _ptr(dx), B, Ci, Co, g.shape[2], g.shape[3], pad, 1,
-                                          *_ws_stream(ws)), "aurppo_conv3x3_f32")
-        if ctx.needs_input_grad[1]:
-            if conv3x3_wgrad_ok(x, Ci, Co, pad):
-                dw = conv3x3_wgrad(g, x, Co, pad)       # K12
-            else:
-                # small channel counts would leave most of K12's 128 x 128 tile empty: the library's implicit-GEMM kernels
-                dw = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
-                                                         [False, True, False])[1]
+        dx, dw = _conv3x3_grads(g.contiguous(), x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return dx, dw, None
+
+
+def _conv3x3_grads(g, x, w, pad, need_dx, need_dw):
+    """(dx, dw) of ``conv2d(x, w, padding=pad)`` under the output gradient ``g`` (contiguous): K11's mode 1 and K12 where their
+    shape rules hold, the library's kernels elsewhere.  The backward of ``conv3x3`` and of ``conv3x3_pool``."""
+    lib = _lib_or_raise()
+    B, Ci, Hh, Ww = x.shape
+    Co = w.shape[0]
+    dx = dw = None
+    if need_dx and Ci % 32 != 0 and os.environ.get("AURPPO_K11_DGRAD16") != "1":
+        # an input gradient with 16 output channels would leave half of every 32-wide matrix block empty: the library's kernel
+        dx = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
+                                                 [True, False, False])[0]
+    elif need_dx:
+        dx = torch.empty_like(x)
+        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Co, Ci), x.device)
+        _check(lib.aurppo_conv3x3_f32(_ptr(g), _ptr(w.detach()), _ptr(dx), B, Ci, Co, g.shape[2], g.shape[3], pad, 1,
+                                      *_ws_stream(ws)), "aurppo_conv3x3_f32")
+    if need_dw:
+        if conv3x3_wgrad_ok(x, Ci, Co, pad):
+            dw = conv3x3_wgrad(g, x, Co, pad)       # K12
+        else:
+            # small channel counts would leave most of K12's 128 x 128 tile empty: the library's implicit-GEMM kernels
+            dw = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
+                                                     [False, True, False])[1]
+    return dx, dw
 
 
 def conv3x3_wgrad_ok(x, cin, cout, pad):
@@ -898,6 +904,68 @@ def conv3x3(x, weight, padding):
     """K11: ``conv2d(x, weight, None, stride=1, padding=padding)`` for a 3x3 filter on the bf16 matrix pipe (fp32 products from
     three-way bf16 splits), forward and input gradient (src/nets/base_cnns.py:32-45's hidden convolutions)."""
     return _Conv3x3.apply(x, weight, int(padding))
+
+
+class _Conv3x3Pool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, pad):
+        lib = _lib_or_raise()
+        x, w = x.contiguous(), w.contiguous()
+        B, Ci, Hh, Ww = x.shape
+        Co = w.shape[0]
+        Ho, Wo = Hh + 2 * pad - 2, Ww + 2 * pad - 2
+        y = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.float32, device=x.device)
+        mask = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.uint8, device=x.device)
+        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
+        _check(lib.aurppo_conv3x3_pool_f32(_ptr(x.detach()), _ptr(w.detach()), _optr(bias.detach().contiguous() if bias is not None else None),
+                                           _ptr(y), C.c_void_p(mask.data_ptr()), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
+               "aurppo_conv3x3_pool_f32")
+        ctx.save_for_backward(x, w, mask)
+        ctx.pad, ctx.has_bias = int(pad), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib_or_raise()
+        x, w, mask = ctx.saved_tensors
+        B, Co, Hp, Wp = mask.shape
+        Ho, Wo = x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2
+        dy = dy.contiguous()
+        # K9's backward rebuilds dz from the pooled gradient and the mask alone; from there on it is conv3x3's backward
+        dz = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=dy.device)
+        part = torch.empty((B, Co), dtype=torch.float32, device=dy.device) if ctx.has_bias else None
+        _check(lib.aurppo_bias_relu_pool2_bwd_f32(_ptr(dy), C.c_void_p(mask.data_ptr()), _ptr(dz), _optr(part), B, Co, Ho, Wo,
+                                                  _stream()), "aurppo_bias_relu_pool2_bwd_f32")
+        dbias = part.sum(0) if part is not None else None
+        dx, dw = _conv3x3_grads(dz, x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dx, dw, dbias, None
+
+
+def conv3x3_pool_ok(x, cin, cout, pad):
+    """K11p's shape rule: ``conv3x3_ok``'s with the pixel count taken as the four positions of every whole pooling window
+    (4 * B * Hp * Wp: an odd trailing row / column is never computed), and at least one window."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
+            and pad in (0, 1, 2)):
+        return False
+    hp, wp = (x.shape[2] + 2 * pad - 2) // 2, (x.shape[3] + 2 * pad - 2) // 2
+    if hp < 1 or wp < 1:
+        return False
+    pixels = 4 * x.shape[0] * hp * wp
+    return pixels >= CONV3X3_MIN_PIXELS or ((pixels + 255) // 256) * ((cout + 127) // 128) >= CONV3X3_MIN_WGS
+
+
+def conv3x3_pool_supported(x, conv):
+    """``conv3x3_pool_ok`` for an ``nn.Conv2d`` that a ReLU and a ``MaxPool2d(2)`` follow (``conv3x3_supported``'s module rule)."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and conv.padding in ((0, 0), (1, 1), (2, 2)) and conv.padding_mode == "zeros"
+            and conv3x3_pool_ok(x, conv.in_channels, conv.out_channels, conv.padding[0]))
+
+
+def conv3x3_pool(x, weight, bias, padding):
+    """K11p: ``max_pool2d(relu(conv2d(x, weight, bias, padding=padding)), 2)`` in one launch -- K11 with K9's bias / ReLU / pool in
+    its epilogue, bit for bit ``bias_relu_pool2(conv3x3(x, weight, padding), bias)`` without the full-resolution tensor in
+    between.  The backward is K9's (the mask is saved) followed by ``conv3x3``'s."""
+    return _Conv3x3Pool.apply(x, weight, bias, int(padding))
 
 
 LINEAR_MIN_ROWS = 32768

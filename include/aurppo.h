@@ -257,6 +257,14 @@ int aurppo_mlp_ppo_apply_parts_f32(float* params, float* grads, float* exp_avg, 
 size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm);
 int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w, int Co_w, int H, int W, int pad, int mode,
                        void* wop_ws, void* stream);
+/* K11p: a whole hidden block, nn.Conv2d(Ci, Co, 3, padding = pad) -> nn.ReLU -> nn.MaxPool2d(2), in one launch: K11's mode 0 with
+ * the bias, the ReLU and the pool of aurppo_bias_relu_pool2_fwd_f32 in its epilogue, so the full-resolution pre-activation is
+ * never stored.  y, mask (B, Co, (H + 2 pad - 2) / 2, (W + 2 pad - 2) / 2) (floor) hold bit for bit what that pair of calls leaves:
+ * the first maximum in scan order, a NaN wins, mask = its window position 0..3 or 4 where the maximum is <= 0 (y = 0 there).
+ * bias (Co) may be NULL.  wop_ws: aurppo_conv3x3_wop_bytes(Ci, Co) bytes.  Refuses what mode 0 refuses, and AURPPO_ESHAPE for a
+ * map without one whole window.  The backward is aurppo_bias_relu_pool2_bwd_f32 on the mask, then K11's mode 1 and K12. */
+int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci, int Co,
+                            int H, int W, int pad, void* wop_ws, void* stream);
 
 /* nn.Linear without its bias on the same arithmetic (the MLP policies wider than the fused steps cover, hidden_dim > 128:
  * src/nets/nets.py:21-27,33-39,45-51 per layer).  mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T, any K_w >= 1;
