@@ -5,7 +5,7 @@
 // (dropped: a1*b2, a2*b1, a2*b2 <= 2^-25 |a*b|), each product exact in fp32.  (Their ADDITION to a long running sum is not: chained
 // through one accumulator, as mma32x3 does, a third-order product is dropped once the sum has grown past 2^8 terms or so, and the
 // pipe cuts towards minus infinity; over the reductions of the MLP steps, <= 1024 with signs mixed, that stays inside their fp64 bars --
-// the convolutions' reductions of up to 2304 did not, conv.hip::mma32x3_step)  Six
+// the convolutions' reductions of up to 2304 did not, bf3_gemm.h::mma32x3_step)  Six
 // v_mfma_f32_32x32x16_bf16 (32 cycles, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles, K = 2): 192 instead of
 // 512 matrix-pipe cycles per 32 x 32 x 16 block, at fp32 accuracy (tools/bf16x3_check.hip measures both).
 //

@@ -68,11 +68,21 @@ int launch_dyn_lds(const char* name, int grid, int threads, size_t lds, size_t l
 // CUs of the calling thread's current device (asked once per device; `fallback` if the runtime reports none), or a negative AURPPO_E*
 // code with the error set (api.hip)
 int aurppo_cu_count(int fallback);
-// The prepared-operand half of the linear products (conv.hip), for the layered rollout step (head.hip): bytes of one forward
-// operand copy of a (N, K) weight, and y (M, N) = act(x (M, K) . w^T + bias) from such a copy (act: 0 none, 1 tanh).
+// The prepared-operand half of the linear products (linear.hip), for the layered steps (layered.hip): bytes of one forward operand
+// copy of a (N, K) weight, the launch that writes it (conv.hip; mode 0; 1: the input gradient's), and y (M, N) = act(x (M, K) . w^T + bias)
+// from such a copy (act: 0 none, 1 tanh).
 constexpr int kLayeredMaxLayers = 16;
 size_t aurppo_linear_wop_bytes(int K, int N);
+int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s);
 int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N, void* stream);
+// K13 / K14's shape rule and K14 on checked operands (head.hip), for the layered steps
+bool head_shape_ok(int H, int A, int continuous);
+int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,
+                    const int* lay, float* actions, float* logp, float* value, hipStream_t s);
+// The kernels conv.hip and linear.hip both run live in conv.hip: linear_prep above (k_conv_prep / k_linear_prep_tail), the fold of a
+// weight gradient's S slices (db != nullptr: k_fold_slices_bias, with the column sums bpart (S, N) -> db), and the slice count.
+int fold_slices_launch(const float* part, int S, long long n, float* out, const double* bpart, int N, float* db, hipStream_t s);
+int slices_for(long long tiles, long long most);
 // Diagnostic knobs.  Every environment variable the library looks at is parsed in ONE place (api.hip) into this struct,
 // once per process -- or on every call when AURPPO_TEST_KNOBS=1 (tests/conftest.py), so that one test process can flip
 // them.  None of them changes results beyond summation order; the defaults are the product configuration.

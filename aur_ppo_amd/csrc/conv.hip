@@ -20,61 +20,13 @@
 //     plane instead of 16-byte pieces of 64 planes.
 // Output is the convolution without bias (the block's bias + ReLU + max-pool tail is K9, csrc/pool.hip) -- or, in the POOL builds
 // (K11p, aurppo_conv3x3_pool_f32), the whole block's pooled output and K9's mask, that tail taken in the epilogue.
-#include <stdio.h>
-
 #pragma clang fp contract(fast)
-#include "bf16x3.h"
+#include "bf3_gemm.h"
 #include "common.h"
 
 using namespace bf3;
 
 namespace {
-
-typedef float f32x16c __attribute__((ext_vector_type(16)));
-
-// One k-step of a convolution's product: the six plane products of bf16x3.h summed from ZERO, smallest first, and the step's sum added
-// to the running accumulator once.  mma32x3 chains all six through the running accumulator; after a few k-steps that sum is so much
-// larger than a third-order product (2^-16 of a term) that the matrix pipe's addition drops it whole: on operands with known positive
-// planes K11 and K12 lost 15 % of the third-order terms at a reduction of 288, 87 % at 2304 (tools/conv_plane_bias.py), and the robot
-// policy's gradients through them sat at 6 x plain fp32 against an fp64 net.  Here each step's small products meet only
-// that step's own a0 * b0, and the accumulator takes one rounded fp32 addition per k-step.
-// NEG: the step is computed as -(sum of (-a) * b).  The matrix pipe cuts the bits below its adder's width off TOWARDS MINUS INFINITY,
-// whatever the sign of the sum: 5e-9 of the sum of |terms| per output, always negative, which a sum over 10^5 pixels (a bias
-// gradient) does not average away.  Every other k-step runs negated, so the cuts of neighbouring steps cancel.
-__device__ __forceinline__ Frag3 neg3(const Frag3& a) {
-    Frag3 r;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        u32x4 v = __builtin_bit_cast(u32x4, a.p[pl]);
-        v = v ^ u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
-        r.p[pl] = __builtin_bit_cast(bf16x8, v);
-    }
-    return r;
-}
-// -DCONV_EXP_NO_ALTERNATE: every k-step with the same sign (a measuring build: tools/conv_plane_bias.py shows the one-sided cut alone)
-__device__ __forceinline__ constexpr bool kStepNeg(int k) {
-#ifdef CONV_EXP_NO_ALTERNATE
-    return false;
-#else
-    return (k & 1) != 0;
-#endif
-}
-template <bool NEG>
-__device__ __forceinline__ f32x16c mma32x3_step(const Frag3& a, const Frag3& b, f32x16c c) {      // NEG: ``a`` comes negated (neg3)
-    f32x16c t;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) t[e] = 0.0f;
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[2], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[2], b.p[0], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[1], b.p[1], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[1], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[1], b.p[0], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.p[0], b.p[0], t, 0, 0, 0);
-    return NEG ? c - t : c + t;
-}
-constexpr int kConvThreads = 256;
-constexpr int kNBW = 4;              // 32-channel blocks per wave
-constexpr int kTileLd = 33;          // floats per row of the epilogue's LDS tile
 
 struct ConvArgs {
     const float* x;                  // (B, Cin, H, W)
@@ -94,8 +46,6 @@ struct ConvPoolArgs {
     const float* bias;               // (Cout,) or nullptr
     uint8_t* mask;                   // (B, Cout, Ho, Wo): K9's byte
 };
-
-__device__ __forceinline__ int acc_row_c(int e, int lane) { return (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5); }
 
 // filter -> operand order.  transpose_flip = 0 (forward): B[k = (tap, ci)][n = co] = W[co][ci][tap];
 // 1 (input gradient): the product's "input" channels are the forward pass's OUTPUT channels: B[k = (tap, co)][n = ci] =
@@ -136,15 +86,6 @@ __global__ __launch_bounds__(256) void k_linear_prep_tail(const float* __restric
     conv_prep_body<true>(w, N_w, K_w, k_gemm, N_w, 0, wop, 1);
 }
 
-constexpr int kMB = 2;               // 32-pixel blocks per wave
-constexpr int kKC = 2;               // k-steps per staged chunk of the filter
-
-// LDS-DMA: 16 bytes per lane from global memory straight into LDS at dst + lane * 16 (wave-uniform dst), no registers in between
-__device__ __forceinline__ void dma16(const void* src, void* dst_wave_uniform) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst_wave_uniform, 16, 0, 0);
-}
-
 // Workgroup = 4 waves x (2 x 32 pixels) = 256 consecutive output pixels x NB 32-channel blocks.  The filter's fragments of two
 // k-steps at a time (kKC x NB x 3 KB) are brought into LDS ONCE per workgroup by LDS-DMA, double-buffered, one barrier per chunk;
 // every wave reads its B fragments from there (with each wave fetching its own from L2, the CU's L2 path -- about 16 B per
@@ -170,84 +111,6 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvPoolArgs 
     uint8_t* const pool_mask = p.mask;
 #include "conv3x3_body.h"
 }
-
-// ---- the same product for nn.Linear (src/nets/nets.py:21-27,33-39,45-51 with hidden_dim > 128, which the fused K7 / K7w steps do not
-// cover): y (M, N) = x (M, K) . B (K, N), x row-major -- a 1 x 1 "convolution" whose pixels are the minibatch's rows.  Same
-// filter staging and matrix loop as k_conv3x3; the A values of a k-step are 32 contiguous bytes per lane (two 16-byte loads), and
-// the accumulator's lane-per-column layout already matches the row-major output (32 lanes = 128 contiguous bytes): no LDS tile.
-struct LinArgs {
-    const float* x;                  // (M, K)
-    const unsigned short* wop;       // [n-block][k-step][plane][lane][8]
-    float* y;                        // (M, N)
-    const float* bias;               // (N,) or nullptr
-    long long M;
-    int K, N, n_mb;
-    int act;                         // 0: none, 1: tanh (1 - 2 / (e^{2x} + 1), as the fused MLP steps form it)
-                                     // 2 (GATE builds): y = acc * (1 - h * h), tanh' of the layer below from its output h
-    const int32_t* rows;             // ROWS builds: (M,) lane row m reads x row rows[m] (the minibatch index); y stays in minibatch order
-    const float* h;                  // GATE builds: (M, N), read at the address the store uses
-};
-
-// ROWS (layer 0 of the layered PPO step, hip_ops.mlp_layered_step: x through the minibatch index) and GATE (its input gradients:
-// tanh' of the layer below in the epilogue) are template parameters, so the plain instantiations keep their instruction streams.
-// KTAIL (k_linear_tail: K is no multiple of 16 -- layer 0 of a policy whose state is 3, 11, 17, 376 floats wide): KS = ceil(K / 16)
-// k-steps against an operand copy whose columns >= K are zero planes (k_linear_prep_tail).  A row is K floats and nothing more: it
-// starts at a 4-byte boundary, what follows it is another row, somebody else's memory or an unmapped page.  So every k-step's A values
-// are eight dword loads per lane, each one issued only where its column is < K, and the columns >= K enter split3 as a selected 0.
-// The two kernel templates share one body text, linear_body.h (it says why a text): KTAIL is a constant of the including kernel.
-template <int NB, bool ROWS = false, bool GATE = false>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
-    constexpr bool KTAIL = false;
-#include "linear_body.h"
-}
-template <int NB, bool ROWS>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear_tail(const LinArgs a) {
-    constexpr bool GATE = false, KTAIL = true;
-#include "linear_body.h"
-}
-
-// ---- nn.Linear's weight gradient on the same arithmetic: dW (N, K) = dY^T (N, M) . X (M, K), both operands row-major with the
-// minibatch's rows as the product's inner dimension.  Both operands change every k-step, so both are split; to split every
-// element once per WORKGROUP (not once per wave that uses it) the workgroup stages 32 rows of its 128 dY columns and its 128 X
-// columns as bf16-plane X images in LDS (bf16x3.h: 8-byte stores along a row, fragments by transposed reads across rows -- the
-// images k_mlp_step3 lands its observation rows in), and its four waves each form a 64 x 64 quarter of the 128 x 128 tile.
-// The inner dimension is cut into S slices: partial[s] (N, K) per slice, summed by the caller in fixed order (deterministic).
-struct WgradArgs {
-    const float* dy;                 // (M, N)
-    const float* x;                  // (M, K)
-    float* part;                     // (S, N, K)
-    long long M;
-    int N, K, rows_per_slice, n_tiles_n, n_tiles_k;
-    const int32_t* rows;             // ROWS builds: (M,) row m of the product reads x row rows[m]; dy stays in minibatch order
-    double* bpart;                   // BIAS builds: (S, N) the slices' column sums of dy, behind `part` (the other builds never read it)
-};
-
-// KTAIL (k_linear_wgrad_tail: K is no multiple of 4 -- layer 0's weight gradient at a ragged state width): an X row is K floats
-// at a 4-byte boundary, so its piece of a chunk is four dword loads, each issued only where its column is < K; the columns >= K
-// are staged as a selected 0 (and the stores to `part` leave them out, as they always did).
-template <bool ROWS = false>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
-    constexpr bool KTAIL = false, BIAS = false;
-#include "linear_wgrad_body.h"
-}
-template <bool ROWS>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const WgradArgs a) {
-    constexpr bool KTAIL = true, BIAS = false;
-#include "linear_wgrad_body.h"
-}
-// The builds that also leave the layer's bias gradient, the column sums of dy (linear_wgrad_body.h).  They are overloads with a
-// second template parameter, not a defaulted one on the templates above: those keep their symbols and their instruction streams.
-template <bool ROWS, bool BIAS>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad(const WgradArgs a) {
-    constexpr bool KTAIL = false;
-#include "linear_wgrad_body.h"
-}
-template <bool ROWS, bool BIAS>
-__global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const WgradArgs a) {
-    constexpr bool KTAIL = true;
-#include "linear_wgrad_body.h"
-}
-
 
 // ---- K12: the 3x3 convolution's WEIGHT gradient on the same arithmetic.
 //     dW[co][ci][ky][kx] = sum over (b, y, x) of dY[b][co][y][x] * X[b][ci][y + ky - p][x + kx - p]
@@ -521,149 +384,41 @@ __global__ __launch_bounds__(256) void k_fold_slices_bias(const float* __restric
     out[i] = fold_slices_at(part, S, n, i);
 }
 
+// The host plan K11 and K11p share: every refusal (under the entry's name `who`), the argument block, the grid and the build, all of it
+// before the entry's first launch.  cin / cout / p are the product's own (the entry has mapped its mode); Ho x Wo is the map z holds
+// and M the product's rows -- K11: the output pixels; K11p: the pooled map and the four positions of each of its windows.
+struct ConvPlan {
+    ConvPoolArgs p;                  // (K11 launches with p.c alone)
+    Bf3Grid g;
+    bool buf;                        // the BUF builds
+};
+int conv_plan(const char* who, const float* x, const float* w, float* z, void* wop_ws, int B, int cin, int cout, int H, int W, int p,
+              int Ho, int Wo, long long M, ConvPlan* pl) {
+    AURPPO_REQUIRE(x && w && z && wop_ws, AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0 && cin % 16 == 0, AURPPO_ESHAPE,
+                   "%s: B=%d H=%d W=%d, %d input channels (a multiple of 16), %d output channels", who, B, H, W, cin, cout);
+    AURPPO_REQUIRE(H + 2 * p - 2 > 0 && W + 2 * p - 2 > 0, AURPPO_ESHAPE, "%s: empty output (%d x %d)", who, H + 2 * p - 2, W + 2 * p - 2);
+    AURPPO_REQUIRE((size_t)B * cin * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
+                   "%s: operand too large / workspace not 16-byte aligned", who);
+    ConvArgs& a = pl->p.c;
+    a.x = x; a.wop = reinterpret_cast<unsigned short*>(wop_ws); a.z = z;
+    a.B = B; a.Cin = cin; a.H = H; a.W = W; a.Cout = cout; a.Ho = Ho; a.Wo = Wo; a.pad = p;
+    a.M = M;
+    a.CG = cin / 16;
+    pl->g = bf3_grid(M, cout);
+    AURPPO_REQUIRE(pl->g.n_mb < (1ll << 30), AURPPO_ESHAPE, "%s: too many pixel blocks", who);
+    a.n_mb4 = (int)pl->g.n_mb;
+    AURPPO_REQUIRE(pl->g.n_mb * pl->g.n_ng < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", who);
+    // buffer loads address 32 bits: inputs under 4 GB (minus the slack a negative tap offset may wrap through); larger ones keep 64-bit addresses
+    pl->buf = (size_t)B * cin * H * W * 4 < ((size_t)1 << 32) - ((size_t)1 << 20);
+    return AURPPO_OK;
+}
+
 }  // namespace
 
-extern "C" size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm) {
-    const size_t nblk = (size_t)((cout_gemm + 31) / 32 + kNBW);      // (+ one group of slack: a wave reads whole groups)
-    return nblk * 9 * (size_t)((cin_gemm + 15) / 16) * 3 * 1024 + 64;      // (whole k-steps: a linear product's K may be ragged)
-}
-
-// mode 0: z = conv2d(x, w, padding = pad)                      x (B, Ci, H, W), w (Co, Ci, 3, 3), z (B, Co, H + 2 pad - 2, ...)
-// mode 1: z = d conv2d / d input applied to x:  x (B, Co, Ho, Wo) is the output gradient, z (B, Ci, Ho + 2 - 2 pad, ...) the
-//         input gradient, w the SAME (Co, Ci, 3, 3) filter, pad the FORWARD padding.
-extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w, int Co_w, int H, int W, int pad,
-                                  int mode, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(x && w && z && wop_ws, AURPPO_EINVAL, "aurppo_conv3x3_f32: null pointer");
-    AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_conv3x3_f32: mode %d", mode);
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_f32: pad=%d (0..2)", pad);
-    const int cin = mode == 0 ? Ci_w : Co_w, cout = mode == 0 ? Co_w : Ci_w;
-    const int p = mode == 0 ? pad : 2 - pad;
-    AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0 && cin % 16 == 0, AURPPO_ESHAPE,
-                   "aurppo_conv3x3_f32: B=%d H=%d W=%d, %d input channels (a multiple of 16), %d output channels", B, H, W, cin, cout);
-    const int Ho = H + 2 * p - 2, Wo = W + 2 * p - 2;
-    AURPPO_REQUIRE(Ho > 0 && Wo > 0, AURPPO_ESHAPE, "aurppo_conv3x3_f32: empty output (%d x %d)", Ho, Wo);
-    AURPPO_REQUIRE((size_t)B * cin * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
-                   "aurppo_conv3x3_f32: operand too large / workspace not 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co_w, Ci_w, cin, cout, mode, wop, 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    ConvArgs a;
-    a.x = x; a.wop = wop; a.z = z;
-    a.B = B; a.Cin = cin; a.H = H; a.W = W; a.Cout = cout; a.Ho = Ho; a.Wo = Wo; a.pad = p;
-    a.M = (long long)B * Ho * Wo;
-    a.CG = cin / 16;
-    const long long n_mb4 = (a.M + 32 * 4 * kMB - 1) / (32 * 4 * kMB);     // workgroups along M: 4 waves x kMB pixel blocks
-    AURPPO_REQUIRE(n_mb4 < (1ll << 30), AURPPO_ESHAPE, "aurppo_conv3x3_f32: too many pixel blocks");
-    a.n_mb4 = (int)n_mb4;
-    const int nblk = (cout + 31) / 32;
-    const int NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    const int n_ng = (nblk + NB - 1) / NB;
-    const long long grid = n_mb4 * n_ng;
-    AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_conv3x3_f32: grid too large");
-    // buffer loads address 32 bits: inputs under 4 GB (minus the slack a negative tap offset may wrap through); larger ones keep 64-bit addresses
-    const bool buf = (size_t)B * cin * H * W * 4 < ((size_t)1 << 32) - ((size_t)1 << 20);
-    const dim3 g((unsigned)grid), blk(kConvThreads);
-    if (buf) {
-        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, true>), g, blk, 0, s, a);
-        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, true>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_conv3x3<1, true>), g, blk, 0, s, a);
-    } else {
-        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, false>), g, blk, 0, s, a);
-        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, false>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_conv3x3<1, false>), g, blk, 0, s, a);
-    }
-    AURPPO_LAUNCH_CHECK("k_conv3x3");
-    return AURPPO_OK;
-}
-
-// K11p: y, mask = max_pool2d(relu(conv2d(x, w, padding = pad) + bias[c]), 2) with K9's semantics; x (B, Ci, H, W), w (Co, Ci, 3, 3),
-// y / mask (B, Co, (H + 2 pad - 2) >> 1, (W + 2 pad - 2) >> 1).  Refuses what mode 0 above refuses, and a map without a whole window.
-extern "C" int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci,
-                                       int Co, int H, int W, int pad, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(x && w && y && mask && wop_ws, AURPPO_EINVAL, "aurppo_conv3x3_pool_f32: null pointer");
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: pad=%d (0..2)", pad);
-    AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0 && Ci % 16 == 0, AURPPO_ESHAPE,
-                   "aurppo_conv3x3_pool_f32: B=%d H=%d W=%d, %d input channels (a multiple of 16), %d output channels", B, H, W, Ci, Co);
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    AURPPO_REQUIRE(Ho > 0 && Wo > 0, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: empty output (%d x %d)", Ho, Wo);
-    const int Hp = Ho >> 1, Wp = Wo >> 1;
-    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
-    AURPPO_REQUIRE((size_t)B * Ci * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
-                   "aurppo_conv3x3_pool_f32: operand too large / workspace not 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    ConvPoolArgs pa;
-    pa.bias = bias; pa.mask = mask;
-    ConvArgs& a = pa.c;
-    a.x = x; a.wop = wop; a.z = y;
-    a.B = B; a.Cin = Ci; a.H = H; a.W = W; a.Cout = Co; a.Ho = Hp; a.Wo = Wp; a.pad = pad;
-    a.M = 4ll * B * Hp * Wp;
-    a.CG = Ci / 16;
-    const long long n_mb4 = (a.M + 32 * 4 * kMB - 1) / (32 * 4 * kMB);     // workgroups along M: 4 waves x kMB blocks of 8 windows
-    AURPPO_REQUIRE(n_mb4 < (1ll << 30), AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: too many pixel blocks");
-    a.n_mb4 = (int)n_mb4;
-    const int nblk = (Co + 31) / 32;
-    const int NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    const int n_ng = (nblk + NB - 1) / NB;
-    const long long grid = n_mb4 * n_ng;
-    AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: grid too large");
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, wop, 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    const bool buf = (size_t)B * Ci * H * W * 4 < ((size_t)1 << 32) - ((size_t)1 << 20);       // (as in aurppo_conv3x3_f32)
-    const dim3 g((unsigned)grid), blk(kConvThreads);
-    if (buf) {
-        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, true, true>), g, blk, 0, s, pa);
-        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, true, true>), g, blk, 0, s, pa);
-        else hipLaunchKernelGGL((k_conv3x3<1, true, true>), g, blk, 0, s, pa);
-    } else {
-        if (NB == 4) hipLaunchKernelGGL((k_conv3x3<4, false, true>), g, blk, 0, s, pa);
-        else if (NB == 2) hipLaunchKernelGGL((k_conv3x3<2, false, true>), g, blk, 0, s, pa);
-        else hipLaunchKernelGGL((k_conv3x3<1, false, true>), g, blk, 0, s, pa);
-    }
-    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool)");
-    return AURPPO_OK;
-}
-
-// mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T      -- nn.Linear without its bias; any K_w >= 1 (no multiple of 16: the tail builds)
-// mode 1: y (M, K_w) = x (M, N_w) . w (N_w, K_w)         -- the gradient with respect to the input (x is dY); N_w a multiple of 16
-// wop_ws: aurppo_conv3x3_wop_bytes(product's K, product's N) / 9 bytes suffice; the same function's size is accepted.
-static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream, const int32_t* rows = nullptr, const float* h = nullptr);
-
-extern "C" int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,
-                                 void* stream) {
-    return linear_impl(x, w, nullptr, 0, y, M, K_w, N_w, mode, wop_ws, stream);
-}
-
-// y (M, N_w) = act(x (M, K_w) . w (N_w, K_w)^T + bias): nn.Linear with its bias and, act = 1, the nn.Tanh behind it
-// (src/nets/nets.py:21-27: every hidden layer of the reference's MLPs) in the product's epilogue.
-extern "C" int aurppo_linear_bias_act_f32(const float* x, const float* w, const float* bias, float* y, long long M, int K_w, int N_w,
-                                          int act, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_bias_act_f32: act %d", act);
-    return linear_impl(x, w, bias, act, y, M, K_w, N_w, 0, wop_ws, stream);
-}
-
-// The same with lane row m reading x row rows[m] (rows == NULL: aurppo_linear_bias_act_f32): the K3 gather of the minibatch's
-// observations (src/ppo.py:219-220) rides in the first layer's product.  Every rows[m] must name a row of x.
-extern "C" int aurppo_linear_rows_bias_act_f32(const float* x, const int32_t* rows, const float* w, const float* bias, float* y,
-                                               long long M, int K_w, int N_w, int act, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_rows_bias_act_f32: act %d", act);
-    return linear_impl(x, w, bias, act, y, M, K_w, N_w, 0, wop_ws, stream, rows);
-}
-
-// out (M, K_w) = (gz (M, N_w) . w (N_w, K_w)) * (1 - h * h), h (M, K_w): the input gradient of a hidden layer with tanh' of the
-// layer below in the epilogue (what autograd's mm + tanh_backward leave); out may be h itself.
-extern "C" int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const float* h, float* out, long long M, int K_w, int N_w,
-                                         void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(h, AURPPO_EINVAL, "aurppo_linear_dx_tanh_f32: null pointer");
-    return linear_impl(gz, w, nullptr, 2, out, M, K_w, N_w, 1, wop_ws, stream, nullptr, h);
-}
-
-// The two halves of a product, host side: the filter into operand order (forward B[k][n] = w[n][k]; input gradient
-// B[k = n_w][n = k_w] = w[k][n]: k_conv_prep, one tap), and k_linear from an operand copy that exists.  linear_impl does both per
-// call; the layered rollout step (aurppo_mlp_layered_prep_f32 / aurppo_linear_prepared) builds the copies once per rollout.
-static int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s) {
+// ---- the kernels linear.hip runs too, as host functions (common.h).  linear_prep: the operand copy of a linear product's (N_w, K_w)
+// weight (forward B[k][n] = w[n][k]; input gradient B[k = n_w][n = k_w] = w[k][n]: k_conv_prep with one tap).
+int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s) {
     const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
     if (K % 16 != 0) {               // (mode 0 only: the callers hold mode 1's inner dimension to 16)
         hipLaunchKernelGGL(k_linear_prep_tail, dim3(64), dim3(256), 0, s, w, N_w, K_w, (K_w + 15) / 16 * 16, wop);
@@ -674,105 +429,11 @@ static int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned shor
     AURPPO_LAUNCH_CHECK("k_conv_prep");
     return AURPPO_OK;
 }
-
-static int linear_launch(const float* x, const unsigned short* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                         hipStream_t s, const int32_t* rows, const float* h) {
-    LinArgs a;
-    a.x = x; a.wop = wop; a.y = y; a.M = M; a.K = K; a.N = N;
-    a.bias = bias; a.act = act; a.rows = rows; a.h = h;
-    const long long n_mb = (M + 32 * 4 * kMB - 1) / (32 * 4 * kMB);
-    const int nblk = (N + 31) / 32;
-    const int NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    const int n_ng = (nblk + NB - 1) / NB;
-    AURPPO_REQUIRE(n_mb * n_ng < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_f32: grid too large");
-    a.n_mb = (int)n_mb;
-    const dim3 g((unsigned)(n_mb * n_ng)), blk(kConvThreads);
-    if (K % 16 != 0) {
-        AURPPO_REQUIRE(!h, AURPPO_ESHAPE, "aurppo_linear_f32: the input gradient's inner dimension %d (a multiple of 16)", K);
-        if (rows) {
-            if (NB == 4) hipLaunchKernelGGL((k_linear_tail<4, true>), g, blk, 0, s, a);
-            else if (NB == 2) hipLaunchKernelGGL((k_linear_tail<2, true>), g, blk, 0, s, a);
-            else hipLaunchKernelGGL((k_linear_tail<1, true>), g, blk, 0, s, a);
-        } else if (NB == 4) hipLaunchKernelGGL((k_linear_tail<4, false>), g, blk, 0, s, a);
-        else if (NB == 2) hipLaunchKernelGGL((k_linear_tail<2, false>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_linear_tail<1, false>), g, blk, 0, s, a);
-    } else if (h) {
-        if (NB == 4) hipLaunchKernelGGL((k_linear<4, false, true>), g, blk, 0, s, a);
-        else if (NB == 2) hipLaunchKernelGGL((k_linear<2, false, true>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_linear<1, false, true>), g, blk, 0, s, a);
-    } else if (rows) {
-        if (NB == 4) hipLaunchKernelGGL((k_linear<4, true, false>), g, blk, 0, s, a);
-        else if (NB == 2) hipLaunchKernelGGL((k_linear<2, true, false>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL((k_linear<1, true, false>), g, blk, 0, s, a);
-    } else if (NB == 4) hipLaunchKernelGGL(k_linear<4>, g, blk, 0, s, a);
-    else if (NB == 2) hipLaunchKernelGGL(k_linear<2>, g, blk, 0, s, a);
-    else hipLaunchKernelGGL(k_linear<1>, g, blk, 0, s, a);
-    AURPPO_LAUNCH_CHECK("k_linear");
-    return AURPPO_OK;
-}
-
-static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream, const int32_t* rows, const float* h) {
-    AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
-    AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
-    const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && (mode == 0 || K % 16 == 0), AURPPO_ESHAPE,
-                   "aurppo_linear_f32: M=%lld, inner dimension %d (mode 1: a multiple of 16), %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL, "aurppo_linear_f32: x / workspace not 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    const int rc = linear_prep(w, K_w, N_w, mode, wop, s);
-    if (rc != AURPPO_OK) return rc;
-    return linear_launch(x, wop, bias, act, y, M, K, N, s, rows, h);
-}
-
-// ---- prepared weights for the layered rollout step (head.hip: aurppo_mlp_layered_act_f32).  The parameters stand still for the T
-// steps of a rollout, so the operand-order copies of the 2 L hidden-layer matrices are built once, into a caller-owned buffer:
-// [net][layer], each copy aurppo_linear_wop_bytes(its K, hidden) bytes.
-// Bytes of one forward operand copy: the blocks k_conv_prep writes and one group of slack, as a workgroup reads whole groups.
-size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + kNBW) * (size_t)((K + 15) / 16) * 3 * 1024; }
-
-// y (M, N) = act(x (M, K) . B + bias) from the operand copy `wop` of a (N, K) weight: linear_impl without its k_conv_prep launch.
-int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                           void* stream) {
-    AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_prepared: null pointer");
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_prepared: x / operand copy not 16-byte aligned");
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_prepared: act %d", act);
-    return linear_launch(x, reinterpret_cast<const unsigned short*>(wop), bias, act, y, M, K, N, (hipStream_t)stream, nullptr, nullptr);
-}
-
-static bool layered_hidden_ok(int D, int hidden, int num_layers) {
-    return D > 0 && hidden >= 32 && hidden <= 1024 && hidden % 32 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers;
-}
-
-extern "C" size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers) {
-    if (!layered_hidden_ok(D, hidden, num_layers)) return 0;
-    return 2 * (aurppo_linear_wop_bytes(D, hidden) + (size_t)(num_layers - 1) * aurppo_linear_wop_bytes(hidden, hidden));
-}
-
-extern "C" int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers,
-                                           void* wop, void* stream) {
-    AURPPO_REQUIRE(params && offsets && wop, AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: null pointer");
-    AURPPO_REQUIRE(layered_hidden_ok(D, hidden, num_layers), AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_prep_f32: D=%d (1 or more), hidden=%d (a multiple of 32, 32..1024), %d layers (1..%d)", D, hidden,
-                   num_layers, kLayeredMaxLayers);
-    AURPPO_REQUIRE(aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: operand buffer not 16-byte aligned");
-    const int per = 2 * (num_layers + 1);
-    for (int net = 0; net < 2; ++net)
-        for (int l = 0; l < num_layers; ++l) {
-            const int o = offsets[net * per + 2 * l];
-            AURPPO_REQUIRE(o >= 0 && (long long)o + (long long)hidden * (l ? hidden : D) <= (long long)n_params, AURPPO_EINVAL,
-                           "aurppo_mlp_layered_prep_f32: layout offset %d (%d) outside the bucket of %d", net * per + 2 * l, o, n_params);
-        }
-    char* at = reinterpret_cast<char*>(wop);
-    for (int net = 0; net < 2; ++net)
-        for (int l = 0; l < num_layers; ++l) {
-            const int K = l ? hidden : D;
-            const int rc = linear_prep(params + offsets[net * per + 2 * l], K, hidden, 0, reinterpret_cast<unsigned short*>(at), (hipStream_t)stream);
-            if (rc != AURPPO_OK) return rc;
-            at += aurppo_linear_wop_bytes(K, hidden);
-        }
+int fold_slices_launch(const float* part, int S, long long n, float* out, const double* bpart, int N, float* db, hipStream_t s) {
+    const long long n_fold = (n + 255) / 256;
+    if (db) hipLaunchKernelGGL(k_fold_slices_bias, dim3((unsigned)(n_fold + (N + 255) / 256)), dim3(256), 0, s, part, S, n, out, bpart, N, db);
+    else hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)n_fold), dim3(256), 0, s, part, S, n, out);
+    AURPPO_LAUNCH_CHECK("k_fold_slices");
     return AURPPO_OK;
 }
 
@@ -781,7 +442,7 @@ extern "C" int aurppo_mlp_layered_prep_f32(const float* params, const int* offse
 // The slice count for `tiles` output tiles: the weight-gradient kernels hold two workgroups per CU (LDS), so the grid is dealt in
 // rounds of 2 x 256 workgroups and a round with two workgroups in it costs what a full one does (1026 workgroups measured 611 us
 // where 504 take 410): the S <= most that wastes the least of its last round, the smallest such S (fewer partial filters to fold).
-static int slices_for(long long tiles, long long most) {
+int slices_for(long long tiles, long long most) {
     constexpr long long kSlots = 2 * 256;
     if (most < 1) most = 1;
     if (most > 4096) most = 4096;
@@ -797,75 +458,56 @@ static int slices_for(long long tiles, long long most) {
     }
     return (int)best;
 }
-static int linear_wgrad_slices(long long M, int N, int K) {
-    const long long tiles = (long long)((N + 127) / 128) * ((K + 127) / 128);
-    return slices_for(tiles, (M + 255) / 256);                // at least 8 chunks of 32 rows per slice
+
+extern "C" size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm) {
+    const size_t nblk = (size_t)((cout_gemm + 31) / 32 + kNBW);      // (+ one group of slack: a wave reads whole groups)
+    return nblk * 9 * (size_t)((cin_gemm + 15) / 16) * 3 * 1024 + 64;      // (whole k-steps: a linear product's K may be ragged)
 }
-extern "C" size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    return (size_t)linear_wgrad_slices(M, N, K) * (size_t)N * (size_t)K * sizeof(float) + 64;
-}
-// bytes of the (S, N, K) partial products, rounded to where the BIAS builds' (S, N) fp64 partial column sums begin
-static size_t linear_wgrad_part_bytes(int S, int N, int K) { return ((size_t)S * (size_t)N * (size_t)K * sizeof(float) + 15) & ~(size_t)15; }
-// The weight-gradient launches; db != nullptr: the BIAS builds and their fold (rows or K a multiple of 4: no plain BIAS tail build)
-static int linear_wgrad_impl(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N, int K,
-                             void* ws, void* stream) {
-    AURPPO_REQUIRE(dy && x && dw && ws, AURPPO_EINVAL, "aurppo_linear_wgrad_f32: null pointer");
-    AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: M=%lld N=%d (a multiple of 4) K=%d", M, N, K);
-    AURPPO_REQUIRE(aligned_to(dy, 16) && aligned_to(x, 16) && aligned_to(ws, 16), AURPPO_EINVAL,
-                   "aurppo_linear_wgrad_f32: operands / workspace not 16-byte aligned");
-    const int S0 = linear_wgrad_slices(M, N, K);
-    WgradArgs a;
-    a.dy = dy; a.x = x; a.part = reinterpret_cast<float*>(ws); a.M = M; a.N = N; a.K = K; a.rows = rows;
-    a.bpart = db ? reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + linear_wgrad_part_bytes(S0, N, K)) : nullptr;
-    const long long rps = ((M + S0 - 1) / S0 + 31) / 32 * 32;           // whole 32-row chunks per slice
-    const long long S = (M + rps - 1) / rps;
-    AURPPO_REQUIRE(S >= 1 && S <= S0 && rps < (1ll << 30), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: slice size");
-    a.rows_per_slice = (int)rps;
-    a.n_tiles_n = (N + 127) / 128;
-    a.n_tiles_k = (K + 127) / 128;
-    const long long grid = (long long)a.n_tiles_n * a.n_tiles_k * S;
-    AURPPO_REQUIRE(grid < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: grid too large");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 g((unsigned)grid), blk(kConvThreads);
-    if (db) {
-        if (K % 4 != 0) hipLaunchKernelGGL((k_linear_wgrad_tail<true, true>), g, blk, 0, st, a);
-        else if (rows) hipLaunchKernelGGL((k_linear_wgrad<true, true>), g, blk, 0, st, a);
-        else hipLaunchKernelGGL((k_linear_wgrad<false, true>), g, blk, 0, st, a);
-    } else if (K % 4 != 0) {
-        if (rows) hipLaunchKernelGGL(k_linear_wgrad_tail<true>, g, blk, 0, st, a);
-        else hipLaunchKernelGGL(k_linear_wgrad_tail<false>, g, blk, 0, st, a);
-    } else if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, g, blk, 0, st, a);
-    else hipLaunchKernelGGL(k_linear_wgrad<false>, g, blk, 0, st, a);
-    AURPPO_LAUNCH_CHECK("k_linear_wgrad");
-    const long long n = (long long)N * K, n_fold = (n + 255) / 256;
-    if (db) hipLaunchKernelGGL(k_fold_slices_bias, dim3((unsigned)(n_fold + (N + 255) / 256)), dim3(256), 0, st, a.part, (int)S, n, dw, a.bpart, N, db);
-    else hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)n_fold), dim3(256), 0, st, a.part, (int)S, n, dw);
-    AURPPO_LAUNCH_CHECK("k_fold_slices");
+
+// mode 0: z = conv2d(x, w, padding = pad)                      x (B, Ci, H, W), w (Co, Ci, 3, 3), z (B, Co, H + 2 pad - 2, ...)
+// mode 1: z = d conv2d / d input applied to x:  x (B, Co, Ho, Wo) is the output gradient, z (B, Ci, Ho + 2 - 2 pad, ...) the
+//         input gradient, w the SAME (Co, Ci, 3, 3) filter, pad the FORWARD padding.
+extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w, int Co_w, int H, int W, int pad,
+                                  int mode, void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_conv3x3_f32: mode %d", mode);
+    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_f32: pad=%d (0..2)", pad);
+    const int cin = mode == 0 ? Ci_w : Co_w, cout = mode == 0 ? Co_w : Ci_w, p = mode == 0 ? pad : 2 - pad;
+    const int Ho = H + 2 * p - 2, Wo = W + 2 * p - 2;
+    ConvPlan pl;
+    if (const int rc = conv_plan("aurppo_conv3x3_f32", x, w, z, wop_ws, B, cin, cout, H, W, p, Ho, Wo, (long long)B * Ho * Wo, &pl)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co_w, Ci_w, cin, cout, mode, reinterpret_cast<unsigned short*>(wop_ws), 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
+    bf3_with_nb(pl.g.NB, [&](auto nb) {
+        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true>), g, blk, 0, s, pl.p.c);
+        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false>), g, blk, 0, s, pl.p.c);
+    });
+    AURPPO_LAUNCH_CHECK("k_conv3x3");
     return AURPPO_OK;
 }
-// dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N a multiple of 4, any K >= 1 -- no multiple of 4:
-// the tail builds; 16-byte aligned operands)
-extern "C" int aurppo_linear_wgrad_f32(const float* dy, const float* x, float* dw, long long M, int N, int K, void* ws, void* stream) {
-    return linear_wgrad_impl(dy, x, nullptr, dw, nullptr, M, N, K, ws, stream);
-}
-// the same with row m of the product reading x row rows[m] (rows == NULL: the plain call); same slice rule, same workspace
-extern "C" int aurppo_linear_wgrad_rows_f32(const float* dy, const float* x, const int32_t* rows, float* dw, long long M, int N, int K,
-                                            void* ws, void* stream) {
-    return linear_wgrad_impl(dy, x, rows, dw, nullptr, M, N, K, ws, stream);
-}
-// ... and with the layer's bias gradient db (N,) = the column sums of dy, taken in the product's kernel: the slices' partial sums
-// (fp64) lie behind the partial products in the workspace
-extern "C" size_t aurppo_linear_wgrad_bias_ws_bytes(long long M, int N, int K) {
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    const int S = linear_wgrad_slices(M, N, K);
-    return linear_wgrad_part_bytes(S, N, K) + (size_t)S * (size_t)N * sizeof(double) + 64;
-}
-extern "C" int aurppo_linear_wgrad_bias_f32(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N,
-                                            int K, void* ws, void* stream) {
-    AURPPO_REQUIRE(db && aligned_to(db, 4), AURPPO_EINVAL, "aurppo_linear_wgrad_bias_f32: db null or not 4-byte aligned");
-    AURPPO_REQUIRE(rows || K % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_bias_f32: K=%d (a multiple of 4 without rows)", K);
-    return linear_wgrad_impl(dy, x, rows, dw, db, M, N, K, ws, stream);
+
+// K11p: y, mask = max_pool2d(relu(conv2d(x, w, padding = pad) + bias[c]), 2) with K9's semantics; x (B, Ci, H, W), w (Co, Ci, 3, 3),
+// y / mask (B, Co, (H + 2 pad - 2) >> 1, (W + 2 pad - 2) >> 1).  Refuses what mode 0 above refuses, and a map without a whole window.
+extern "C" int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci,
+                                       int Co, int H, int W, int pad, void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(mask, AURPPO_EINVAL, "aurppo_conv3x3_pool_f32: null pointer");
+    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: pad=%d (0..2)", pad);
+    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2, Hp = Ho >> 1, Wp = Wo >> 1;
+    ConvPlan pl;
+    pl.p.bias = bias; pl.p.mask = mask;
+    if (const int rc = conv_plan("aurppo_conv3x3_pool_f32", x, w, y, wop_ws, B, Ci, Co, H, W, pad, Hp, Wp, 4ll * B * Hp * Wp, &pl)) return rc;
+    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
+    bf3_with_nb(pl.g.NB, [&](auto nb) {
+        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true, true>), g, blk, 0, s, pl.p);
+        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false, true>), g, blk, 0, s, pl.p);
+    });
+    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool)");
+    return AURPPO_OK;
 }
 
 // K12: dw (Co, Ci, 3, 3) = the gradient of conv2d(x (B, Ci, H, W), w, padding = pad) with respect to w, given the output gradient
@@ -924,16 +566,10 @@ extern "C" int aurppo_conv3x3_wgrad_f32(const float* dy, const float* x, float* 
     const dim3 g((unsigned)((long long)p.n_tiles_m * p.n_tiles_n * p.S)), blk(kConvThreads);
     // a quad of output pixels stays inside one row of its image, whose 16-byte pieces are aligned
     const bool quad = a.Wo % 4 == 0 && W >= 4 && pad <= 1 && aligned_to(dy, 16);
-    if (p.WM == 2) {
-        if (quad) hipLaunchKernelGGL((k_conv3x3_wgrad<2, true>), g, blk, 0, st, a);
-        else hipLaunchKernelGGL((k_conv3x3_wgrad<2, false>), g, blk, 0, st, a);
-    } else {
-        if (quad) hipLaunchKernelGGL((k_conv3x3_wgrad<1, true>), g, blk, 0, st, a);
-        else hipLaunchKernelGGL((k_conv3x3_wgrad<1, false>), g, blk, 0, st, a);
-    }
+    if (p.WM == 2 && quad) hipLaunchKernelGGL((k_conv3x3_wgrad<2, true>), g, blk, 0, st, a);
+    else if (p.WM == 2) hipLaunchKernelGGL((k_conv3x3_wgrad<2, false>), g, blk, 0, st, a);
+    else if (quad) hipLaunchKernelGGL((k_conv3x3_wgrad<1, true>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((k_conv3x3_wgrad<1, false>), g, blk, 0, st, a);
     AURPPO_LAUNCH_CHECK("k_conv3x3_wgrad");
-    const long long n = (long long)Co * a.NK;
-    hipLaunchKernelGGL(k_fold_slices, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.part, p.S, n, dw);
-    AURPPO_LAUNCH_CHECK("k_fold_slices");
-    return AURPPO_OK;
+    return fold_slices_launch(a.part, p.S, (long long)Co * a.NK, dw, nullptr, 0, nullptr, st);
 }

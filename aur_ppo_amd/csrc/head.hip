@@ -1,7 +1,7 @@
 // K13: the heads of the MLP actor-critic, the action distribution, the PPO loss and their backward pass in one kernel -- the
 // part of a minibatch step (src/ppo.py:219-266) that sits between the last hidden layer of src/nets/nets.py:19-53 and the
 // loss, for the policies the fused steps K7 / K7w do not cover (hidden_dim > 128 or more than 128 state floats), whose
-// hidden layers run a layer at a time on k_linear / k_linear_wgrad (conv.hip).  It replaces, per minibatch: the two head
+// hidden layers run a layer at a time on k_linear / k_linear_wgrad (linear.hip).  It replaces, per minibatch: the two head
 // GEMMs (A and 1 columns), the Normal / Categorical log-prob and entropy (a dozen element-wise kernels), K4 + K5, and
 // autograd's backward of all of them down to the pre-activation of the last hidden layer.
 //
@@ -20,9 +20,7 @@
 // K14 (k_head_act, below K13's host helpers) is the forward half alone for the rollout step: same layout, same head expressions in the
 // same order, then sampling -- so the log-prob it stores is the one K13 forms from the stored action.  One dispatcher by threads per
 // row launches either kernel (launch_k_head_ppo / launch_k_head_act), one function checks a layout's bounds, one fills K14's arguments.
-// aurppo_mlp_layered_act_f32 at the end of the file is the whole rollout step: k_linear from prepared operand copies (conv.hip), then K14;
-// aurppo_mlp_layered_step_f32 / aurppo_mlp_layered_minibatch_f32 behind it are the whole update step: the products and weight
-// gradients of conv.hip around K13, from one workspace (host code only: no kernel of its own).
+// The layered rollout and update steps that run these kernels behind linear.hip's products are host code of their own: layered.hip.
 #include "mlp_common.h"
 
 namespace {
@@ -455,7 +453,6 @@ HeadWs head_carve(void* workspace, int M, int H, int A) {
     w.bytes = c.bytes;
     return w;
 }
-bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
 
 // ---- K14: the forward-only sibling of k_head_ppo for the rollout step (src/ppo.py:103-108: policy.evaluate(next_obs) under no_grad,
 // then the three buffer row stores) of the policies whose hidden layers run on k_linear.  K13's thread layout, LDS weights, butterfly
@@ -645,7 +642,11 @@ int head_layout_check(const int* layout, const long long* need, int count, int n
     return AURPPO_OK;
 }
 
-// K14 on checked operands; lay = {actor head w, b; critic head w, b; actor_logstd}
+}  // namespace
+
+bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
+
+// K14 on checked operands; lay = {actor head w, b; critic head w, b; actor_logstd}  (this and head_shape_ok: also layered.hip's)
 int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,
                     const int* lay, float* actions, float* logp, float* value, hipStream_t s) {
     HeadActArgs a;
@@ -657,50 +658,6 @@ int head_act_launch(const float* hA, const float* hC, const float* noise, int N,
     a.n_iter = head_n_iter(N, H, grid);
     return launch_k_head_act(a, grid, s);
 }
-
-size_t layered_act_plane_bytes(int N, int hidden) { return ((size_t)N * hidden * sizeof(float) + 63) & ~(size_t)63; }
-
-// the layered layout's 4 (L + 1) + 1 offsets, each with what lies at it inside the bucket
-int layered_offsets_check(const int* offsets, int D, int A, int continuous, int hidden, int L, int n_params, const char* who) {
-    const int per = 2 * (L + 1), n_off = 2 * per + 1;
-    for (int i = 0; i < n_off; ++i) {
-        const int net = i / per, j = i % per, l = j / 2;
-        const int out = i == 2 * per ? 0 : (l < L ? hidden : (net ? 1 : A));
-        long long need;
-        if (i == 2 * per) need = continuous ? A : 0;
-        else if (j & 1) need = out;
-        else need = (long long)out * (l == 0 ? D : hidden);
-        AURPPO_REQUIRE(offsets[i] >= 0 && (long long)offsets[i] + need <= (long long)n_params, AURPPO_EINVAL,
-                       "%s: layout offset %d (%d) outside the bucket of %d", who, i, offsets[i], n_params);
-    }
-    return AURPPO_OK;
-}
-
-// The layered update step's one workspace: per net and hidden layer an (M, hidden) activation array (the gradient with respect to the
-// layer's pre-activation takes its place on the way down), the operand copy of the product in flight, the weight-gradient slices
-// (with the bias builds' partial column sums), K13's workspace, and clip + Adam's for the minibatch call.
-struct LayeredStepWs {
-    float* act;              // [net][layer] planes of `plane` bytes
-    size_t plane;
-    void *wop, *wgrad, *head, *clip;
-    size_t bytes;
-};
-LayeredStepWs layered_step_carve(void* workspace, int M, int D, int A, int hidden, int L) {
-    aurppo_mlp::WsCarver c(workspace);
-    LayeredStepWs w;
-    w.plane = layered_act_plane_bytes(M, hidden);
-    w.act = c.take<float>((size_t)2 * L * w.plane, 64);
-    w.wop = c.take<char>(aurppo_conv3x3_wop_bytes(D > hidden ? D : hidden, hidden), 64);
-    size_t wg = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, D);
-    if (aurppo_linear_wgrad_bias_ws_bytes(M, hidden, hidden) > wg) wg = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, hidden);
-    w.wgrad = c.take<char>(wg, 64);
-    w.head = c.take<char>(aurppo_head_ppo_workspace_bytes(M, hidden, A), 64);
-    w.clip = c.take<char>(aurppo_clip_workspace_bytes(0), 64);
-    w.bytes = c.bytes;
-    return w;
-}
-
-}  // namespace
 
 extern "C" size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A) {
     if (M <= 0 || !head_shape_ok(H, A, 1)) return 0;
@@ -765,136 +722,4 @@ extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float
     const long long need[5] = {(long long)A * H, A, H, 1, continuous ? A : 0};
     if (const int rc = head_layout_check(layout_h, need, 5, n_params, "aurppo_head_act_f32")) return rc;
     return head_act_launch(hA, hC, noise, N, H, A, continuous, params, layout_h, actions, logp, value, (hipStream_t)stream);
-}
-
-// ---- the layered rollout step: per net, the hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand
-// copies (conv.hip: aurppo_mlp_layered_prep_f32), then K14.  2 L + 1 launches; the value alone: the critic only, L + 1.
-extern "C" size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden) {
-    if (N <= 0 || hidden <= 0) return 0;
-    return 4 * layered_act_plane_bytes(N, hidden);      // two activation planes per net, written in turn
-}
-
-extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
-                                          int num_layers, const float* params, const int* offsets, int n_params, float* actions,
-                                          float* logp, float* value, const void* wop, void* workspace, void* stream) {
-    AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL,
-                   "aurppo_mlp_layered_act_f32: null pointer");
-    AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_act_f32: N=%d, D=%d, %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
-    AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_act_f32: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", hidden, A);
-    AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
-                   "aurppo_mlp_layered_act_f32: obs / operand copies not 16-byte / workspace not 64-byte aligned");
-    AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
-                   AURPPO_EINVAL, "aurppo_mlp_layered_act_f32: noise / outputs not 4-byte aligned");
-    const int L = num_layers, per = 2 * (L + 1);
-    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, "aurppo_mlp_layered_act_f32")) return rc;
-    const size_t plane = layered_act_plane_bytes(N, hidden);
-    const char* const wbase = reinterpret_cast<const char*>(wop);
-    const size_t net_wop = aurppo_linear_wop_bytes(D, hidden) + (size_t)(L - 1) * aurppo_linear_wop_bytes(hidden, hidden);
-    const float* last[2] = {nullptr, nullptr};
-    for (int net = noise ? 0 : 1; net < 2; ++net) {
-        const int* o = offsets + net * per;
-        const char* w = wbase + net * net_wop;
-        const float* x = obs;
-        for (int l = 0; l < L; ++l) {
-            const int K = l ? hidden : D;
-            float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane);
-            const int rc = aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream);
-            if (rc != AURPPO_OK) return rc;
-            w += aurppo_linear_wop_bytes(K, hidden);
-            x = y;
-        }
-        last[net] = x;
-    }
-    const int lay[5] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per]};
-    return head_act_launch(last[0], last[1], noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
-}
-
-// ---- the layered update step: mlp_ppo_step's contract on the same products.  Per net: layer 0 through the index (k_linear, bias + tanh
-// in the epilogue), layers 1 .. L - 1; K13 (statistics, the kernel, its fold); then per net from the last layer down the weight gradient
-// (k_linear_wgrad + fold) and the input gradient with tanh' (k_linear).  The weight gradient of a layer below the last runs the BIAS
-// build, which leaves the layer's bias gradient (K13 writes the last layers').  Per product two launches (operand copy + k_linear,
-// or k_linear_wgrad + fold): 2 (2 L) + 3 + 2 (2 L + 2 (L - 1)) = 12 L - 1 launches, no allocation, no host synchronisation.
-namespace {
-int layered_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A, int continuous,
-                      int hidden, int num_layers, const float* params, const int* offsets, int n_params, float* grads, double clip,
-                      double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace, void* stream,
-                      const char* who) {
-    AURPPO_REQUIRE(obs && rec && idx && params && offsets && grads && out_scalars && workspace, AURPPO_EINVAL, "%s: null pointer", who);
-    AURPPO_REQUIRE(M > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE, "%s: M=%d, D=%d, %d layers (1..%d)",
-                   who, M, D, num_layers, kLayeredMaxLayers);
-    AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
-                   "%s: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", who, hidden, A);
-    AURPPO_REQUIRE(actions || (continuous ? A : 1) <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (A=%d)", who, A);
-    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: vloss_mode %d", who, vloss_mode);
-    AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(rec, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
-                   "%s: obs / rec not 16-byte / workspace not 64-byte aligned", who);
-    const int L = num_layers, per = 2 * (L + 1);
-    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, who)) return rc;
-    const LayeredStepWs w = layered_step_carve(workspace, M, D, A, hidden, L);
-    auto h = [&](int net, int l) { return reinterpret_cast<float*>(reinterpret_cast<char*>(w.act) + (size_t)(net * L + l) * w.plane); };
-    for (int net = 0; net < 2; ++net) {
-        const int* o = offsets + net * per;
-        if (const int rc = aurppo_linear_rows_bias_act_f32(obs, idx, params + o[0], params + o[1], h(net, 0), M, D, hidden, 1, w.wop, stream))
-            return rc;
-        for (int l = 1; l < L; ++l)
-            if (const int rc = aurppo_linear_bias_act_f32(h(net, l - 1), params + o[2 * l], params + o[2 * l + 1], h(net, l), M, hidden, hidden,
-                                                          1, w.wop, stream))
-                return rc;
-    }
-    const int lay[7] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per],
-                        offsets[2 * L - 1], offsets[per + 2 * L - 1]};
-    if (const int rc = aurppo_head_ppo_f32(h(0, L - 1), h(1, L - 1), h(0, L - 1), h(1, L - 1), actions, rec, idx, M, hidden, A, continuous,
-                                           params, lay, n_params, grads, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, w.head,
-                                           stream))
-        return rc;
-    for (int net = 0; net < 2; ++net) {
-        const int* o = offsets + net * per;          // h(net, L - 1) now holds gz of the last layer; the lower layers follow in place
-        for (int l = L - 1; l > 0; --l) {
-            const int rc = l == L - 1 ? aurppo_linear_wgrad_f32(h(net, l), h(net, l - 1), grads + o[2 * l], M, hidden, hidden, w.wgrad, stream)
-                                      : aurppo_linear_wgrad_bias_f32(h(net, l), h(net, l - 1), nullptr, grads + o[2 * l], grads + o[2 * l + 1],
-                                                                     M, hidden, hidden, w.wgrad, stream);
-            if (rc != AURPPO_OK) return rc;
-            if (const int rc2 = aurppo_linear_dx_tanh_f32(h(net, l), params + o[2 * l], h(net, l - 1), h(net, l - 1), M, hidden, hidden, w.wop,
-                                                          stream))
-                return rc2;
-        }
-        const int rc = L == 1 ? aurppo_linear_wgrad_rows_f32(h(net, 0), obs, idx, grads + o[0], M, hidden, D, w.wgrad, stream)
-                              : aurppo_linear_wgrad_bias_f32(h(net, 0), obs, idx, grads + o[0], grads + o[1], M, hidden, D, w.wgrad, stream);
-        if (rc != AURPPO_OK) return rc;
-    }
-    return AURPPO_OK;
-}
-}  // namespace
-
-extern "C" size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {
-    if (M <= 0 || D <= 0 || num_layers < 1 || num_layers > kLayeredMaxLayers || !head_shape_ok(hidden, A, 1)) return 0;
-    return layered_step_carve(nullptr, M, D, A, hidden, num_layers).bytes;
-}
-
-extern "C" int aurppo_mlp_layered_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
-                                           int continuous, int hidden, int num_layers, const float* params, const int* offsets,
-                                           int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
-                                           int vloss_mode, float* out_scalars, void* workspace, void* stream) {
-    return layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads, clip, ent_coef,
-                             vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, "aurppo_mlp_layered_step_f32");
-}
-
-// The step, then clip + Adam (aurppo_clip_adam_f32's two launches) over [0, n_params) on the same stream.
-extern "C" int aurppo_mlp_layered_minibatch_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
-                                                int A, int continuous, int hidden, int num_layers, float* params, const int* offsets,
-                                                int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
-                                                int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
-                                                const float* lr_dev, float* step_dev, double beta1, double beta2, double eps,
-                                                float* out_norm, void* workspace, void* stream) {
-    AURPPO_REQUIRE(exp_avg && exp_avg_sq && lr_dev && step_dev && out_norm, AURPPO_EINVAL,
-                   "aurppo_mlp_layered_minibatch_f32: null optimizer pointer");
-    if (const int rc = layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads,
-                                         clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream,
-                                         "aurppo_mlp_layered_minibatch_f32"))
-        return rc;
-    const LayeredStepWs w = layered_step_carve(workspace, M, D, A, hidden, num_layers);
-    return aurppo_clip_adam_f32(params, grads, exp_avg, exp_avg_sq, n_params, n_params, max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm,
-                                w.clip, stream);
 }

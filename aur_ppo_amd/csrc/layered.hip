@@ -1,0 +1,213 @@
+// The layered steps for the MLP policies the fused K7 / K7w steps do not cover (hidden_dim > 128 or more than 128 state floats): host
+// code only, no kernel of its own.  The hidden layers run a layer at a time on linear.hip's products, the heads on head.hip's K13 (the
+// update step, aurppo_mlp_layered_step_f32 / _minibatch_f32) and K14 (the rollout step, aurppo_mlp_layered_prep_f32 + _act_f32).
+#include "mlp_common.h"
+
+namespace {
+
+bool layered_hidden_ok(int D, int hidden, int num_layers) {
+    return D > 0 && hidden >= 32 && hidden <= 1024 && hidden % 32 == 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers;
+}
+size_t layered_act_plane_bytes(int N, int hidden) { return ((size_t)N * hidden * sizeof(float) + 63) & ~(size_t)63; }
+
+// the layered layout's 4 (L + 1) + 1 offsets, each with what lies at it inside the bucket
+int layered_offsets_check(const int* offsets, int D, int A, int continuous, int hidden, int L, int n_params, const char* who) {
+    const int per = 2 * (L + 1), n_off = 2 * per + 1;
+    for (int i = 0; i < n_off; ++i) {
+        const int net = i / per, j = i % per, l = j / 2;
+        const int out = i == 2 * per ? 0 : (l < L ? hidden : (net ? 1 : A));
+        long long need;
+        if (i == 2 * per) need = continuous ? A : 0;
+        else if (j & 1) need = out;
+        else need = (long long)out * (l == 0 ? D : hidden);
+        AURPPO_REQUIRE(offsets[i] >= 0 && (long long)offsets[i] + need <= (long long)n_params, AURPPO_EINVAL,
+                       "%s: layout offset %d (%d) outside the bucket of %d", who, i, offsets[i], n_params);
+    }
+    return AURPPO_OK;
+}
+
+// The layered update step's one workspace: per net and hidden layer an (M, hidden) activation array (the gradient with respect to the
+// layer's pre-activation takes its place on the way down), the operand copy of the product in flight, the weight-gradient slices
+// (with the bias builds' partial column sums), K13's workspace, and clip + Adam's for the minibatch call.
+struct LayeredStepWs {
+    float* act;              // [net][layer] planes of `plane` bytes
+    size_t plane;
+    void *wop, *wgrad, *head, *clip;
+    size_t bytes;
+};
+LayeredStepWs layered_step_carve(void* workspace, int M, int D, int A, int hidden, int L) {
+    aurppo_mlp::WsCarver c(workspace);
+    LayeredStepWs w;
+    w.plane = layered_act_plane_bytes(M, hidden);
+    w.act = c.take<float>((size_t)2 * L * w.plane, 64);
+    w.wop = c.take<char>(aurppo_conv3x3_wop_bytes(D > hidden ? D : hidden, hidden), 64);
+    const size_t wg0 = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, D), wg = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, hidden);
+    w.wgrad = c.take<char>(wg0 > wg ? wg0 : wg, 64);
+    w.head = c.take<char>(aurppo_head_ppo_workspace_bytes(M, hidden, A), 64);
+    w.clip = c.take<char>(aurppo_clip_workspace_bytes(0), 64);
+    w.bytes = c.bytes;
+    return w;
+}
+
+// ---- the layered update step: mlp_ppo_step's contract on the same products.  Per net: layer 0 through the index (k_linear, bias + tanh
+// in the epilogue), layers 1 .. L - 1; K13 (statistics, the kernel, its fold); then per net from the last layer down the weight gradient
+// (k_linear_wgrad + fold) and the input gradient with tanh' (k_linear).  The weight gradient of a layer below the last runs the BIAS
+// build, which leaves the layer's bias gradient (K13 writes the last layers').  Per product two launches (operand copy + k_linear,
+// or k_linear_wgrad + fold): 2 (2 L) + 3 + 2 (2 L + 2 (L - 1)) = 12 L - 1 launches, no allocation, no host synchronisation.
+int layered_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A, int continuous,
+                      int hidden, int num_layers, const float* params, const int* offsets, int n_params, float* grads, double clip,
+                      double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace, void* stream,
+                      const char* who) {
+    AURPPO_REQUIRE(obs && rec && idx && params && offsets && grads && out_scalars && workspace, AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(M > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE, "%s: M=%d, D=%d, %d layers (1..%d)",
+                   who, M, D, num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
+                   "%s: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", who, hidden, A);
+    AURPPO_REQUIRE(actions || (continuous ? A : 1) <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (A=%d)", who, A);
+    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: vloss_mode %d", who, vloss_mode);
+    AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(rec, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
+                   "%s: obs / rec not 16-byte / workspace not 64-byte aligned", who);
+    const int L = num_layers, per = 2 * (L + 1);
+    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, who)) return rc;
+    const LayeredStepWs w = layered_step_carve(workspace, M, D, A, hidden, L);
+    auto h = [&](int net, int l) { return reinterpret_cast<float*>(reinterpret_cast<char*>(w.act) + (size_t)(net * L + l) * w.plane); };
+    for (int net = 0; net < 2; ++net) {
+        const int* o = offsets + net * per;
+        if (const int rc = aurppo_linear_rows_bias_act_f32(obs, idx, params + o[0], params + o[1], h(net, 0), M, D, hidden, 1, w.wop, stream))
+            return rc;
+        for (int l = 1; l < L; ++l)
+            if (const int rc = aurppo_linear_bias_act_f32(h(net, l - 1), params + o[2 * l], params + o[2 * l + 1], h(net, l), M, hidden, hidden,
+                                                          1, w.wop, stream))
+                return rc;
+    }
+    const int lay[7] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per],
+                        offsets[2 * L - 1], offsets[per + 2 * L - 1]};
+    if (const int rc = aurppo_head_ppo_f32(h(0, L - 1), h(1, L - 1), h(0, L - 1), h(1, L - 1), actions, rec, idx, M, hidden, A, continuous,
+                                           params, lay, n_params, grads, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, w.head,
+                                           stream))
+        return rc;
+    for (int net = 0; net < 2; ++net) {
+        const int* o = offsets + net * per;          // h(net, L - 1) now holds gz of the last layer; the lower layers follow in place
+        for (int l = L - 1; l > 0; --l) {
+            const int rc = l == L - 1 ? aurppo_linear_wgrad_f32(h(net, l), h(net, l - 1), grads + o[2 * l], M, hidden, hidden, w.wgrad, stream)
+                                      : aurppo_linear_wgrad_bias_f32(h(net, l), h(net, l - 1), nullptr, grads + o[2 * l], grads + o[2 * l + 1],
+                                                                     M, hidden, hidden, w.wgrad, stream);
+            if (rc != AURPPO_OK) return rc;
+            if (const int rc2 = aurppo_linear_dx_tanh_f32(h(net, l), params + o[2 * l], h(net, l - 1), h(net, l - 1), M, hidden, hidden, w.wop,
+                                                          stream))
+                return rc2;
+        }
+        const int rc = L == 1 ? aurppo_linear_wgrad_rows_f32(h(net, 0), obs, idx, grads + o[0], M, hidden, D, w.wgrad, stream)
+                              : aurppo_linear_wgrad_bias_f32(h(net, 0), obs, idx, grads + o[0], grads + o[1], M, hidden, D, w.wgrad, stream);
+        if (rc != AURPPO_OK) return rc;
+    }
+    return AURPPO_OK;
+}
+
+}  // namespace
+
+extern "C" size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers) {
+    if (!layered_hidden_ok(D, hidden, num_layers)) return 0;
+    return 2 * (aurppo_linear_wop_bytes(D, hidden) + (size_t)(num_layers - 1) * aurppo_linear_wop_bytes(hidden, hidden));
+}
+
+// The parameters stand still for the T steps of a rollout, so the operand-order copies of the 2 L hidden-layer matrices are built once,
+// into a caller-owned buffer: [net][layer], each copy aurppo_linear_wop_bytes(its K, hidden) bytes.
+extern "C" int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers,
+                                           void* wop, void* stream) {
+    AURPPO_REQUIRE(params && offsets && wop, AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: null pointer");
+    AURPPO_REQUIRE(layered_hidden_ok(D, hidden, num_layers), AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_prep_f32: D=%d (1 or more), hidden=%d (a multiple of 32, 32..1024), %d layers (1..%d)", D, hidden,
+                   num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_mlp_layered_prep_f32: operand buffer not 16-byte aligned");
+    const int per = 2 * (num_layers + 1);
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < num_layers; ++l) {
+            const int o = offsets[net * per + 2 * l];
+            AURPPO_REQUIRE(o >= 0 && (long long)o + (long long)hidden * (l ? hidden : D) <= (long long)n_params, AURPPO_EINVAL,
+                           "aurppo_mlp_layered_prep_f32: layout offset %d (%d) outside the bucket of %d", net * per + 2 * l, o, n_params);
+        }
+    char* at = reinterpret_cast<char*>(wop);
+    for (int net = 0; net < 2; ++net)
+        for (int l = 0; l < num_layers; ++l) {
+            const int K = l ? hidden : D;
+            if (const int rc = linear_prep(params + offsets[net * per + 2 * l], K, hidden, 0, reinterpret_cast<unsigned short*>(at), (hipStream_t)stream))
+                return rc;
+            at += aurppo_linear_wop_bytes(K, hidden);
+        }
+    return AURPPO_OK;
+}
+
+// ---- the layered rollout step: per net, the hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand
+// copies (aurppo_mlp_layered_prep_f32), then K14.  2 L + 1 launches; the value alone: the critic only, L + 1.
+extern "C" size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden) {
+    if (N <= 0 || hidden <= 0) return 0;
+    return 4 * layered_act_plane_bytes(N, hidden);      // two activation planes per net, written in turn
+}
+
+extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                          int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                          float* logp, float* value, const void* wop, void* workspace, void* stream) {
+    AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL,
+                   "aurppo_mlp_layered_act_f32: null pointer");
+    AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_act_f32: N=%d, D=%d, %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
+    AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
+                   "aurppo_mlp_layered_act_f32: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", hidden, A);
+    AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
+                   "aurppo_mlp_layered_act_f32: obs / operand copies not 16-byte / workspace not 64-byte aligned");
+    AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
+                   AURPPO_EINVAL, "aurppo_mlp_layered_act_f32: noise / outputs not 4-byte aligned");
+    const int L = num_layers, per = 2 * (L + 1);
+    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, "aurppo_mlp_layered_act_f32")) return rc;
+    const size_t plane = layered_act_plane_bytes(N, hidden);
+    const char* const wbase = reinterpret_cast<const char*>(wop);
+    const size_t net_wop = aurppo_linear_wop_bytes(D, hidden) + (size_t)(L - 1) * aurppo_linear_wop_bytes(hidden, hidden);
+    const float* last[2] = {nullptr, nullptr};
+    for (int net = noise ? 0 : 1; net < 2; ++net) {
+        const int* o = offsets + net * per;
+        const char* w = wbase + net * net_wop;
+        const float* x = obs;
+        for (int l = 0; l < L; ++l) {
+            const int K = l ? hidden : D;
+            float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane);
+            if (const int rc = aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream)) return rc;
+            w += aurppo_linear_wop_bytes(K, hidden);
+            x = y;
+        }
+        last[net] = x;
+    }
+    const int lay[5] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per]};
+    return head_act_launch(last[0], last[1], noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
+}
+
+extern "C" size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {
+    if (M <= 0 || D <= 0 || num_layers < 1 || num_layers > kLayeredMaxLayers || !head_shape_ok(hidden, A, 1)) return 0;
+    return layered_step_carve(nullptr, M, D, A, hidden, num_layers).bytes;
+}
+
+extern "C" int aurppo_mlp_layered_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
+                                           int continuous, int hidden, int num_layers, const float* params, const int* offsets,
+                                           int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                           int vloss_mode, float* out_scalars, void* workspace, void* stream) {
+    return layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads, clip, ent_coef,
+                             vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, "aurppo_mlp_layered_step_f32");
+}
+
+// The step, then clip + Adam (aurppo_clip_adam_f32's two launches) over [0, n_params) on the same stream.
+extern "C" int aurppo_mlp_layered_minibatch_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
+                                                int A, int continuous, int hidden, int num_layers, float* params, const int* offsets,
+                                                int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                                int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
+                                                const float* lr_dev, float* step_dev, double beta1, double beta2, double eps,
+                                                float* out_norm, void* workspace, void* stream) {
+    AURPPO_REQUIRE(exp_avg && exp_avg_sq && lr_dev && step_dev && out_norm, AURPPO_EINVAL,
+                   "aurppo_mlp_layered_minibatch_f32: null optimizer pointer");
+    if (const int rc = layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads,
+                                         clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream,
+                                         "aurppo_mlp_layered_minibatch_f32"))
+        return rc;
+    const LayeredStepWs w = layered_step_carve(workspace, M, D, A, hidden, num_layers);
+    return aurppo_clip_adam_f32(params, grads, exp_avg, exp_avg_sq, n_params, n_params, max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm,
+                                w.clip, stream);
+}

@@ -1,4 +1,4 @@
-// The body of k_linear and k_linear_tail (conv.hip), included INSIDE each of the two kernel templates: NB, ROWS, GATE and KTAIL are
+// The body of k_linear and k_linear_tail (linear.hip), included INSIDE each of the two kernel templates: NB, ROWS, GATE and KTAIL are
 // compile-time constants of the including kernel, `a` its LinArgs.  One text, so the two cannot drift; compiled in place, so the
 // aligned kernels keep their names and their instruction streams (through a shared __device__ function they kept neither).
     static_assert(!(GATE && KTAIL), "the input gradient's inner dimension is a hidden width");

@@ -1,4 +1,4 @@
-// The body of k_linear_wgrad and k_linear_wgrad_tail (conv.hip), included INSIDE each of the kernel templates: ROWS, KTAIL and BIAS
+// The body of k_linear_wgrad and k_linear_wgrad_tail (linear.hip), included INSIDE each of the kernel templates: ROWS, KTAIL and BIAS
 // are compile-time constants of the including kernel, `a` its WgradArgs (see linear_body.h for why it is a text and not a function).
 // BIAS: the workgroups of k-tile 0 also sum the dY pieces they fetch anyway over the slice's rows, per column, in fp64 (a thread's
 // rows in ascending order, then the eight row groups in order), and leave one partial vector of N doubles per slice in a.bpart.

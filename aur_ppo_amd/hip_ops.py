@@ -345,7 +345,7 @@ def mlp_layered_layout(policy, bucket, any_state=False):
     """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
     kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, at most 16 actions,
     and a state of a multiple of 16 floats -- or, with ``any_state=True``, of any width (Hopper's 11, HalfCheetah's 17, Humanoid's
-    376: layer 0's three products then run on the tail builds of k_linear / k_linear_wgrad, csrc/conv.hip).  Offsets as K7w's:
+    376: layer 0's three products then run on the tail builds of k_linear / k_linear_wgrad, csrc/linear.hip).  Offsets as K7w's:
     {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no device."""
     if mlp_layout(policy, bucket) is not None:
         return None
@@ -715,6 +715,18 @@ def clip_adam_(flat_param, flat_grad, exp_avg, exp_avg_sq, lr_dev, step_dev, max
 
 
 # ------------------------------------------------------------------ K9
+def _pool2_bwd(dy, mask, shape, has_bias):
+    """K9's backward from the pooled gradient and the mask alone: (dx of ``shape`` (B, C, H, W), the bias gradient or None)."""
+    lib = _lib_or_raise()
+    B, Cc, Hh, Ww = shape
+    dy = dy.contiguous()
+    dx = torch.empty((B, Cc, Hh, Ww), dtype=torch.float32, device=dy.device)
+    part = torch.empty((B, Cc), dtype=torch.float32, device=dy.device) if has_bias else None
+    _check(lib.aurppo_bias_relu_pool2_bwd_f32(_ptr(dy), C.c_void_p(mask.data_ptr()), _ptr(dx), _optr(part), B, Cc, Hh, Ww,
+                                              _stream()), "aurppo_bias_relu_pool2_bwd_f32")
+    return dx, (part.sum(0) if part is not None else None)
+
+
 class _BiasReluPool2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, scale, plane):
@@ -739,12 +751,7 @@ class _BiasReluPool2(torch.autograd.Function):
         lib = _lib_or_raise()
         mask, scale = ctx.saved_tensors
         B, Cc, Hh, Ww = ctx.shape
-        dy = dy.contiguous()
-        dx = torch.empty((B, Cc, Hh, Ww), dtype=torch.float32, device=dy.device)
-        part = torch.empty((B, Cc), dtype=torch.float32, device=dy.device) if ctx.has[0] else None
-        _check(lib.aurppo_bias_relu_pool2_bwd_f32(_ptr(dy), C.c_void_p(mask.data_ptr()), _ptr(dx), _optr(part), B, Cc, Hh, Ww,
-                                                  _stream()), "aurppo_bias_relu_pool2_bwd_f32")
-        dbias = part.sum(0) if part is not None else None
+        dx, dbias = _pool2_bwd(dy, mask, ctx.shape, ctx.has[0])
         dplane = None
         if ctx.has[1]:
             dplane = torch.empty((1, Cc, Hh, Ww), dtype=torch.float32, device=dy.device)
@@ -880,24 +887,30 @@ def conv3x3_wgrad(g, x, cout, pad):
     return dw
 
 
+def _conv3x3_shape_ok(x, cin, cout, pixels):
+    """What K11 and K11p ask of a 4-d ``x`` and a product of ``pixels`` rows (``conv3x3_ok`` says why)."""
+    # a workgroup takes 256 output pixels x 128 output channels: the launch needs a few hundred of them to fill 256 CUs
+    return (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
+            and (pixels >= CONV3X3_MIN_PIXELS or ((pixels + 255) // 256) * ((cout + 127) // 128) >= CONV3X3_MIN_WGS))
+
+
+def _conv3x3_module_ok(conv):
+    """An ``nn.Conv2d`` K11 / K11p can stand in for: 3x3 kernel, stride 1, square zero padding 0..2, no dilation / groups."""
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and conv.padding in ((0, 0), (1, 1), (2, 2)) and conv.padding_mode == "zeros")
+
+
 def conv3x3_ok(x, cin, cout, pad):
     """K11's shape rule for ``conv2d(x, w (cout, cin, 3, 3), padding=pad)``, stride 1: a CUDA fp32 NCHW tensor, cin a multiple
     of 16 (one k-step = 16 channels of a tap), cout a multiple of 32 (whole matrix blocks), and enough output pixels -- a workgroup
     takes 256 of them, and below ~512 workgroups (the encoder's last 3x3 -> 1x1 layers) the launch is a handful of long serial K
     loops that the library's kernels beat."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
-            and pad in (0, 1, 2)):
-        return False
-    pixels = x.shape[0] * (x.shape[2] + 2 * pad - 2) * (x.shape[3] + 2 * pad - 2)
-    # a workgroup takes 256 output pixels x 128 output channels: the launch needs a few hundred of them to fill 256 CUs
-    return pixels >= CONV3X3_MIN_PIXELS or ((pixels + 255) // 256) * ((cout + 127) // 128) >= CONV3X3_MIN_WGS
+    return x.dim() == 4 and pad in (0, 1, 2) and _conv3x3_shape_ok(x, cin, cout, x.shape[0] * (x.shape[2] + 2 * pad - 2) * (x.shape[3] + 2 * pad - 2))
 
 
 def conv3x3_supported(x, conv):
-    """``conv3x3_ok`` for an ``nn.Conv2d``: 3x3 kernel, stride 1, square zero padding 0..2, no dilation / groups."""
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and conv.padding in ((0, 0), (1, 1), (2, 2)) and conv.padding_mode == "zeros"
-            and conv3x3_ok(x, conv.in_channels, conv.out_channels, conv.padding[0]))
+    """``conv3x3_ok`` for an ``nn.Conv2d`` (``_conv3x3_module_ok``)."""
+    return _conv3x3_module_ok(conv) and conv3x3_ok(x, conv.in_channels, conv.out_channels, conv.padding[0])
 
 
 def conv3x3(x, weight, padding):
@@ -926,17 +939,9 @@ class _Conv3x3Pool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib_or_raise()
         x, w, mask = ctx.saved_tensors
-        B, Co, Hp, Wp = mask.shape
-        Ho, Wo = x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2
-        dy = dy.contiguous()
         # K9's backward rebuilds dz from the pooled gradient and the mask alone; from there on it is conv3x3's backward
-        dz = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=dy.device)
-        part = torch.empty((B, Co), dtype=torch.float32, device=dy.device) if ctx.has_bias else None
-        _check(lib.aurppo_bias_relu_pool2_bwd_f32(_ptr(dy), C.c_void_p(mask.data_ptr()), _ptr(dz), _optr(part), B, Co, Ho, Wo,
-                                                  _stream()), "aurppo_bias_relu_pool2_bwd_f32")
-        dbias = part.sum(0) if part is not None else None
+        dz, dbias = _pool2_bwd(dy, mask, mask.shape[:2] + (x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2), ctx.has_bias)
         dx, dw = _conv3x3_grads(dz, x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return dx, dw, dbias, None
 
@@ -944,21 +949,15 @@ class _Conv3x3Pool(torch.autograd.Function):
 def conv3x3_pool_ok(x, cin, cout, pad):
     """K11p's shape rule: ``conv3x3_ok``'s with the pixel count taken as the four positions of every whole pooling window
     (4 * B * Hp * Wp: an odd trailing row / column is never computed), and at least one window."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
-            and pad in (0, 1, 2)):
+    if x.dim() != 4 or pad not in (0, 1, 2):
         return False
     hp, wp = (x.shape[2] + 2 * pad - 2) // 2, (x.shape[3] + 2 * pad - 2) // 2
-    if hp < 1 or wp < 1:
-        return False
-    pixels = 4 * x.shape[0] * hp * wp
-    return pixels >= CONV3X3_MIN_PIXELS or ((pixels + 255) // 256) * ((cout + 127) // 128) >= CONV3X3_MIN_WGS
+    return hp >= 1 and wp >= 1 and _conv3x3_shape_ok(x, cin, cout, 4 * x.shape[0] * hp * wp)
 
 
 def conv3x3_pool_supported(x, conv):
     """``conv3x3_pool_ok`` for an ``nn.Conv2d`` that a ReLU and a ``MaxPool2d(2)`` follow (``conv3x3_supported``'s module rule)."""
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
-            and conv.padding in ((0, 0), (1, 1), (2, 2)) and conv.padding_mode == "zeros"
-            and conv3x3_pool_ok(x, conv.in_channels, conv.out_channels, conv.padding[0]))
+    return _conv3x3_module_ok(conv) and conv3x3_pool_ok(x, conv.in_channels, conv.out_channels, conv.padding[0])
 
 
 def conv3x3_pool(x, weight, bias, padding):
@@ -980,7 +979,7 @@ def linear_ok(x, in_features, out_features):
 
 def linear_nobias(x, w, mode=0):
     """mode 0: ``x @ w.T``; mode 1: ``x @ w`` (the gradient of mode 0 with respect to its input, x being dY) -- fp32 products formed
-    from three-way bf16 splits on the MFMA pipe (csrc/conv.hip::k_linear).  The inner dimension: mode 0 any width (no multiple of 16:
+    from three-way bf16 splits on the MFMA pipe (csrc/linear.hip::k_linear).  The inner dimension: mode 0 any width (no multiple of 16:
     k_linear_tail, which reads nothing past a row's floats), mode 1 a multiple of 16."""
     lib = _lib_or_raise()
     x, w = x.contiguous(), w.contiguous()
@@ -1011,7 +1010,7 @@ def _linear_wgrad(gy, x, rows):
 
 
 def linear_wgrad(gy, x):
-    """``gy.T @ x`` -- nn.Linear's weight gradient -- on the bf16 matrix pipe (csrc/conv.hip::k_linear_wgrad: both operands split
+    """``gy.T @ x`` -- nn.Linear's weight gradient -- on the bf16 matrix pipe (csrc/linear.hip::k_linear_wgrad: both operands split
     once per workgroup through LDS, the rows cut into slices that are summed in slice order).  ``gy``'s width a multiple of 4; ``x`` of
     any width (no multiple of 4: k_linear_wgrad_tail)."""
     return _linear_wgrad(gy, x, None)
@@ -1038,7 +1037,7 @@ def _linear_bias_act(x, rows, w, bias, act):
 
 
 def linear_bias_act(x, w, bias, act=0):
-    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/conv.hip::k_linear with the layer's tail in its epilogue.
+    """``act(x @ w.T + bias)`` in one kernel (act: 0 none, 1 tanh): csrc/linear.hip::k_linear with the layer's tail in its epilogue.
     ``x`` of any width (``linear_nobias``, mode 0)."""
     return _linear_bias_act(x, None, w, bias, act)
 

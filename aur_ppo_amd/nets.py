@@ -13,7 +13,7 @@ from torch import nn
 
 
 def _bf16x3_linear(x, in_features, out_features):
-    """Route this product through csrc/conv.hip::k_linear?  Off by default: measured through ``bench.py --hidden-dim 256 --num-layers 2``
+    """Route this product through csrc/linear.hip::k_linear?  Off by default: measured through ``bench.py --hidden-dim 256 --num-layers 2``
     (the per-op path these layers run on) the update took 40.5 ms with it against 39.1 ms on the library's GEMMs -- that path is
     bound by its ~100 launches and element-wise passes per minibatch, and the separate bias pass this route adds costs what the
     faster product saves.  ``AURPPO_LINEAR_BF16X3=1`` switches it on (tests/test_conv_gpu.py holds it to the fp64 product)."""
@@ -40,7 +40,7 @@ class _LinearSplitK(torch.autograd.Function):
         ctx.save_for_backward(x, weight)
         if _bf16x3_linear(x, weight.shape[1], weight.shape[0]):
             # layers the fused steps do not cover (hidden_dim > 128): the product on bf16 MFMAs over three-way splits
-            # (csrc/conv.hip::k_linear, fp32-equivalent) instead of the library's fp32 GEMM at 0.35 of the fp32 MFMA peak
+            # (csrc/linear.hip::k_linear, fp32-equivalent) instead of the library's fp32 GEMM at 0.35 of the fp32 MFMA peak
             from . import hip_ops as H
             return H.linear_nobias(x.detach(), weight.detach(), 0) + bias
         return torch.nn.functional.linear(x, weight, bias)
@@ -66,7 +66,7 @@ class _LinearSplitK(torch.autograd.Function):
 
 
 class _LinearTanhFn(torch.autograd.Function):
-    """``tanh(x W^T + b)`` as ONE kernel forward (csrc/conv.hip::k_linear with bias + tanh in its epilogue) -- a hidden layer of
+    """``tanh(x W^T + b)`` as ONE kernel forward (csrc/linear.hip::k_linear with bias + tanh in its epilogue) -- a hidden layer of
     src/nets/nets.py:21-27 for the shapes the fused K7 / K7w steps do not cover; backward: tanh' from the saved output, the input
     gradient on the same kernel (mode 1), the weight gradient on k_linear_wgrad where both of its dimensions fill a 128 x 128 tile,
     else with the split over the batch of ``_LinearSplitK``."""

@@ -1,5 +1,5 @@
 """Cases of the layered PPO step and the layered rollout step at state widths that are no multiple of 16 (``mlp_layered_layout(...,
-any_state=True)``: layer 0's products on the tail builds k_linear_tail / k_linear_wgrad_tail of csrc/conv.hip), shared by the GPU test
+any_state=True)``: layer 0's products on the tail builds k_linear_tail / k_linear_wgrad_tail of csrc/linear.hip), shared by the GPU test
 (tests/test_layered_ragged_fp64_gpu.py) and the host test that shows the bars can be met at these shapes
 (tests/test_layered_ragged_host.py).  A plain helper module: ``tests/ref64.py`` supplies the reference, the yardstick, the metric and the
 bars, ``tests/layered_act_cases.py`` the rollout step's ``build`` / ``yardstick`` / ``metrics``, all unchanged.

@@ -83,7 +83,7 @@ def test_conv3x3_weight_gradient_matches_the_fp64_convolution(B, Ci, Co, H, W, p
 
 @pytest.mark.parametrize("M,N,K", [(32768, 256, 256), (40001, 256, 64), (33000, 96, 256), (70001, 160, 48), (32768, 64, 64), (1000, 256, 256)])
 def test_linear_weight_gradient_matches_the_fp64_product(M, N, K):
-    """csrc/conv.hip::k_linear_wgrad (dW = dY^T X for the layers wider than the fused steps cover) against fp64."""
+    """csrc/linear.hip::k_linear_wgrad (dW = dY^T X for the layers wider than the fused steps cover) against fp64."""
     from aur_ppo_amd import hip_ops as Hh
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     gy = torch.randn(M, N, device="cuda", generator=g)
@@ -132,7 +132,7 @@ def test_encoder_with_k11_matches_the_stock_encoder(monkeypatch):
 
 @pytest.mark.parametrize("M,K,N", [(32768, 64, 256), (40000, 256, 256), (33000, 256, 96), (32768, 16, 32), (70001, 48, 160)])
 def test_linear_forward_and_input_gradient_match_the_fp64_product(M, K, N, monkeypatch):
-    """csrc/conv.hip::k_linear (nn.Linear's product for the MLP shapes the fused steps do not cover) against the fp64 matrix product:
+    """csrc/linear.hip::k_linear (nn.Linear's product for the MLP shapes the fused steps do not cover) against the fp64 matrix product:
     the fp32 rounding level of the sum of |products|; through nets._Linear the module's forward / backward use it."""
     from aur_ppo_amd import hip_ops as Hh
     from aur_ppo_amd import nets

@@ -1,4 +1,4 @@
-"""GPU: csrc/conv.hip's nn.Linear products at an inner dimension that is no multiple of 16 (forward: k_linear_tail, plain and through
+"""GPU: csrc/linear.hip's nn.Linear products at an inner dimension that is no multiple of 16 (forward: k_linear_tail, plain and through
 the minibatch index, from k_linear_prep_tail's zero-padded operand copy) or of 4 (weight gradient: k_linear_wgrad_tail, its x operand).
 
 T1  bit equality with the aligned kernels on zero-padded operands: the k-steps and their order are the same and the padded columns are

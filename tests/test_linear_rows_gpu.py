@@ -1,4 +1,4 @@
-"""GPU: the three additions to csrc/conv.hip's nn.Linear products that the layered PPO step rides on -- rows through the minibatch
+"""GPU: the three additions to csrc/linear.hip's nn.Linear products that the layered PPO step rides on -- rows through the minibatch
 index in k_linear and in k_linear_wgrad's x operand, and tanh' of the layer below in k_linear's epilogue.  Each is the plain kernel
 with one operand addressed differently (or one more multiply), so each is held to the plain call's BITS on the gathered / un-gated
 operands; one shape of each also goes against the fp64 product on tests/test_conv_gpu.py's metric and bound (1e-6 of sum |a b|)."""
@@ -47,7 +47,7 @@ def test_indexed_weight_gradient_equals_the_product_on_gathered_rows(M, N, K, ki
 
 @pytest.mark.parametrize("M,K,N", [(1, 32, 32), (255, 96, 32), (257, 256, 256), (1000, 160, 160)])
 def test_tanh_backward_epilogue_equals_product_then_tanh_backward(M, K, N):
-    """(gz @ w) * (1 - h * h) in one launch == the mode-1 product followed by aten's tanh_backward, bit for bit (conv.hip is
+    """(gz @ w) * (1 - h * h) in one launch == the mode-1 product followed by aten's tanh_backward, bit for bit (linear.hip is
     compiled without contraction: the epilogue is a multiply, a subtract and a multiply); in place of ``h`` too."""
     from aur_ppo_amd import hip_ops as H
     g = torch.Generator(device="cuda").manual_seed(M + K + N + 2)
