@@ -27,6 +27,8 @@ SYMBOLS = (
     "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_linear_wgrad_bias_f32", "aurppo_mlp_layered_step_workspace_bytes",
     "aurppo_mlp_layered_step_f32", "aurppo_mlp_layered_minibatch_f32",
     "aurppo_conv3x3_pool_f32",
+    "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_dgrad_narrow_f32", "aurppo_conv3x3_wgrad_narrow_ws_bytes",
+    "aurppo_conv3x3_wgrad_narrow_f32",
 )
 
 _lib = None
@@ -128,6 +130,11 @@ def _declare(lib):
     lib.aurppo_mlp_layered_minibatch_f32.argtypes = step_prefix(2) + adam_tail + ws_stream
     lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
     lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
+    # the narrow builds of the 16 -> 32 block's gradients
+    lib.aurppo_conv3x3_dgrad_narrow_wop_bytes.argtypes = [i32] * 2
+    lib.aurppo_conv3x3_dgrad_narrow_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
+    lib.aurppo_conv3x3_wgrad_narrow_ws_bytes.argtypes = [i32] * 6
+    lib.aurppo_conv3x3_wgrad_narrow_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
     # the one-shot exchange
     lib.aurppo_p2p_parts.argtypes = [i32]
     lib.aurppo_p2p_create.argtypes = [C.POINTER(vp), i32, i32, i32, vp]
@@ -156,6 +163,7 @@ def _declare(lib):
     sized = ("aurppo_loss_workspace_bytes", "aurppo_clip_workspace_bytes", "aurppo_mlp_workspace_bytes", "aurppo_conv3x3_wop_bytes",
              "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
              "aurppo_head_ppo_workspace_bytes", "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_act_workspace_bytes",
-             "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes")
+             "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes",
+             "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes")
     for name in SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

@@ -806,6 +806,7 @@ class _FirstBlock(torch.autograd.Function):
 CONV3X3_MIN_PIXELS = 131072
 CONV3X3_MIN_WGS = 512
 K12_MIN_COUT, K12_MIN_CIN, K12_MIN_PIXELS = 64, 32, 16384
+NARROW_MIN_PIXELS = 262144      # output pixels of the batch from which K11n / K12n are taken (512 one-wave slices of K12n, 2048 tiles of K11n)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -837,6 +838,11 @@ def _conv3x3_grads(g, x, w, pad, need_dx, need_dw):
     B, Ci, Hh, Ww = x.shape
     Co = w.shape[0]
     dx = dw = None
+    if os.environ.get("AURPPO_NARROW_GRADS") == "1":      # opt-in: the narrow builds first, where their rules hold
+        if need_dx and conv3x3_dgrad_narrow_ok(g, w, pad):
+            dx, need_dx = conv3x3_dgrad_narrow(g, w, pad), False      # K11n
+        if need_dw and conv3x3_wgrad_narrow_ok(g, x, Co, pad):
+            dw, need_dw = conv3x3_wgrad_narrow(g, x, Co, pad), False      # K12n
     if need_dx and Ci % 32 != 0 and os.environ.get("AURPPO_K11_DGRAD16") != "1":
         # an input gradient with 16 output channels would leave half of every 32-wide matrix block empty: the library's kernel
         dx = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
@@ -884,6 +890,70 @@ def conv3x3_wgrad(g, x, cout, pad):
     ws = _workspace("wgrad", nb, x.device)
     dw = torch.empty((cout, Ci, 3, 3), dtype=torch.float32, device=x.device)
     _check(lib.aurppo_conv3x3_wgrad_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), *_ws_stream(ws)), "aurppo_conv3x3_wgrad_f32")
+    return dw
+
+
+def _narrow_tensor_ok(t):
+    return t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+
+
+def conv3x3_dgrad_narrow_ok(g, w, pad):
+    """K11n's rule for the input gradient of ``conv2d(x, w (Co, Ci, 3, 3), padding=pad)`` under ``g`` (B, Co, Ho, Wo): contiguous CUDA
+    fp32 4-d tensors, Ci in 1..16, Co a multiple of 32, pad 0..2 (the library's byte query says so), and at least
+    ``NARROW_MIN_PIXELS`` pixels in ``g``."""
+    if not (_narrow_tensor_ok(g) and _narrow_tensor_ok(w) and pad in (0, 1, 2) and tuple(w.shape[2:]) == (3, 3) and g.shape[1] == w.shape[0]):
+        return False
+    if g.shape[2] + 2 - 2 * pad <= 0 or g.shape[3] + 2 - 2 * pad <= 0:
+        return False
+    if _lib_or_raise().aurppo_conv3x3_dgrad_narrow_wop_bytes(w.shape[1], w.shape[0]) == 0:
+        return False
+    return g.shape[0] * g.shape[2] * g.shape[3] >= NARROW_MIN_PIXELS
+
+
+def conv3x3_dgrad_narrow(g, w, pad):
+    """K11n: the gradient of ``conv2d(x, w (Co, Ci <= 16, 3, 3), padding=pad)`` with respect to ``x`` given the output gradient ``g``
+    (csrc/conv_narrow.hip::k_conv3x3_narrow_dgrad: 16-wide matrix blocks, the dy tile split once for all nine taps)."""
+    lib = _lib_or_raise()
+    B, Co, Ho, Wo = g.shape
+    Ci = w.shape[1]
+    Hh, Ww = Ho + 2 - 2 * pad, Wo + 2 - 2 * pad
+    nb = lib.aurppo_conv3x3_dgrad_narrow_wop_bytes(Ci, Co)
+    if nb == 0:
+        raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_dgrad_narrow_f32 does not take this shape")
+    ws = _workspace("dgrad_narrow", nb, g.device)
+    dx = torch.empty((B, Ci, Hh, Ww), dtype=torch.float32, device=g.device)
+    _check(lib.aurppo_conv3x3_dgrad_narrow_f32(_ptr(g), _ptr(w.detach()), _ptr(dx), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
+           "aurppo_conv3x3_dgrad_narrow_f32")
+    return dx
+
+
+def conv3x3_wgrad_narrow_ok(g, x, cout, pad):
+    """K12n's rule for the weight gradient of ``conv2d(x, w (cout, Ci, 3, 3), padding=pad)``: contiguous CUDA fp32 4-d tensors, Ci in
+    1..16, cout in 1..32, pad 0..2 and an addressable shape (the library's byte query), and at least ``NARROW_MIN_PIXELS`` pixels
+    in ``g``."""
+    if not (_narrow_tensor_ok(g) and _narrow_tensor_ok(x) and pad in (0, 1, 2)):
+        return False
+    B, Ci, Hh, Ww = x.shape
+    if tuple(g.shape) != (B, cout, Hh + 2 * pad - 2, Ww + 2 * pad - 2):
+        return False
+    if _lib_or_raise().aurppo_conv3x3_wgrad_narrow_ws_bytes(B, Ci, cout, Hh, Ww, pad) == 0:
+        return False
+    return g.shape[0] * g.shape[2] * g.shape[3] >= NARROW_MIN_PIXELS
+
+
+def conv3x3_wgrad_narrow(g, x, cout, pad):
+    """K12n: the gradient of ``conv2d(x, w (cout <= 32, Ci <= 16, 3, 3), padding=pad)`` with respect to ``w`` given ``g``
+    (csrc/conv_narrow.hip::k_conv3x3_narrow_wgrad: a wave owns the whole 32 x 144 filter and a slice of the pixels; slices folded in order)."""
+    lib = _lib_or_raise()
+    B, Ci, Hh, Ww = x.shape
+    assert g.shape == (B, cout, Hh + 2 * pad - 2, Ww + 2 * pad - 2), (g.shape, x.shape, cout, pad)
+    nb = lib.aurppo_conv3x3_wgrad_narrow_ws_bytes(B, Ci, cout, Hh, Ww, int(pad))
+    if nb == 0:
+        raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_wgrad_narrow_f32 does not take this shape")
+    ws = _workspace("wgrad_narrow", nb, x.device)
+    dw = torch.empty((cout, Ci, 3, 3), dtype=torch.float32, device=x.device)
+    _check(lib.aurppo_conv3x3_wgrad_narrow_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), *_ws_stream(ws)),
+           "aurppo_conv3x3_wgrad_narrow_f32")
     return dw
 
 

@@ -413,6 +413,23 @@ size_t aurppo_conv3x3_wgrad_ws_bytes(int B, int Ci, int Co, int H, int W, int pa
 int aurppo_conv3x3_wgrad_f32(const float* dy, const float* x, float* dw, int B, int Ci, int Co, int H, int W, int pad, void* ws,
                              void* stream);
 
+/* K11n / K12n -- the narrow builds of K11's mode 1 and of K12 for the first hidden block of the encoder, nn.Conv2d(16, 32, 3,
+ * padding=1) (src/nets/base_cnns.py:32-33), whose gradients fill half of K11's 32-channel blocks and 28 % of K12's smallest tile:
+ * the same arithmetic (three bf16 planes per fp32 operand, six products, fp32 accumulation) in 16 x 16 x 32 matrix blocks.  NCHW fp32;
+ * H x W is the map of x / dx, pad the FORWARD padding (0..2), dy (B, Co, H + 2 pad - 2, W + 2 pad - 2), w (Co, Ci, 3, 3).
+ * K11n: dx (B, Ci, H, W) = d conv2d(x, w, padding = pad) / d x applied to dy; Ci in 1..16, Co a positive multiple of 32.
+ * wop_ws: aurppo_conv3x3_dgrad_narrow_wop_bytes(Ci, Co) bytes, 16-byte aligned (0 = channel counts outside the class).
+ * K12n: dw (Co, Ci, 3, 3) from dy and x (B, Ci, H, W); Co in 1..32, Ci in 1..16; a deterministic split over the batch's pixels whose
+ * partial filters live in ws: aurppo_conv3x3_wgrad_narrow_ws_bytes(...) bytes, 16-byte aligned (0 = shape not taken: outside the
+ * class, an empty output, or one image of either tensor of 1 GB and more).  No atomics: a second call leaves the same bits.
+ * Both refuse (AURPPO_EINVAL: null pointer, unaligned workspace; AURPPO_ESHAPE: the shape) before their first launch. */
+size_t aurppo_conv3x3_dgrad_narrow_wop_bytes(int Ci, int Co);
+int aurppo_conv3x3_dgrad_narrow_f32(const float* dy, const float* w, float* dx, int B, int Ci, int Co, int H, int W, int pad,
+                                    void* wop_ws, void* stream);
+size_t aurppo_conv3x3_wgrad_narrow_ws_bytes(int B, int Ci, int Co, int H, int W, int pad);
+int aurppo_conv3x3_wgrad_narrow_f32(const float* dy, const float* x, float* dw, int B, int Ci, int Co, int H, int W, int pad,
+                                    void* ws, void* stream);
+
 /* ---- one-shot gradient all-reduce over peer memory (one process per GPU; SURVEY 8e plan B) ------------------
  * Where it sits in the reference: between loss.backward() and clip_grad_norm_ (src/ppo.py:266-268); upstream is
  * single-process, so there is no call to cite -- the semantics are "mean of the ranks' gradients, identical bits on
