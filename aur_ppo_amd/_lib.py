@@ -29,6 +29,8 @@ SYMBOLS = (
     "aurppo_conv3x3_pool_f32",
     "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_dgrad_narrow_f32", "aurppo_conv3x3_wgrad_narrow_ws_bytes",
     "aurppo_conv3x3_wgrad_narrow_f32",
+    "aurppo_planes_bytes", "aurppo_split_planes_f32", "aurppo_conv3x3_planes_f32", "aurppo_conv3x3_pool_planes_f32",
+    "aurppo_first_block_planes_fwd_f32",
 )
 
 _lib = None
@@ -135,6 +137,12 @@ def _declare(lib):
     lib.aurppo_conv3x3_dgrad_narrow_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
     lib.aurppo_conv3x3_wgrad_narrow_ws_bytes.argtypes = [i32] * 6
     lib.aurppo_conv3x3_wgrad_narrow_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
+    # K11x: activations as bf16 planes
+    lib.aurppo_planes_bytes.argtypes = [i32] * 4
+    lib.aurppo_split_planes_f32.argtypes = [vp, vp] + [i32] * 4 + [vp]
+    lib.aurppo_conv3x3_planes_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
+    lib.aurppo_conv3x3_pool_planes_f32.argtypes = [vp, i32] + [vp] * 5 + [i32] * 6 + ws_stream
+    lib.aurppo_first_block_planes_fwd_f32.argtypes = [vp] * 7 + [i32] * 5 + [vp]
     # the one-shot exchange
     lib.aurppo_p2p_parts.argtypes = [i32]
     lib.aurppo_p2p_create.argtypes = [C.POINTER(vp), i32, i32, i32, vp]
@@ -164,6 +172,6 @@ def _declare(lib):
              "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
              "aurppo_head_ppo_workspace_bytes", "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_act_workspace_bytes",
              "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes",
-             "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes")
+             "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes", "aurppo_planes_bytes")
     for name in SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

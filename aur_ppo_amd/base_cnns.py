@@ -51,10 +51,27 @@ class base_encoder(nn.Module):
     fused_conv = os.environ.get("AURPPO_NO_K11") != "1"      # K11 for the hidden 3x3 convolutions on CUDA tensors (False / AURPPO_NO_K11=1: torch / MIOpen, for A/B runs)
     fused_first = True     # K10 for the first block when it runs in split form on CUDA tensors
     fused_block = os.environ.get("AURPPO_K11_POOL") == "1"   # K11p: a hidden block's convolution, bias, ReLU and pool in one launch (opt-in)
+    # K11x: a block hands its output to the next one as bf16 planes too, and the next convolution reads those (opt-in; the blocks it
+    # takes run fused, as under fused_block, and compute the same bits)
+    fused_planes = os.environ.get("AURPPO_K11_PLANES") == "1"
 
-    def _blocks(self, x, start, scale=None, plane=None, first_weight=None):
+    @staticmethod
+    def _is_triple(mods, i):
+        return (isinstance(mods[i], nn.Conv2d) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                and isinstance(mods[i + 2], nn.MaxPool2d) and mods[i + 2].kernel_size in (2, (2, 2))
+                and mods[i + 2].stride in (2, (2, 2)) and mods[i + 2].padding in (0, (0, 0)))
+
+    def _reads_planes(self, H, mods, j, shape):
+        """Would ``mods[j]`` run on the planes of an input of ``shape``?  A K11 / K11p convolution whose producer is asked for them."""
+        if not (self.fused_planes and self.fused_conv) or j >= len(mods) or not isinstance(mods[j], nn.Conv2d) or shape[1] % 8 != 0:
+            return False
+        like = H.like_gpu(shape)
+        return H.conv3x3_pool_supported(like, mods[j]) if self._is_triple(mods, j) else H.conv3x3_supported(like, mods[j])
+
+    def _blocks(self, x, start, scale=None, plane=None, first_weight=None, xp=None):
         """Run self.conv[start:] on x; on the GPU every (Conv2d, ReLU, MaxPool2d(2)) triple becomes convolution without bias
-        + K9.  ``scale`` / ``plane`` / ``first_weight`` belong to the first convolution when it runs in split form."""
+        + K9.  ``scale`` / ``plane`` / ``first_weight`` belong to the first convolution when it runs in split form; ``xp``: the
+        planes of ``x`` where its producer wrote them (K11x)."""
         mods = list(self.conv)
         use = self.fused_pool and x.is_cuda
         if use:
@@ -62,12 +79,21 @@ class base_encoder(nn.Module):
         i = start
         while i < len(mods):
             m = mods[i]
-            triple = (isinstance(m, nn.Conv2d) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                      and isinstance(mods[i + 2], nn.MaxPool2d) and mods[i + 2].kernel_size in (2, (2, 2))
-                      and mods[i + 2].stride in (2, (2, 2)) and mods[i + 2].padding in (0, (0, 0)))
+            triple = self._is_triple(mods, i)
+            xp_in, xp = xp, None            # planes belong to the tensor they were written beside: one consumer, then gone
             if use and triple:
                 w = first_weight if (i == start and first_weight is not None) else m.weight
                 own_tail = i == start and (scale is not None or plane is not None)      # the split first block's state plane: K9's
+                if self.fused_planes and self.fused_conv and w is m.weight and not own_tail and H.conv3x3_pool_supported(x, m):
+                    pad = m.padding[0]
+                    out_shape = (x.shape[0], m.out_channels, (x.shape[2] + 2 * pad - 2) // 2, (x.shape[3] + 2 * pad - 2) // 2)
+                    want = self._reads_planes(H, mods, i + 3, out_shape)
+                    if xp_in is not None or want:       # K11x: reads its predecessor's planes, writes its successor's, or both
+                        x = H.conv3x3_pool_planes(x, xp_in, m.weight, m.bias, pad, want)
+                        if want:
+                            x, xp = x
+                        i += 3
+                        continue
                 if self.fused_block and self.fused_conv and w is m.weight and not own_tail and H.conv3x3_pool_supported(x, m):
                     x = H.conv3x3_pool(x, m.weight, m.bias, m.padding[0])       # K11p: z is never written
                     i += 3
@@ -79,7 +105,8 @@ class base_encoder(nn.Module):
                 x = H.bias_relu_pool2(z, m.bias, scale if i == start else None, plane if i == start else None)
                 i += 3
             elif use and self.fused_conv and isinstance(m, nn.Conv2d) and H.conv3x3_supported(x, m):
-                x = H.conv3x3(x, m.weight, m.padding[0]) + m.bias.reshape(1, -1, 1, 1)
+                z = H.conv3x3(x, m.weight, m.padding[0]) if xp_in is None else H.conv3x3_planes(x, xp_in, m.weight, m.padding[0])
+                x = z + m.bias.reshape(1, -1, 1, 1)
                 i += 1
             else:
                 x = m(x)
@@ -101,6 +128,10 @@ class base_encoder(nn.Module):
                 and isinstance(mods[1], nn.ReLU) and isinstance(mods[2], nn.MaxPool2d) and mods[2].kernel_size in (2, (2, 2))):
             # K10: convolution of the image channels and of the tiled state, bias, ReLU and the pool in one kernel
             from . import hip_ops as H
+            out_shape = (obs.shape[0], first.out_channels, obs.shape[2] // 2, obs.shape[3] // 2)
+            if self._reads_planes(H, list(mods), 3, out_shape):
+                y, yp = H.first_block(obs, state, first.weight, first.bias, want_planes=True)
+                return self._blocks(y, 3, xp=yp)
             return self._blocks(H.first_block(obs, state, first.weight, first.bias), 3)
         if self.fused_pool and obs.is_cuda and memory_format is None:
             # K9 adds state * plane and the bias while it applies ReLU and the pool: the block's output is written once

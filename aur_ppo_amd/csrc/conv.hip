@@ -47,6 +47,20 @@ struct ConvPoolArgs {
     uint8_t* mask;                   // (B, Cout, Ho, Wo): K9's byte
 };
 
+// K11x (the XPL / OPL builds): activations as bf16 planes, uint16 [b][c / 8][plane][pixel][8] (include/aurppo.h)
+struct ConvPlanesArgs {
+    ConvPoolArgs p;                  // (without POOL: p.c alone)
+    const unsigned short* xp;        // XPL: the input's planes (p.c.x is not read)
+    unsigned short* yp;              // OPL: the pooled output's planes, beside p.c.z and p.mask
+};
+
+// One pixel block's A values of a k-step in an XPL build are its three planes, in an fp32 build eight floats: the body's text names
+// both, and only the including build's kind is ever called.
+__device__ __forceinline__ void put_plane(u32x4 (&d)[3], int pl, u32x4 t) { d[pl] = t; }
+[[maybe_unused]] __device__ __forceinline__ void put_plane(float (&)[8], int, u32x4) {}
+__device__ __forceinline__ u32x4 get_plane(const u32x4 (&d)[3], int pl) { return d[pl]; }
+[[maybe_unused]] __device__ __forceinline__ u32x4 get_plane(const float (&)[8], int) { return u32x4{0u, 0u, 0u, 0u}; }
+
 // filter -> operand order.  transpose_flip = 0 (forward): B[k = (tap, ci)][n = co] = W[co][ci][tap];
 // 1 (input gradient): the product's "input" channels are the forward pass's OUTPUT channels: B[k = (tap, co)][n = ci] =
 // W[co][ci][8 - tap].  cin_gemm / cout_gemm are the product's own channel counts (cin_gemm a multiple of 16).
@@ -96,9 +110,11 @@ __global__ __launch_bounds__(256) void k_linear_prep_tail(const float* __restric
 // 48 matrix instructions, and the two barely overlap (SQ_VALU_MFMA_COEXEC_CYCLES 7 % of the matrix time, profiles/r04).
 template <int NB, bool BUF>      // NB: 32-channel blocks of the channel group (1, 2 or 4)
 __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvArgs a) {
-    constexpr bool POOL = false;
+    constexpr bool POOL = false, XPL = false, OPL = false;
     constexpr const float* pool_bias = nullptr;
     constexpr uint8_t* pool_mask = nullptr;
+    constexpr const unsigned short* in_planes = nullptr;
+    constexpr unsigned short* out_planes = nullptr;
 #include "conv3x3_body.h"
 }
 // The POOL builds (K11p, conv3x3_body.h says what they are) are an overload with a third template parameter and their own argument
@@ -107,9 +123,47 @@ template <int NB, bool BUF, bool POOL>
 __global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvPoolArgs p) {
     static_assert(POOL, "the plain builds are k_conv3x3<NB, BUF>");
     const ConvArgs& a = p.c;
+    constexpr bool XPL = false, OPL = false;
     const float* const pool_bias = p.bias;
     uint8_t* const pool_mask = p.mask;
+    constexpr const unsigned short* in_planes = nullptr;
+    constexpr unsigned short* out_planes = nullptr;
 #include "conv3x3_body.h"
+}
+// K11x (the XPL / OPL builds, conv3x3_body.h says what they are): again an overload with its own argument block, forward products only.
+// XPL without POOL is K11 on planes (q.p.c alone, with c.x unused); with POOL it is K11p reading planes, writing them (OPL), or both.
+template <int NB, bool BUF, bool POOL, bool XPL, bool OPL>
+__global__ __launch_bounds__(kConvThreads, 2) void k_conv3x3(const ConvPlanesArgs q) {
+    static_assert(XPL || OPL, "the fp32 builds are k_conv3x3<NB, BUF> and k_conv3x3<NB, BUF, true>");
+    static_assert(POOL || !OPL, "planes are written by the pooled epilogue");
+    const ConvArgs& a = q.p.c;
+    [[maybe_unused]] const float* const pool_bias = q.p.bias;
+    [[maybe_unused]] uint8_t* const pool_mask = q.p.mask;
+    [[maybe_unused]] const unsigned short* const in_planes = q.xp;
+    [[maybe_unused]] unsigned short* const out_planes = q.yp;
+#include "conv3x3_body.h"
+}
+
+// fp32 NCHW -> planes (include/aurppo.h: uint16 [b][c / 8][plane][pixel][8]): a thread takes one pixel of one group of eight channels --
+// eight dword loads, coalesced over the pixels, and one 16-byte store per plane.  The DEFINITION of the layout: what an OPL producer
+// writes and what an XPL build reads is what this kernel leaves.
+__global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ x, unsigned short* __restrict__ xp, long long n_groups,
+                                                      int HW) {
+    const long long total = n_groups * HW;        // n_groups = B * C / 8
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long bg = e / HW;
+        const int px = (int)(e - bg * HW);
+        const float* const src = x + (size_t)bg * 8 * HW + px;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = src[(size_t)j * HW];
+        unsigned p[4][3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) split3(v[2 * q], v[2 * q + 1], p[q][0], p[q][1], p[q][2]);
+        u32x4* const dst = reinterpret_cast<u32x4*>(xp) + (size_t)bg * 3 * HW + px;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) dst[(size_t)pl * HW] = u32x4{p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
+    }
 }
 
 // ---- K12: the 3x3 convolution's WEIGHT gradient on the same arithmetic.
@@ -387,19 +441,26 @@ __global__ __launch_bounds__(256) void k_fold_slices_bias(const float* __restric
 // The host plan K11 and K11p share: every refusal (under the entry's name `who`), the argument block, the grid and the build, all of it
 // before the entry's first launch.  cin / cout / p are the product's own (the entry has mapped its mode); Ho x Wo is the map z holds
 // and M the product's rows -- K11: the output pixels; K11p: the pooled map and the four positions of each of its windows.
+// K11x: xp (the input as planes, x then null) and / or yp (the output's planes, K11p's epilogue only) -- both 16-byte aligned, yp with whole
+// groups of eight output channels.
 struct ConvPlan {
     ConvPoolArgs p;                  // (K11 launches with p.c alone)
     Bf3Grid g;
     bool buf;                        // the BUF builds
+    const unsigned short* xp;        // K11x's two further arguments (null: the fp32 builds)
+    unsigned short* yp;
 };
 int conv_plan(const char* who, const float* x, const float* w, float* z, void* wop_ws, int B, int cin, int cout, int H, int W, int p,
-              int Ho, int Wo, long long M, ConvPlan* pl) {
-    AURPPO_REQUIRE(x && w && z && wop_ws, AURPPO_EINVAL, "%s: null pointer", who);
+              int Ho, int Wo, long long M, ConvPlan* pl, const unsigned short* xp = nullptr, unsigned short* yp = nullptr) {
+    AURPPO_REQUIRE((x || xp) && w && z && wop_ws, AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(aligned_to(xp, 16) && aligned_to(yp, 16), AURPPO_EINVAL, "%s: planes not 16-byte aligned", who);
     AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0 && cin % 16 == 0, AURPPO_ESHAPE,
                    "%s: B=%d H=%d W=%d, %d input channels (a multiple of 16), %d output channels", who, B, H, W, cin, cout);
     AURPPO_REQUIRE(H + 2 * p - 2 > 0 && W + 2 * p - 2 > 0, AURPPO_ESHAPE, "%s: empty output (%d x %d)", who, H + 2 * p - 2, W + 2 * p - 2);
     AURPPO_REQUIRE((size_t)B * cin * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
                    "%s: operand too large / workspace not 16-byte aligned", who);
+    AURPPO_REQUIRE(!yp || cout % 8 == 0, AURPPO_ESHAPE, "%s: %d output channels as planes (a multiple of 8)", who, cout);
+    pl->xp = xp; pl->yp = yp;
     ConvArgs& a = pl->p.c;
     a.x = x; a.wop = reinterpret_cast<unsigned short*>(wop_ws); a.z = z;
     a.B = B; a.Cin = cin; a.H = H; a.W = W; a.Cout = cout; a.Ho = Ho; a.Wo = Wo; a.pad = p;
@@ -410,7 +471,8 @@ int conv_plan(const char* who, const float* x, const float* w, float* z, void* w
     a.n_mb4 = (int)pl->g.n_mb;
     AURPPO_REQUIRE(pl->g.n_mb * pl->g.n_ng < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", who);
     // buffer loads address 32 bits: inputs under 4 GB (minus the slack a negative tap offset may wrap through); larger ones keep 64-bit addresses
-    pl->buf = (size_t)B * cin * H * W * 4 < ((size_t)1 << 32) - ((size_t)1 << 20);
+    // (planes hold 6 bytes an element: the same limit, reached 1.5 x sooner)
+    pl->buf = (size_t)B * cin * H * W * (xp ? 6 : 4) < ((size_t)1 << 32) - ((size_t)1 << 20);
     return AURPPO_OK;
 }
 
@@ -507,6 +569,82 @@ extern "C" int aurppo_conv3x3_pool_f32(const float* x, const float* w, const flo
         else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false, true>), g, blk, 0, s, pl.p);
     });
     AURPPO_LAUNCH_CHECK("k_conv3x3 (pool)");
+    return AURPPO_OK;
+}
+
+// ---- K11x: activations as bf16 planes (include/aurppo.h: the layout, and what each entry refuses)
+extern "C" size_t aurppo_planes_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || C % 8 != 0) return 0;
+    return (size_t)6 * B * C * H * W;
+}
+
+extern "C" int aurppo_split_planes_f32(const float* x, uint16_t* xp, int B, int C, int H, int W, void* stream) {
+    AURPPO_REQUIRE(x && xp, AURPPO_EINVAL, "aurppo_split_planes_f32: null pointer");
+    AURPPO_REQUIRE(aligned_to(xp, 16), AURPPO_EINVAL, "aurppo_split_planes_f32: planes not 16-byte aligned");
+    AURPPO_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && C % 8 == 0 && (size_t)H * W < ((size_t)1 << 31) &&
+                   (size_t)B * C * H * W < ((size_t)1 << 40), AURPPO_ESHAPE,
+                   "aurppo_split_planes_f32: B=%d C=%d H=%d W=%d (C a multiple of 8)", B, C, H, W);
+    const long long n_groups = (long long)B * (C / 8), total = n_groups * H * W;
+    const long long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(k_split_planes, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, x, xp, n_groups, H * W);
+    AURPPO_LAUNCH_CHECK("k_split_planes");
+    return AURPPO_OK;
+}
+
+namespace {
+template <bool POOL, bool XPL, bool OPL>
+void launch_conv_planes(const ConvPlan& pl, hipStream_t s) {
+    const ConvPlanesArgs q{pl.p, pl.xp, pl.yp};
+    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
+    bf3_with_nb(pl.g.NB, [&](auto nb) {
+        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true, POOL, XPL, OPL>), g, blk, 0, s, q);
+        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false, POOL, XPL, OPL>), g, blk, 0, s, q);
+    });
+}
+}  // namespace
+
+// K11 on planes: z = conv2d(x, w, padding = pad) for the x whose planes xp holds -- aurppo_conv3x3_f32's mode 0, bit for bit.
+extern "C" int aurppo_conv3x3_planes_f32(const uint16_t* xp, const float* w, float* z, int B, int Ci, int Co, int H, int W, int pad,
+                                         void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(xp, AURPPO_EINVAL, "aurppo_conv3x3_planes_f32: null pointer");
+    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_planes_f32: pad=%d (0..2)", pad);
+    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+    ConvPlan pl;
+    pl.p.bias = nullptr; pl.p.mask = nullptr;
+    if (const int rc = conv_plan("aurppo_conv3x3_planes_f32", nullptr, w, z, wop_ws, B, Ci, Co, H, W, pad, Ho, Wo, (long long)B * Ho * Wo, &pl, xp))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    launch_conv_planes<false, true, false>(pl, s);
+    AURPPO_LAUNCH_CHECK("k_conv3x3 (planes)");
+    return AURPPO_OK;
+}
+
+// K11p with its input read as planes (x_is_planes), its pooled output also written as planes (yp), or both; neither: K11p itself.
+extern "C" int aurppo_conv3x3_pool_planes_f32(const void* x_or_xp, int x_is_planes, const float* w, const float* bias, float* y,
+                                              uint8_t* mask, uint16_t* yp_or_null, int B, int Ci, int Co, int H, int W, int pad,
+                                              void* wop_ws, void* stream) {
+    if (!x_is_planes && !yp_or_null)
+        return aurppo_conv3x3_pool_f32(reinterpret_cast<const float*>(x_or_xp), w, bias, y, mask, B, Ci, Co, H, W, pad, wop_ws, stream);
+    AURPPO_REQUIRE(x_or_xp && mask, AURPPO_EINVAL, "aurppo_conv3x3_pool_planes_f32: null pointer");
+    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_planes_f32: pad=%d (0..2)", pad);
+    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2, Hp = Ho >> 1, Wp = Wo >> 1;
+    ConvPlan pl;
+    pl.p.bias = bias; pl.p.mask = mask;
+    const float* const x = x_is_planes ? nullptr : reinterpret_cast<const float*>(x_or_xp);
+    const unsigned short* const xp = x_is_planes ? reinterpret_cast<const unsigned short*>(x_or_xp) : nullptr;
+    if (const int rc = conv_plan("aurppo_conv3x3_pool_planes_f32", x, w, y, wop_ws, B, Ci, Co, H, W, pad, Hp, Wp, 4ll * B * Hp * Wp, &pl, xp,
+                                 yp_or_null))
+        return rc;
+    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_planes_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    if (xp && yp_or_null) launch_conv_planes<true, true, true>(pl, s);
+    else if (xp) launch_conv_planes<true, true, false>(pl, s);
+    else launch_conv_planes<true, false, true>(pl, s);
+    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool, planes)");
     return AURPPO_OK;
 }
 

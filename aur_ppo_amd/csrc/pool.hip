@@ -17,6 +17,7 @@
 // value displaces it), counts as alive (`!(m <= 0)`), so y is NaN there and the backward routes the gradient to that element.
 #include <type_traits>
 
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
@@ -250,70 +251,24 @@ __global__ __launch_bounds__(kFbThreads) void k_first_block_fwd(const float* __r
                                                                 const float* __restrict__ bias,
                                                                 const float* __restrict__ state, float* __restrict__ y,
                                                                 uint8_t* __restrict__ mask, int Co, int H, int W) {
-    const int Ho = H >> 1, Wo = W >> 1;
-    const int q = blockIdx.x * kFbThreads + threadIdx.x;
-    const int cg = blockIdx.y, b = blockIdx.z;
-    const bool live = q < Ho * Wo;
-    const int ho = live ? q / Wo : 0, wo = live ? q - ho * Wo : 0;
-    const float sv = state[b];
-    // the 4x4 input patch of this pooled cell, per image channel (rows 2ho-1 .. 2ho+2, cols 2wo-1 .. 2wo+2), zero outside
-    float p[CI][4][4];
-#pragma unroll
-    for (int ci = 0; ci < CI; ++ci) {
-        const float* op = obs + ((size_t)b * CI + ci) * H * W;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int h = 2 * ho - 1 + r;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int ww = 2 * wo - 1 + c;
-                const bool in = live && h >= 0 && h < H && ww >= 0 && ww < W;
-                p[ci][r][c] = in ? op[(size_t)(in ? h : 0) * W + (in ? ww : 0)] : 0.0f;
-            }
-        }
-    }
-    // border classes of the four conv positions (rows 2ho, 2ho+1; cols 2wo, 2wo+1) as 0/1 factors: the state plane's
-    // response is the sum of the channel's state taps that fall inside the image = all - border row - border column + corner
-    const float ft = ho == 0 ? 1.0f : 0.0f, fb = 2 * ho + 1 == H - 1 ? 1.0f : 0.0f;
-    const float fl = wo == 0 ? 1.0f : 0.0f, fr = 2 * wo + 1 == W - 1 ? 1.0f : 0.0f;
-    for (int cc = 0; cc < kFbCo; ++cc) {
-        const int c = cg * kFbCo + cc;
-        const float* wc = w + (size_t)c * (CI + 1) * 9;       // uniform address: scalar loads
-        float acc[4];
-        const float bv = bias ? bias[c] : 0.0f;
-        const float* ts = wc + CI * 9;
-        // state plane first, then the bias (the association of base_encoder.forward_split: (conv + state*plane) + bias)
-        const float all = ((ts[0] + ts[1]) + (ts[2] + ts[3])) + ((ts[4] + ts[5]) + (ts[6] + ts[7])) + ts[8];
-        const float r0 = ts[0] + ts[1] + ts[2], r2 = ts[6] + ts[7] + ts[8];
-        const float c0 = ts[0] + ts[3] + ts[6], c2 = ts[2] + ts[5] + ts[8];
-        const float pl[4] = {all - ft * r0 - fl * c0 + ft * fl * ts[0], all - ft * r0 - fr * c2 + ft * fr * ts[2],
-                             all - fb * r2 - fl * c0 + fb * fl * ts[6], all - fb * r2 - fr * c2 + fb * fr * ts[8]};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = 0.0f;
-#pragma unroll
-        for (int ci = 0; ci < CI; ++ci)
-#pragma unroll
-            for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                for (int kw = 0; kw < 3; ++kw) {
-                    const float wv = wc[ci * 9 + kh * 3 + kw];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) acc[u] = fmaf(p[ci][(u >> 1) + kh][(u & 1) + kw], wv, acc[u]);
-                }
-        float m = 0.0f;
-        int k = 0;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float v = (acc[u] + sv * pl[u]) + bv;
-            if (u == 0 || v > m || v != v) { m = v; k = u; }
-        }
-        const bool alive = !(m <= 0.0f);
-        if (live) {
-            const size_t o = (((size_t)b * Co + c) * Ho + ho) * Wo + wo;
-            y[o] = alive ? m : 0.0f;
-            mask[o] = alive ? (uint8_t)k : (uint8_t)4;
-        }
-    }
+    constexpr bool OPL = false;
+    constexpr uint16_t* out_planes = nullptr;
+#define AURPPO_FB_CHANNEL_LOOP
+#include "first_block_fwd_body.h"
+#undef AURPPO_FB_CHANNEL_LOOP
+}
+// The OPL build (first_block_fwd_body.h says what it is): an overload with a second template parameter and a further argument, as
+// conv.hip's POOL builds are -- the kernel above keeps its symbol and its instruction stream.
+template <int CI, bool OPL>
+__global__ __launch_bounds__(kFbThreads) void k_first_block_fwd(const float* __restrict__ obs, const float* __restrict__ w,
+                                                                const float* __restrict__ bias,
+                                                                const float* __restrict__ state, float* __restrict__ y,
+                                                                uint8_t* __restrict__ mask, uint16_t* __restrict__ out_planes, int Co,
+                                                                int H, int W) {
+    static_assert(OPL, "the plain build is k_first_block_fwd<CI>");
+#define AURPPO_FB_CHANNEL_LOOP _Pragma("unroll")
+#include "first_block_fwd_body.h"
+#undef AURPPO_FB_CHANNEL_LOOP
 }
 
 // grid: (1, Co / 16, B): one workgroup of 16 waves per sample and channel group, ONE WAVE PER OUTPUT CHANNEL; a wave walks all
@@ -442,12 +397,13 @@ __global__ __launch_bounds__(kFbBwdThreads) void k_first_block_bwd(const float* 
 
 }  // namespace
 
-extern "C" int aurppo_first_block_fwd_f32(const float* obs, const float* w, const float* bias, const float* state, float* y,
-                                          uint8_t* mask, int B, int Ci, int Co, int H, int W, void* stream) {
-    AURPPO_REQUIRE(obs && w && state && y && mask, AURPPO_EINVAL, "aurppo_first_block_fwd_f32: null pointer");
+namespace {
+// K10's forward behind both of its entries: yp null -- the plain build; else the OPL build, which also writes y's planes
+int first_block_fwd(const char* who, const float* obs, const float* w, const float* bias, const float* state, float* y, uint8_t* mask,
+                    uint16_t* yp, int B, int Ci, int Co, int H, int W, hipStream_t s) {
+    AURPPO_REQUIRE(obs && w && state && y && mask, AURPPO_EINVAL, "%s: null pointer", who);
     AURPPO_REQUIRE(B > 0 && Ci >= 1 && Ci <= 3 && Co > 0 && Co % kFbCo == 0 && Co / kFbCo <= 65535 && H >= 2 && W >= 3,
-                   AURPPO_ESHAPE, "aurppo_first_block_fwd_f32: B=%d Ci=%d Co=%d H=%d W=%d (Ci in 1..3, Co a multiple of 16, W >= 3)", B, Ci, Co, H, W);
-    hipStream_t s = (hipStream_t)stream;
+                   AURPPO_ESHAPE, "%s: B=%d Ci=%d Co=%d H=%d W=%d (Ci in 1..3, Co a multiple of 16, W >= 3)", who, B, Ci, Co, H, W);
     const size_t in_s = (size_t)Ci * H * W, out_s = (size_t)Co * (H / 2) * (W / 2);
     for (int b0 = 0; b0 < B; b0 += 65535) {          // the sample index rides in gridDim.z (<= 65535): larger batches in slices
         const int nb = B - b0 < 65535 ? B - b0 : 65535;
@@ -456,12 +412,31 @@ extern "C" int aurppo_first_block_fwd_f32(const float* obs, const float* w, cons
         const float* st = state + b0;
         float* yy = y + b0 * out_s;
         uint8_t* mm = mask + b0 * out_s;
-        if (Ci == 1) hipLaunchKernelGGL(k_first_block_fwd<1>, grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, Co, H, W);
+        if (yp) {
+            uint16_t* pp = yp + b0 * out_s * 3;      // (three 2-byte planes an element)
+            if (Ci == 1) hipLaunchKernelGGL((k_first_block_fwd<1, true>), grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, pp, Co, H, W);
+            else if (Ci == 2) hipLaunchKernelGGL((k_first_block_fwd<2, true>), grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, pp, Co, H, W);
+            else hipLaunchKernelGGL((k_first_block_fwd<3, true>), grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, pp, Co, H, W);
+        } else if (Ci == 1) hipLaunchKernelGGL(k_first_block_fwd<1>, grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, Co, H, W);
         else if (Ci == 2) hipLaunchKernelGGL(k_first_block_fwd<2>, grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, Co, H, W);
         else hipLaunchKernelGGL(k_first_block_fwd<3>, grid, dim3(kFbThreads), 0, s, o, w, bias, st, yy, mm, Co, H, W);
         AURPPO_LAUNCH_CHECK("k_first_block_fwd");
     }
     return AURPPO_OK;
+}
+}  // namespace
+
+extern "C" int aurppo_first_block_fwd_f32(const float* obs, const float* w, const float* bias, const float* state, float* y,
+                                          uint8_t* mask, int B, int Ci, int Co, int H, int W, void* stream) {
+    return first_block_fwd("aurppo_first_block_fwd_f32", obs, w, bias, state, y, mask, nullptr, B, Ci, Co, H, W, (hipStream_t)stream);
+}
+
+// aurppo_first_block_fwd_f32 that also writes y's planes (include/aurppo.h: uint16 [b][Co / 8][plane][pixel][8]) for K11x's first block
+extern "C" int aurppo_first_block_planes_fwd_f32(const float* obs, const float* w, const float* bias, const float* state, float* y,
+                                                 uint8_t* mask, uint16_t* yp, int B, int Ci, int Co, int H, int W, void* stream) {
+    AURPPO_REQUIRE(yp, AURPPO_EINVAL, "aurppo_first_block_planes_fwd_f32: null pointer");
+    AURPPO_REQUIRE(aligned_to(yp, 16), AURPPO_EINVAL, "aurppo_first_block_planes_fwd_f32: planes not 16-byte aligned");
+    return first_block_fwd("aurppo_first_block_planes_fwd_f32", obs, w, bias, state, y, mask, yp, B, Ci, Co, H, W, (hipStream_t)stream);
 }
 
 extern "C" int aurppo_first_block_bwd_f32(const float* dy, const uint8_t* mask, const float* obs, const float* state,

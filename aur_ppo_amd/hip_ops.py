@@ -768,26 +768,47 @@ def bias_relu_pool2(x, bias=None, scale=None, plane=None):
 
 
 # ------------------------------------------------------------------ K10
+def _planes_like(y):
+    """An uninitialised planes tensor for the fp32 NCHW ``y`` (include/aurppo.h, K11x): int16 (B, C / 8, 3, H * W, 8)."""
+    B, Cc, Hh, Ww = y.shape
+    if Cc % 8 != 0:
+        raise ValueError(f"planes hold whole groups of eight channels, got {Cc}")
+    return torch.empty((B, Cc // 8, 3, Hh * Ww, 8), dtype=torch.int16, device=y.device)
+
+
+def _first_block_fwd(ctx, obs, state, weight, bias, want_planes):
+    """K10's forward for ``_FirstBlock`` (y) and ``_FirstBlockPlanes`` (y and its planes): what is saved is the same."""
+    lib = _lib_or_raise()
+    obs = obs.detach().contiguous()
+    state = state.detach().reshape(-1).to(torch.float32).contiguous()
+    B, Ci, Hh, Ww = obs.shape
+    Co = weight.shape[0]
+    w = weight.detach().contiguous()
+    y = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.float32, device=obs.device)
+    mask = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.uint8, device=obs.device)
+    head = (_ptr(obs), _ptr(w), _optr(bias.detach().contiguous() if bias is not None else None), _ptr(state), _ptr(y),
+            C.c_void_p(mask.data_ptr()))
+    yp = _planes_like(y) if want_planes else None
+    if yp is None:
+        _check(lib.aurppo_first_block_fwd_f32(*head, B, Ci, Co, Hh, Ww, _stream()), "aurppo_first_block_fwd_f32")
+    else:
+        _check(lib.aurppo_first_block_planes_fwd_f32(*head, _ptr(yp, torch.int16), B, Ci, Co, Hh, Ww, _stream()),
+               "aurppo_first_block_planes_fwd_f32")
+    ctx.save_for_backward(obs, state, mask)
+    ctx.dims = (B, Ci, Co, Hh, Ww, bias is not None)
+    if yp is None:
+        return y
+    ctx.mark_non_differentiable(yp)
+    return y, yp
+
+
 class _FirstBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, obs, state, weight, bias):
-        lib = _lib_or_raise()
-        obs = obs.detach().contiguous()
-        state = state.detach().reshape(-1).to(torch.float32).contiguous()
-        B, Ci, Hh, Ww = obs.shape
-        Co = weight.shape[0]
-        w = weight.detach().contiguous()
-        y = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.float32, device=obs.device)
-        mask = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.uint8, device=obs.device)
-        _check(lib.aurppo_first_block_fwd_f32(_ptr(obs), _ptr(w), _optr(bias.detach().contiguous() if bias is not None else None),
-                                              _ptr(state), _ptr(y), C.c_void_p(mask.data_ptr()), B, Ci, Co, Hh, Ww, _stream()),
-               "aurppo_first_block_fwd_f32")
-        ctx.save_for_backward(obs, state, mask)
-        ctx.dims = (B, Ci, Co, Hh, Ww, bias is not None)
-        return y
+        return _first_block_fwd(ctx, obs, state, weight, bias, False)
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, _dyp=None):
         lib = _lib_or_raise()
         obs, state, mask = ctx.saved_tensors
         B, Ci, Co, Hh, Ww, has_bias = ctx.dims
@@ -801,6 +822,13 @@ class _FirstBlock(torch.autograd.Function):
         dw = dw_part.view(B, Co // 16, 16, (Ci + 1) * 9).sum(0).reshape(Co, Ci + 1, 3, 3)
         db = db_part.view(B, Co // 16, 16).sum(0).reshape(Co) if has_bias else None
         return None, None, dw, db
+
+
+class _FirstBlockPlanes(_FirstBlock):
+    """K10 that also returns its output's planes (not differentiable); saves and backpropagates what ``_FirstBlock`` does."""
+    @staticmethod
+    def forward(ctx, obs, state, weight, bias):
+        return _first_block_fwd(ctx, obs, state, weight, bias, True)
 
 
 CONV3X3_MIN_PIXELS = 131072
@@ -1037,6 +1065,101 @@ def conv3x3_pool(x, weight, bias, padding):
     return _Conv3x3Pool.apply(x, weight, bias, int(padding))
 
 
+# ------------------------------------------------------------------ K11x: activations kept as bf16 planes
+def split_planes(x):
+    """The planes of an fp32 NCHW ``x`` with whole groups of eight channels (include/aurppo.h, K11x): int16
+    (B, C / 8, 3, H * W, 8), the three bf16 parts of every value in the order K11's lanes read them."""
+    lib = _lib_or_raise()
+    x = x.detach().contiguous()
+    xp = _planes_like(x)
+    B, Cc, Hh, Ww = x.shape
+    _check(lib.aurppo_split_planes_f32(_ptr(x), _ptr(xp, torch.int16), B, Cc, Hh, Ww, _stream()), "aurppo_split_planes_f32")
+    return xp
+
+
+def _planes_of(x, xp):
+    B, Cc, Hh, Ww = x.shape
+    if xp.dtype != torch.int16 or tuple(xp.shape) != (B, Cc // 8, 3, Hh * Ww, 8) or Cc % 8 != 0:
+        raise ValueError(f"planes of shape {tuple(xp.shape)} ({xp.dtype}) do not belong to an input of shape {tuple(x.shape)}")
+    return _ptr(xp, torch.int16)
+
+
+class _Conv3x3Planes(torch.autograd.Function):
+    """``_Conv3x3`` whose forward reads ``xp``, the planes of ``x``; ``x`` itself is saved for the unchanged backward."""
+    @staticmethod
+    def forward(ctx, x, xp, w, pad):
+        lib = _lib_or_raise()
+        x, w = x.contiguous(), w.contiguous()
+        B, Ci, Hh, Ww = x.shape
+        Co = w.shape[0]
+        z = torch.empty((B, Co, Hh + 2 * pad - 2, Ww + 2 * pad - 2), dtype=torch.float32, device=x.device)
+        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
+        _check(lib.aurppo_conv3x3_planes_f32(_planes_of(x, xp), _ptr(w.detach()), _ptr(z), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
+               "aurppo_conv3x3_planes_f32")
+        ctx.save_for_backward(x, w)
+        ctx.pad = int(pad)
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        dx, dw = _conv3x3_grads(g.contiguous(), x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        return dx, None, dw, None
+
+
+def conv3x3_planes(x, xp, weight, padding):
+    """K11 on planes: ``conv3x3(x, weight, padding)``, bit for bit, computed from ``xp`` -- the planes of ``x`` that its producer
+    wrote (``first_block`` / ``conv3x3_pool_planes`` with ``want_planes``, or ``split_planes``).  ``x`` takes the gradient."""
+    return _Conv3x3Planes.apply(x, xp, weight, int(padding))
+
+
+class _Conv3x3PoolPlanes(torch.autograd.Function):
+    """``_Conv3x3Pool`` that reads ``xp`` (when given) instead of ``x`` and / or also returns the planes of ``y`` (not differentiable).
+    It saves what ``_Conv3x3Pool`` saves -- fp32 ``x``, ``w``, the mask -- and its backward is that function's."""
+    @staticmethod
+    def forward(ctx, x, xp, w, bias, pad, want_planes):
+        lib = _lib_or_raise()
+        x, w = x.contiguous(), w.contiguous()
+        B, Ci, Hh, Ww = x.shape
+        Co = w.shape[0]
+        Ho, Wo = Hh + 2 * pad - 2, Ww + 2 * pad - 2
+        y = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.float32, device=x.device)
+        mask = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.uint8, device=x.device)
+        yp = _planes_like(y) if want_planes else None
+        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
+        src = _planes_of(x, xp) if xp is not None else _ptr(x.detach())
+        _check(lib.aurppo_conv3x3_pool_planes_f32(src, int(xp is not None), _ptr(w.detach()),
+                                                  _optr(bias.detach().contiguous() if bias is not None else None), _ptr(y),
+                                                  C.c_void_p(mask.data_ptr()), _optr(yp, torch.int16), B, Ci, Co, Hh, Ww, int(pad),
+                                                  *_ws_stream(ws)), "aurppo_conv3x3_pool_planes_f32")
+        ctx.save_for_backward(x, w, mask)
+        ctx.pad, ctx.has_bias = int(pad), bias is not None
+        if yp is None:
+            return y
+        ctx.mark_non_differentiable(yp)
+        return y, yp
+
+    @staticmethod
+    def backward(ctx, dy, _dyp=None):
+        x, w, mask = ctx.saved_tensors
+        dz, dbias = _pool2_bwd(dy, mask, mask.shape[:2] + (x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2), ctx.has_bias)
+        dx, dw = _conv3x3_grads(dz, x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        return dx, None, dw, dbias, None, None
+
+
+def conv3x3_pool_planes(x, xp, weight, bias, padding, want_planes=False):
+    """K11p on planes: ``conv3x3_pool(x, weight, bias, padding)``, bit for bit, reading ``xp`` (the planes of ``x``; None: ``x`` itself)
+    and, with ``want_planes``, returning ``(y, yp)`` -- ``yp == split_planes(y)``, written by the same launch for the next block."""
+    return _Conv3x3PoolPlanes.apply(x, xp, weight, bias, int(padding), bool(want_planes))
+
+
+def like_gpu(shape):
+    """What the shape rules above ask of a tensor, for an fp32 CUDA tensor of ``shape`` that does not exist yet (a block's output)."""
+    import types
+    shape = tuple(int(v) for v in shape)
+    return types.SimpleNamespace(shape=shape, dtype=torch.float32, is_cuda=True, dim=lambda: len(shape))
+
+
 LINEAR_MIN_ROWS = 32768
 
 
@@ -1112,11 +1235,12 @@ def linear_bias_act(x, w, bias, act=0):
     return _linear_bias_act(x, None, w, bias, act)
 
 
-def first_block(obs, state, weight, bias):
+def first_block(obs, state, weight, bias, want_planes=False):
     """K10: ``max_pool2d(relu(conv2d(cat[obs, state tiled to a plane], weight, bias, padding=1)), 2)`` -- the first block of
     src/nets/base_cnns.py:28-31 on the input of src/models/robot_actor_critic.py:58-59 -- forward and backward without the
-    full-resolution tensors.  ``weight``: (Co, Ci + 1, 3, 3), state plane last; Ci in 1..3, Co a multiple of 16."""
-    return _FirstBlock.apply(obs, state, weight, bias)
+    full-resolution tensors.  ``weight``: (Co, Ci + 1, 3, 3), state plane last; Ci in 1..3, Co a multiple of 16.
+    ``want_planes``: returns ``(y, yp)``, ``yp`` the planes of ``y`` (``split_planes``) written by the same launch."""
+    return (_FirstBlockPlanes if want_planes else _FirstBlock).apply(obs, state, weight, bias)
 
 
 def linear_rows_bias_act(x, rows, w, bias, act=0):

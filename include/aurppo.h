@@ -266,6 +266,31 @@ int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w
 int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci, int Co,
                             int H, int W, int pad, void* wop_ws, void* stream);
 
+/* ---- K11x: hidden activations kept as bf16 planes --------------------------------------------------------------
+ * THE PLANES LAYOUT.  For an fp32 NCHW tensor x (B, C, H, W) with C a multiple of 8, its planes are
+ *     uint16 xp[B][C / 8][3][H * W][8],      xp[b][g][pl][y * W + x][j] = plane pl of x[b][8 g + j][y][x]
+ * where the three planes of a value a are the bf16x3 split every matrix kernel here forms in registers: a0 = bf16(a) (round to
+ * nearest even), a1 = bf16(a - a0), a2 = bf16(a - a0 - a1); a0 + a1 + a2 == a.  The 16 bytes at (b, g, pl, pixel) are the operand
+ * fragment K11's lane builds for channels 8 g .. 8 g + 7 of that pixel; consecutive pixels are consecutive 16-byte pieces.  The
+ * tensor is aurppo_planes_bytes(B, C, H, W) = 6 B C H W bytes (0 for a C that is no multiple of 8 or a dimension < 1) and its base
+ * must be 16-byte aligned.  The split is a function of the value alone, so a kernel that READS planes multiplies the very bits the
+ * fp32 kernel would have split: every result below equals its fp32 sibling's bit for bit.
+ *
+ * aurppo_split_planes_f32: xp = the planes of x (the layout's definition; for inputs no kernel here produced).
+ * aurppo_conv3x3_planes_f32: aurppo_conv3x3_f32's mode 0 with x given as its planes.
+ * aurppo_conv3x3_pool_planes_f32: aurppo_conv3x3_pool_f32 whose input is fp32 x (x_is_planes = 0) or its planes (1), and which,
+ *   with yp_or_null set, also writes the planes of y -- (B, Co / 8, 3, Hp * Wp, 8), Co a multiple of 8, a dead window as the planes
+ *   of 0.0f -- beside y and mask, which are written as before (the backward reads fp32).  Neither: aurppo_conv3x3_pool_f32 itself.
+ * aurppo_first_block_planes_fwd_f32: aurppo_first_block_fwd_f32 (below) that also writes the planes of y.
+ * All refuse before their first launch, with nothing written: AURPPO_EINVAL for a NULL or a planes pointer off its 16-byte
+ * boundary, AURPPO_ESHAPE for what their fp32 siblings refuse and for planes of a channel count that is no multiple of 8. */
+size_t aurppo_planes_bytes(int B, int C, int H, int W);
+int aurppo_split_planes_f32(const float* x, uint16_t* xp, int B, int C, int H, int W, void* stream);
+int aurppo_conv3x3_planes_f32(const uint16_t* xp, const float* w, float* z, int B, int Ci, int Co, int H, int W, int pad,
+                              void* wop_ws, void* stream);
+int aurppo_conv3x3_pool_planes_f32(const void* x_or_xp, int x_is_planes, const float* w, const float* bias, float* y, uint8_t* mask,
+                                   uint16_t* yp_or_null, int B, int Ci, int Co, int H, int W, int pad, void* wop_ws, void* stream);
+
 /* nn.Linear without its bias on the same arithmetic (the MLP policies wider than the fused steps cover, hidden_dim > 128:
  * src/nets/nets.py:21-27,33-39,45-51 per layer).  mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T, any K_w >= 1;
  * mode 1 (gradient with respect to the input; x is dY): y (M, K_w) = x (M, N_w) . w, N_w a multiple of 16.  Row-major fp32.
@@ -545,6 +570,9 @@ int aurppo_weighted_batch_sum_f32(const float* x, const float* w, float* out, in
  * be a multiple of 16, W at least 3. */
 int aurppo_first_block_fwd_f32(const float* obs, const float* w, const float* bias, const float* state, float* y,
                                uint8_t* mask, int B, int Ci, int Co, int H, int W, void* stream);
+/* ... and y's planes (K11x above: uint16 yp[B][Co / 8][3][(H / 2) * (W / 2)][8], 16-byte aligned) beside y and mask */
+int aurppo_first_block_planes_fwd_f32(const float* obs, const float* w, const float* bias, const float* state, float* y,
+                                      uint8_t* mask, uint16_t* yp, int B, int Ci, int Co, int H, int W, void* stream);
 int aurppo_first_block_bwd_f32(const float* dy, const uint8_t* mask, const float* obs, const float* state,
                                float* dw_part, float* db_part, int B, int Ci, int Co, int H, int W, void* stream);
 
