@@ -36,12 +36,20 @@ struct LinArgs {
 // The two kernel templates share one body text, linear_body.h (it says why a text): KTAIL is a constant of the including kernel.
 template <int NB, bool ROWS = false, bool GATE = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
-    constexpr bool KTAIL = false;
+    constexpr bool KTAIL = false, GRAD = GATE;
 #include "linear_body.h"
 }
 template <int NB, bool ROWS>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_tail(const LinArgs a) {
-    constexpr bool GATE = false, KTAIL = true;
+    constexpr bool GATE = false, GRAD = false, KTAIL = true;
+#include "linear_body.h"
+}
+// GRAD: the product is an input gradient (mode 1), whose k-steps change sign in another order in every other block of 32 rows
+// (linear_body.h says why).  The GATE builds above are input gradients already; this overload is the plain mode-1 product.
+template <int NB, bool ROWS, bool GATE, bool GRAD>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
+    static_assert(GRAD && !ROWS && !GATE, "the plain input gradient");
+    constexpr bool KTAIL = false;
 #include "linear_body.h"
 }
 
@@ -92,14 +100,15 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const Wgr
 // The two halves of a product, host side: the filter into operand order (linear_prep, conv.hip) and k_linear from an operand copy that
 // exists.  linear_impl does both per call; the layered rollout step (layered.hip) builds the copies once per rollout.
 static int linear_launch(const float* x, const unsigned short* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                         hipStream_t s, const int32_t* rows, const float* h) {
+                         hipStream_t s, const int32_t* rows, const float* h, bool grad = false) {
     LinArgs a;
     a.x = x; a.wop = wop; a.y = y; a.M = M; a.K = K; a.N = N;
     a.bias = bias; a.act = act; a.rows = rows; a.h = h;
     const Bf3Grid gr = bf3_grid(M, N);
     AURPPO_REQUIRE(gr.n_mb * gr.n_ng < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_f32: grid too large");
     a.n_mb = (int)gr.n_mb;
-    AURPPO_REQUIRE(K % 16 == 0 || !h, AURPPO_ESHAPE, "aurppo_linear_f32: the input gradient's inner dimension %d (a multiple of 16)", K);
+    AURPPO_REQUIRE(K % 16 == 0 || !(h || grad), AURPPO_ESHAPE, "aurppo_linear_f32: the input gradient's inner dimension %d (a multiple of 16)", K);
+    AURPPO_REQUIRE(!(grad && rows), AURPPO_EINVAL, "aurppo_linear_f32: an input gradient through an index");
     const dim3 g((unsigned)(gr.n_mb * gr.n_ng)), blk(kConvThreads);
     bf3_with_nb(gr.NB, [&](auto nb) {
         constexpr int NB = decltype(nb)::value;
@@ -107,6 +116,7 @@ static int linear_launch(const float* x, const unsigned short* wop, const float*
             if (rows) hipLaunchKernelGGL((k_linear_tail<NB, true>), g, blk, 0, s, a);
             else hipLaunchKernelGGL((k_linear_tail<NB, false>), g, blk, 0, s, a);
         } else if (h) hipLaunchKernelGGL((k_linear<NB, false, true>), g, blk, 0, s, a);
+        else if (grad) hipLaunchKernelGGL((k_linear<NB, false, false, true>), g, blk, 0, s, a);
         else if (rows) hipLaunchKernelGGL((k_linear<NB, true, false>), g, blk, 0, s, a);
         else hipLaunchKernelGGL(k_linear<NB>, g, blk, 0, s, a);
     });
@@ -128,7 +138,7 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     hipStream_t s = (hipStream_t)stream;
     unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
     if (const int rc = linear_prep(w, K_w, N_w, mode, wop, s)) return rc;
-    return linear_launch(x, wop, bias, act, y, M, K, N, s, rows, h);
+    return linear_launch(x, wop, bias, act, y, M, K, N, s, rows, h, mode == 1);
 }
 
 extern "C" int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,

@@ -1,7 +1,7 @@
-// The body of k_linear and k_linear_tail (linear.hip), included INSIDE each of the two kernel templates: NB, ROWS, GATE and KTAIL are
-// compile-time constants of the including kernel, `a` its LinArgs.  One text, so the two cannot drift; compiled in place, so the
+// The body of k_linear and k_linear_tail (linear.hip), included INSIDE each of the two kernel templates: NB, ROWS, GATE, GRAD and KTAIL
+// are compile-time constants of the including kernel, `a` its LinArgs.  One text, so the two cannot drift; compiled in place, so the
 // aligned kernels keep their names and their instruction streams (through a shared __device__ function they kept neither).
-    static_assert(!(GATE && KTAIL), "the input gradient's inner dimension is a hidden width");
+    static_assert(!(GRAD && KTAIL) && (GRAD || !GATE), "the input gradient's inner dimension is a hidden width");
     constexpr int kChunkBytes = kKC * NB * 3 * 1024;
     __shared__ __attribute__((aligned(16))) char s_b[2 * kChunkBytes];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -72,13 +72,24 @@
             if (ks < KS) {
                 float4 (&cur)[kMB][2] = abuf[kk];
                 if (ks + 1 < KS) load_a(ks + 1, abuf[kk ^ 1]);
+                // every k-step is summed from zero and added once, every other one negated (bf3_gemm.h::mma32x3_step): ks and kk have the
+                // same parity, and the A values of a negated step are negated BEFORE the split (the split of -a is the negated split of a).
+                // GRAD (the input gradient): the wave's two row blocks negate OPPOSITE steps.  Where the steps differ in size -- an
+                // output gradient whose columns differ in scale: the cut follows the largest term of a step -- the cuts of neighbouring
+                // steps do not cancel, and what is left has one sign for every row.  What consumes a gradient sums it over rows (the
+                // weight and bias gradients of the layer below): with the other sign in the next block of 32 rows that sum cancels it.
+                // The forward product keeps one pattern: a row's result must not depend on where the row stands (the rollout's
+                // log-prob and value are the update's bit for bit).
                 Frag3 A[kMB];
 #pragma unroll
                 for (int mb = 0; mb < kMB; ++mb) {
+                    const bool NEG = kStepNeg(kk + (GRAD ? mb : 0));     // (a constant once the loops are unrolled)
                     const float c[8] = {cur[mb][0].x, cur[mb][0].y, cur[mb][0].z, cur[mb][0].w, cur[mb][1].x, cur[mb][1].y, cur[mb][1].z, cur[mb][1].w};
                     unsigned p[4][3];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) split3(valid[mb] ? c[2 * q] : 0.0f, valid[mb] ? c[2 * q + 1] : 0.0f, p[q][0], p[q][1], p[q][2]);
+                    for (int q = 0; q < 4; ++q)
+                        split3(valid[mb] ? (NEG ? -c[2 * q] : c[2 * q]) : 0.0f, valid[mb] ? (NEG ? -c[2 * q + 1] : c[2 * q + 1]) : 0.0f, p[q][0],
+                               p[q][1], p[q][2]);
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
                         const u32x4 v = {p[0][pl], p[1][pl], p[2][pl], p[3][pl]};
@@ -91,7 +102,9 @@
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) Bf.p[pl] = *reinterpret_cast<const bf16x8*>(bsrc + ((kk * NB + nb) * 3 + pl) * 1024);
 #pragma unroll
-                    for (int mb = 0; mb < kMB; ++mb) acc[mb][nb] = mma32x3(A[mb], Bf, acc[mb][nb]);
+                    for (int mb = 0; mb < kMB; ++mb)
+                        acc[mb][nb] = kStepNeg(kk + (GRAD ? mb : 0)) ? mma32x3_step<true>(A[mb], Bf, acc[mb][nb])
+                                                                     : mma32x3_step<false>(A[mb], Bf, acc[mb][nb]);
                 }
             }
         }

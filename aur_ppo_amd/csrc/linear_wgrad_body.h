@@ -73,10 +73,19 @@
         for (int ks = 0; ks < 2; ++ks) {
             const Frag3 A0 = x_cols(imgA + wn * 3 * kXPlane, ks, 0, lane), A1 = x_cols(imgA + wn * 3 * kXPlane, ks, 32, lane);
             const Frag3 B0 = x_cols(imgB + wk * 3 * kXPlane, ks, 0, lane), B1 = x_cols(imgB + wk * 3 * kXPlane, ks, 32, lane);
-            acc[0][0] = mma32x3(A0, B0, acc[0][0]);
-            acc[0][1] = mma32x3(A0, B1, acc[0][1]);
-            acc[1][0] = mma32x3(A1, B0, acc[1][0]);
-            acc[1][1] = mma32x3(A1, B1, acc[1][1]);
+            // every k-step is summed from zero and added once, the second of a chunk negated (bf3_gemm.h::mma32x3_step)
+            if (kStepNeg(ks)) {
+                const Frag3 N0 = neg3(A0), N1 = neg3(A1);
+                acc[0][0] = mma32x3_step<true>(N0, B0, acc[0][0]);
+                acc[0][1] = mma32x3_step<true>(N0, B1, acc[0][1]);
+                acc[1][0] = mma32x3_step<true>(N1, B0, acc[1][0]);
+                acc[1][1] = mma32x3_step<true>(N1, B1, acc[1][1]);
+            } else {
+                acc[0][0] = mma32x3_step<false>(A0, B0, acc[0][0]);
+                acc[0][1] = mma32x3_step<false>(A0, B1, acc[0][1]);
+                acc[1][0] = mma32x3_step<false>(A1, B0, acc[1][0]);
+                acc[1][1] = mma32x3_step<false>(A1, B1, acc[1][1]);
+            }
         }
     }
     // C[m = dY column][n = X column]: the lane holds the X column, its registers the dY columns -- rows of `part` are contiguous over the lanes

@@ -17,6 +17,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from aur_ppo_amd import _lib                              # noqa: E402
+if os.environ.get("AURPPO_LIB"):                          # another build of the library (tools/build_variant.sh), as tools/bench_wgrad.py
+    _lib.LIB_PATH = os.environ["AURPPO_LIB"]
 from aur_ppo_amd import hip_ops as H                       # noqa: E402
 from aur_ppo_amd.actor_critic import actor_critic         # noqa: E402
 from aur_ppo_amd.flat import FlatBucket                   # noqa: E402
@@ -79,7 +82,7 @@ def one_shape(layers, D):
 
 def main():
     out = [one_shape(layers, D) for layers, D in SHAPES]
-    print(json.dumps(dict(hidden=HIDDEN, A=A, M=M, B=B, rounds=7, steps_per_batch=STEPS, warmup_steps=WARMUP, shapes=out,
+    print(json.dumps(dict(library=os.environ.get("AURPPO_LIB", "default build"), hidden=HIDDEN, A=A, M=M, B=B, rounds=7, steps_per_batch=STEPS, warmup_steps=WARMUP, shapes=out,
                           note="us per step, eager, host included; one batch per arm and round, arms alternating; layered_minibatch "
                                "alone includes clip + Adam"), indent=1))
 
