@@ -1,9 +1,9 @@
 """Plain-CNN encoder / actor / critic of the robot policy with the reference's module layout and
 state-dict keys (src/nets/base_cnns.py:12-84): ``base_encoder.conv.{0,3,6,9,12,14,17}``,
 ``base_actor.{conv,mean_linear}``, ``base_critic.{conv,critic.{0,2}}``; xavier init as upstream.
-The convolutions are stock PyTorch-ROCm (MIOpen); on the GPU the element-wise tail of every conv + ReLU + max-pool block
-(bias add, ReLU, 2x2 max-pool, and for the first block the tiled gripper-state channel) is K9, one fused HIP pass forward
-and one backward (csrc/pool.hip): rocprof put 53 % of robot_ppo.update's GPU time in those memory-bound passes."""
+On the GPU (``base_encoder._route``) the split first block is K10, a hidden 3x3 convolution is K11 where its shape rule holds (MIOpen's
+kernel elsewhere) and its block's bias / ReLU / max-pool tail is K9; opt-in, a whole hidden block is one launch (K11p,
+AURPPO_K11_POOL=1) that hands its output on as bf16 planes too (K11x, AURPPO_K11_PLANES=1).  On the CPU the stock torch modules run."""
 from __future__ import annotations
 
 import os
@@ -68,49 +68,48 @@ class base_encoder(nn.Module):
         like = H.like_gpu(shape)
         return H.conv3x3_pool_supported(like, mods[j]) if self._is_triple(mods, j) else H.conv3x3_supported(like, mods[j])
 
+    def _route(self, H, mods, i, x, has_planes, own_tail):
+        """How ``mods[i]`` runs on the CUDA tensor ``x``: (route, whether the planes of its output are wanted).  A (Conv2d, ReLU,
+        MaxPool2d(2)) triple: "k11x" (one launch that reads its predecessor's planes, writes its successor's, or both), "k11p" (one
+        launch), "k11+k9" or "conv+k9" (torch's convolution without bias, then K9).  Anything else: "k11" (on planes where they came
+        in) or "module".  ``own_tail``: the split first block, whose weight is a slice and whose tail carries the state plane -- K9's."""
+        m, triple = mods[i], self._is_triple(mods, i)
+        fused = self.fused_conv and not own_tail and isinstance(m, nn.Conv2d)      # K11 and its kin take the layer's own weight
+        if triple and fused and (self.fused_planes or self.fused_block) and H.conv3x3_pool_supported(x, m):
+            ho, wo = ((s + 2 * m.padding[0] - 2) // 2 for s in x.shape[2:])
+            want = self._reads_planes(H, mods, i + 3, (x.shape[0], m.out_channels, ho, wo))
+            if self.fused_planes and (has_planes or want):
+                return "k11x", want
+            if self.fused_block:
+                return "k11p", False
+        k11 = fused and H.conv3x3_supported(x, m)
+        return (("k11+k9" if k11 else "conv+k9") if triple else ("k11" if k11 else "module")), False
+
     def _blocks(self, x, start, scale=None, plane=None, first_weight=None, xp=None):
-        """Run self.conv[start:] on x; on the GPU every (Conv2d, ReLU, MaxPool2d(2)) triple becomes convolution without bias
-        + K9.  ``scale`` / ``plane`` / ``first_weight`` belong to the first convolution when it runs in split form; ``xp``: the
-        planes of ``x`` where its producer wrote them (K11x)."""
-        mods = list(self.conv)
-        use = self.fused_pool and x.is_cuda
-        if use:
+        """Run self.conv[start:] on x, on the GPU every module or (Conv2d, ReLU, MaxPool2d(2)) triple by its ``_route``.  ``scale`` / ``plane``
+        / ``first_weight``: the first convolution's when it runs in split form; ``xp``: the planes of ``x`` where its producer wrote them."""
+        mods, H = list(self.conv), None
+        if self.fused_pool and x.is_cuda:
             from . import hip_ops as H      # raises without the built library: there is no silent fallback on a GPU box
         i = start
         while i < len(mods):
-            m = mods[i]
-            triple = self._is_triple(mods, i)
-            xp_in, xp = xp, None            # planes belong to the tensor they were written beside: one consumer, then gone
-            if use and triple:
-                w = first_weight if (i == start and first_weight is not None) else m.weight
-                own_tail = i == start and (scale is not None or plane is not None)      # the split first block's state plane: K9's
-                if self.fused_planes and self.fused_conv and w is m.weight and not own_tail and H.conv3x3_pool_supported(x, m):
-                    pad = m.padding[0]
-                    out_shape = (x.shape[0], m.out_channels, (x.shape[2] + 2 * pad - 2) // 2, (x.shape[3] + 2 * pad - 2) // 2)
-                    want = self._reads_planes(H, mods, i + 3, out_shape)
-                    if xp_in is not None or want:       # K11x: reads its predecessor's planes, writes its successor's, or both
-                        x = H.conv3x3_pool_planes(x, xp_in, m.weight, m.bias, pad, want)
-                        if want:
-                            x, xp = x
-                        i += 3
-                        continue
-                if self.fused_block and self.fused_conv and w is m.weight and not own_tail and H.conv3x3_pool_supported(x, m):
-                    x = H.conv3x3_pool(x, m.weight, m.bias, m.padding[0])       # K11p: z is never written
-                    i += 3
-                    continue
-                if self.fused_conv and w is m.weight and H.conv3x3_supported(x, m):
-                    z = H.conv3x3(x, w, m.padding[0])
-                else:
-                    z = torch.nn.functional.conv2d(x, w, None, stride=m.stride, padding=m.padding)
-                x = H.bias_relu_pool2(z, m.bias, scale if i == start else None, plane if i == start else None)
-                i += 3
-            elif use and self.fused_conv and isinstance(m, nn.Conv2d) and H.conv3x3_supported(x, m):
+            m, xp_in, xp = mods[i], xp, None        # planes belong to the tensor they were written beside: one consumer, then gone
+            own_tail = any(t is not None for t in (scale, plane, first_weight))
+            route, want = self._route(H, mods, i, x, xp_in is not None, own_tail) if H is not None else ("module", False)
+            if route in ("k11x", "k11p"):       # z is never written
+                x = H.conv3x3_pool(x, m.weight, m.bias, m.padding[0]) if route == "k11p" else H.conv3x3_pool_planes(x, xp_in, m.weight, m.bias, m.padding[0], want)
+                x, xp = x if want else (x, None)
+            elif route in ("k11+k9", "conv+k9"):
+                w = m.weight if first_weight is None else first_weight
+                z = H.conv3x3(x, w, m.padding[0]) if route == "k11+k9" else torch.nn.functional.conv2d(x, w, None, stride=m.stride, padding=m.padding)
+                x = H.bias_relu_pool2(z, m.bias, scale, plane)
+            elif route == "k11":
                 z = H.conv3x3(x, m.weight, m.padding[0]) if xp_in is None else H.conv3x3_planes(x, xp_in, m.weight, m.padding[0])
                 x = z + m.bias.reshape(1, -1, 1, 1)
-                i += 1
             else:
                 x = m(x)
-                i += 1
+            i += 1 if route in ("k11", "module") else 3
+            scale = plane = first_weight = None       # (the split form's, spent on the first module)
         return x
 
     def forward(self, x):
@@ -128,8 +127,7 @@ class base_encoder(nn.Module):
                 and isinstance(mods[1], nn.ReLU) and isinstance(mods[2], nn.MaxPool2d) and mods[2].kernel_size in (2, (2, 2))):
             # K10: convolution of the image channels and of the tiled state, bias, ReLU and the pool in one kernel
             from . import hip_ops as H
-            out_shape = (obs.shape[0], first.out_channels, obs.shape[2] // 2, obs.shape[3] // 2)
-            if self._reads_planes(H, list(mods), 3, out_shape):
+            if self._reads_planes(H, list(mods), 3, (obs.shape[0], first.out_channels, obs.shape[2] // 2, obs.shape[3] // 2)):
                 y, yp = H.first_block(obs, state, first.weight, first.bias, want_planes=True)
                 return self._blocks(y, 3, xp=yp)
             return self._blocks(H.first_block(obs, state, first.weight, first.bias), 3)

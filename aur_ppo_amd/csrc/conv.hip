@@ -438,20 +438,40 @@ __global__ __launch_bounds__(256) void k_fold_slices_bias(const float* __restric
     out[i] = fold_slices_at(part, S, n, i);
 }
 
-// The host plan K11 and K11p share: every refusal (under the entry's name `who`), the argument block, the grid and the build, all of it
-// before the entry's first launch.  cin / cout / p are the product's own (the entry has mapped its mode); Ho x Wo is the map z holds
-// and M the product's rows -- K11: the output pixels; K11p: the pooled map and the four positions of each of its windows.
-// K11x: xp (the input as planes, x then null) and / or yp (the output's planes, K11p's epilogue only) -- both 16-byte aligned, yp with whole
-// groups of eight output channels.
+// The host side of K11's four forward entries (first_block_fwd of pool.hip is the model): every refusal under the entry's name `who`, then
+// the argument block, the grid and the build, the filter's operand copy (k_conv_prep of the (Co_w, Ci_w, 3, 3) filter, transposed and
+// flipped for an input gradient) and the product -- every refusal before the first launch.  cin / cout / p are the product's own (the
+// entry has mapped its mode).  `pool`: K11p -- z and mask hold the pooled map, the product's rows are the four positions of each of its
+// windows.  `planes`: a K11x entry -- xp (the input as planes, x then null) and / or yp (the pooled output's planes, K11p's epilogue only),
+// both 16-byte aligned, yp with whole groups of eight output channels.
 struct ConvPlan {
-    ConvPoolArgs p;                  // (K11 launches with p.c alone)
+    ConvPlanesArgs q;                // (K11 launches with q.p.c alone, K11p with q.p)
     Bf3Grid g;
     bool buf;                        // the BUF builds
-    const unsigned short* xp;        // K11x's two further arguments (null: the fp32 builds)
-    unsigned short* yp;
 };
-int conv_plan(const char* who, const float* x, const float* w, float* z, void* wop_ws, int B, int cin, int cout, int H, int W, int p,
-              int Ho, int Wo, long long M, ConvPlan* pl, const unsigned short* xp = nullptr, unsigned short* yp = nullptr) {
+template <bool POOL, bool XPL, bool OPL>
+void launch_conv(const ConvPlan& pl, hipStream_t s) {
+    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
+    bf3_with_nb(pl.g.NB, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        if constexpr (XPL || OPL) {
+            if (pl.buf) hipLaunchKernelGGL((k_conv3x3<NB, true, POOL, XPL, OPL>), g, blk, 0, s, pl.q);
+            else hipLaunchKernelGGL((k_conv3x3<NB, false, POOL, XPL, OPL>), g, blk, 0, s, pl.q);
+        } else if constexpr (POOL) {
+            if (pl.buf) hipLaunchKernelGGL((k_conv3x3<NB, true, true>), g, blk, 0, s, pl.q.p);
+            else hipLaunchKernelGGL((k_conv3x3<NB, false, true>), g, blk, 0, s, pl.q.p);
+        } else {
+            if (pl.buf) hipLaunchKernelGGL((k_conv3x3<NB, true>), g, blk, 0, s, pl.q.p.c);
+            else hipLaunchKernelGGL((k_conv3x3<NB, false>), g, blk, 0, s, pl.q.p.c);
+        }
+    });
+}
+int conv_fwd(const char* who, bool pool, bool planes, const float* x, const unsigned short* xp, const float* w, const float* bias, float* z,
+             uint8_t* mask, unsigned short* yp, void* wop_ws, int B, int cin, int cout, int H, int W, int p, int Co_w, int Ci_w,
+             int transpose_flip, hipStream_t s) {
+    // what K11p and K11x add to K11's pointers is looked at ahead of the padding, K11's own behind it
+    AURPPO_REQUIRE((!pool || mask) && (!planes || x || xp), AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(p >= 0 && p <= 2, AURPPO_ESHAPE, "%s: pad=%d (0..2)", who, transpose_flip ? 2 - p : p);      // (the entry's own pad)
     AURPPO_REQUIRE((x || xp) && w && z && wop_ws, AURPPO_EINVAL, "%s: null pointer", who);
     AURPPO_REQUIRE(aligned_to(xp, 16) && aligned_to(yp, 16), AURPPO_EINVAL, "%s: planes not 16-byte aligned", who);
     AURPPO_REQUIRE(B > 0 && H > 0 && W > 0 && cin > 0 && cout > 0 && cin % 16 == 0, AURPPO_ESHAPE,
@@ -460,19 +480,37 @@ int conv_plan(const char* who, const float* x, const float* w, float* z, void* w
     AURPPO_REQUIRE((size_t)B * cin * H * W < ((size_t)1 << 40) && aligned_to(wop_ws, 16), AURPPO_ESHAPE,
                    "%s: operand too large / workspace not 16-byte aligned", who);
     AURPPO_REQUIRE(!yp || cout % 8 == 0, AURPPO_ESHAPE, "%s: %d output channels as planes (a multiple of 8)", who, cout);
-    pl->xp = xp; pl->yp = yp;
-    ConvArgs& a = pl->p.c;
+    ConvPlan pl{};
+    pl.q.p.bias = bias; pl.q.p.mask = mask; pl.q.xp = xp; pl.q.yp = yp;
+    ConvArgs& a = pl.q.p.c;
     a.x = x; a.wop = reinterpret_cast<unsigned short*>(wop_ws); a.z = z;
-    a.B = B; a.Cin = cin; a.H = H; a.W = W; a.Cout = cout; a.Ho = Ho; a.Wo = Wo; a.pad = p;
-    a.M = M;
+    a.B = B; a.Cin = cin; a.H = H; a.W = W; a.Cout = cout; a.pad = p;
+    a.Ho = H + 2 * p - 2; a.Wo = W + 2 * p - 2;
+    if (pool) { a.Ho >>= 1; a.Wo >>= 1; }
+    a.M = (pool ? 4ll : 1ll) * B * a.Ho * a.Wo;
     a.CG = cin / 16;
-    pl->g = bf3_grid(M, cout);
-    AURPPO_REQUIRE(pl->g.n_mb < (1ll << 30), AURPPO_ESHAPE, "%s: too many pixel blocks", who);
-    a.n_mb4 = (int)pl->g.n_mb;
-    AURPPO_REQUIRE(pl->g.n_mb * pl->g.n_ng < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", who);
+    pl.g = bf3_grid(a.M, cout);
+    AURPPO_REQUIRE(pl.g.n_mb < (1ll << 30), AURPPO_ESHAPE, "%s: too many pixel blocks", who);
+    a.n_mb4 = (int)pl.g.n_mb;
+    AURPPO_REQUIRE(pl.g.n_mb * pl.g.n_ng < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", who);
+    AURPPO_REQUIRE(!pool || (a.Ho >= 1 && a.Wo >= 1), AURPPO_ESHAPE, "%s: no whole 2 x 2 window in a %d x %d map", who, H + 2 * p - 2,
+                   W + 2 * p - 2);
     // buffer loads address 32 bits: inputs under 4 GB (minus the slack a negative tap offset may wrap through); larger ones keep 64-bit addresses
     // (planes hold 6 bytes an element: the same limit, reached 1.5 x sooner)
-    pl->buf = (size_t)B * cin * H * W * (xp ? 6 : 4) < ((size_t)1 << 32) - ((size_t)1 << 20);
+    pl.buf = (size_t)B * cin * H * W * (xp ? 6 : 4) < ((size_t)1 << 32) - ((size_t)1 << 20);
+    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co_w, Ci_w, cin, cout, transpose_flip, reinterpret_cast<unsigned short*>(wop_ws), 9);
+    AURPPO_LAUNCH_CHECK("k_conv_prep");
+    if (!planes) {
+        if (!pool) launch_conv<false, false, false>(pl, s);
+        else launch_conv<true, false, false>(pl, s);
+        AURPPO_LAUNCH_CHECK(pool ? "k_conv3x3 (pool)" : "k_conv3x3");
+    } else {
+        if (!pool) launch_conv<false, true, false>(pl, s);
+        else if (xp && yp) launch_conv<true, true, true>(pl, s);
+        else if (xp) launch_conv<true, true, false>(pl, s);
+        else launch_conv<true, false, true>(pl, s);
+        AURPPO_LAUNCH_CHECK(pool ? "k_conv3x3 (pool, planes)" : "k_conv3x3 (planes)");
+    }
     return AURPPO_OK;
 }
 
@@ -532,44 +570,17 @@ extern "C" size_t aurppo_conv3x3_wop_bytes(int cin_gemm, int cout_gemm) {
 extern "C" int aurppo_conv3x3_f32(const float* x, const float* w, float* z, int B, int Ci_w, int Co_w, int H, int W, int pad,
                                   int mode, void* wop_ws, void* stream) {
     AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_conv3x3_f32: mode %d", mode);
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_f32: pad=%d (0..2)", pad);
     const int cin = mode == 0 ? Ci_w : Co_w, cout = mode == 0 ? Co_w : Ci_w, p = mode == 0 ? pad : 2 - pad;
-    const int Ho = H + 2 * p - 2, Wo = W + 2 * p - 2;
-    ConvPlan pl;
-    if (const int rc = conv_plan("aurppo_conv3x3_f32", x, w, z, wop_ws, B, cin, cout, H, W, p, Ho, Wo, (long long)B * Ho * Wo, &pl)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co_w, Ci_w, cin, cout, mode, reinterpret_cast<unsigned short*>(wop_ws), 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
-    bf3_with_nb(pl.g.NB, [&](auto nb) {
-        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true>), g, blk, 0, s, pl.p.c);
-        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false>), g, blk, 0, s, pl.p.c);
-    });
-    AURPPO_LAUNCH_CHECK("k_conv3x3");
-    return AURPPO_OK;
+    return conv_fwd("aurppo_conv3x3_f32", false, false, x, nullptr, w, nullptr, z, nullptr, nullptr, wop_ws, B, cin, cout, H, W, p, Co_w,
+                    Ci_w, mode, (hipStream_t)stream);
 }
 
 // K11p: y, mask = max_pool2d(relu(conv2d(x, w, padding = pad) + bias[c]), 2) with K9's semantics; x (B, Ci, H, W), w (Co, Ci, 3, 3),
 // y / mask (B, Co, (H + 2 pad - 2) >> 1, (W + 2 pad - 2) >> 1).  Refuses what mode 0 above refuses, and a map without a whole window.
 extern "C" int aurppo_conv3x3_pool_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* mask, int B, int Ci,
                                        int Co, int H, int W, int pad, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(mask, AURPPO_EINVAL, "aurppo_conv3x3_pool_f32: null pointer");
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: pad=%d (0..2)", pad);
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2, Hp = Ho >> 1, Wp = Wo >> 1;
-    ConvPlan pl;
-    pl.p.bias = bias; pl.p.mask = mask;
-    if (const int rc = conv_plan("aurppo_conv3x3_pool_f32", x, w, y, wop_ws, B, Ci, Co, H, W, pad, Hp, Wp, 4ll * B * Hp * Wp, &pl)) return rc;
-    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
-    bf3_with_nb(pl.g.NB, [&](auto nb) {
-        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true, true>), g, blk, 0, s, pl.p);
-        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false, true>), g, blk, 0, s, pl.p);
-    });
-    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool)");
-    return AURPPO_OK;
+    return conv_fwd("aurppo_conv3x3_pool_f32", true, false, x, nullptr, w, bias, y, mask, nullptr, wop_ws, B, Ci, Co, H, W, pad, Co, Ci, 0,
+                    (hipStream_t)stream);
 }
 
 // ---- K11x: activations as bf16 planes (include/aurppo.h: the layout, and what each entry refuses)
@@ -591,34 +602,11 @@ extern "C" int aurppo_split_planes_f32(const float* x, uint16_t* xp, int B, int 
     return AURPPO_OK;
 }
 
-namespace {
-template <bool POOL, bool XPL, bool OPL>
-void launch_conv_planes(const ConvPlan& pl, hipStream_t s) {
-    const ConvPlanesArgs q{pl.p, pl.xp, pl.yp};
-    const dim3 g((unsigned)(pl.g.n_mb * pl.g.n_ng)), blk(kConvThreads);
-    bf3_with_nb(pl.g.NB, [&](auto nb) {
-        if (pl.buf) hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, true, POOL, XPL, OPL>), g, blk, 0, s, q);
-        else hipLaunchKernelGGL((k_conv3x3<decltype(nb)::value, false, POOL, XPL, OPL>), g, blk, 0, s, q);
-    });
-}
-}  // namespace
-
 // K11 on planes: z = conv2d(x, w, padding = pad) for the x whose planes xp holds -- aurppo_conv3x3_f32's mode 0, bit for bit.
 extern "C" int aurppo_conv3x3_planes_f32(const uint16_t* xp, const float* w, float* z, int B, int Ci, int Co, int H, int W, int pad,
                                          void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(xp, AURPPO_EINVAL, "aurppo_conv3x3_planes_f32: null pointer");
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_planes_f32: pad=%d (0..2)", pad);
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-    ConvPlan pl;
-    pl.p.bias = nullptr; pl.p.mask = nullptr;
-    if (const int rc = conv_plan("aurppo_conv3x3_planes_f32", nullptr, w, z, wop_ws, B, Ci, Co, H, W, pad, Ho, Wo, (long long)B * Ho * Wo, &pl, xp))
-        return rc;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    launch_conv_planes<false, true, false>(pl, s);
-    AURPPO_LAUNCH_CHECK("k_conv3x3 (planes)");
-    return AURPPO_OK;
+    return conv_fwd("aurppo_conv3x3_planes_f32", false, true, nullptr, xp, w, nullptr, z, nullptr, nullptr, wop_ws, B, Ci, Co, H, W, pad, Co,
+                    Ci, 0, (hipStream_t)stream);
 }
 
 // K11p with its input read as planes (x_is_planes), its pooled output also written as planes (yp), or both; neither: K11p itself.
@@ -627,25 +615,10 @@ extern "C" int aurppo_conv3x3_pool_planes_f32(const void* x_or_xp, int x_is_plan
                                               void* wop_ws, void* stream) {
     if (!x_is_planes && !yp_or_null)
         return aurppo_conv3x3_pool_f32(reinterpret_cast<const float*>(x_or_xp), w, bias, y, mask, B, Ci, Co, H, W, pad, wop_ws, stream);
-    AURPPO_REQUIRE(x_or_xp && mask, AURPPO_EINVAL, "aurppo_conv3x3_pool_planes_f32: null pointer");
-    AURPPO_REQUIRE(pad >= 0 && pad <= 2, AURPPO_ESHAPE, "aurppo_conv3x3_pool_planes_f32: pad=%d (0..2)", pad);
-    const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2, Hp = Ho >> 1, Wp = Wo >> 1;
-    ConvPlan pl;
-    pl.p.bias = bias; pl.p.mask = mask;
     const float* const x = x_is_planes ? nullptr : reinterpret_cast<const float*>(x_or_xp);
     const unsigned short* const xp = x_is_planes ? reinterpret_cast<const unsigned short*>(x_or_xp) : nullptr;
-    if (const int rc = conv_plan("aurppo_conv3x3_pool_planes_f32", x, w, y, wop_ws, B, Ci, Co, H, W, pad, Hp, Wp, 4ll * B * Hp * Wp, &pl, xp,
-                                 yp_or_null))
-        return rc;
-    AURPPO_REQUIRE(Hp >= 1 && Wp >= 1, AURPPO_ESHAPE, "aurppo_conv3x3_pool_planes_f32: no whole 2 x 2 window in a %d x %d map", Ho, Wo);
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_conv_prep, dim3(128), dim3(256), 0, s, w, Co, Ci, Ci, Co, 0, reinterpret_cast<unsigned short*>(wop_ws), 9);
-    AURPPO_LAUNCH_CHECK("k_conv_prep");
-    if (xp && yp_or_null) launch_conv_planes<true, true, true>(pl, s);
-    else if (xp) launch_conv_planes<true, true, false>(pl, s);
-    else launch_conv_planes<true, false, true>(pl, s);
-    AURPPO_LAUNCH_CHECK("k_conv3x3 (pool, planes)");
-    return AURPPO_OK;
+    return conv_fwd("aurppo_conv3x3_pool_planes_f32", true, true, x, xp, w, bias, y, mask, yp_or_null, wop_ws, B, Ci, Co, H, W, pad, Co, Ci, 0,
+                    (hipStream_t)stream);
 }
 
 // K12: dw (Co, Ci, 3, 3) = the gradient of conv2d(x (B, Ci, H, W), w, padding = pad) with respect to w, given the output gradient

@@ -776,36 +776,32 @@ def _planes_like(y):
     return torch.empty((B, Cc // 8, 3, Hh * Ww, 8), dtype=torch.int16, device=y.device)
 
 
-def _first_block_fwd(ctx, obs, state, weight, bias, want_planes):
-    """K10's forward for ``_FirstBlock`` (y) and ``_FirstBlockPlanes`` (y and its planes): what is saved is the same."""
-    lib = _lib_or_raise()
-    obs = obs.detach().contiguous()
-    state = state.detach().reshape(-1).to(torch.float32).contiguous()
-    B, Ci, Hh, Ww = obs.shape
-    Co = weight.shape[0]
-    w = weight.detach().contiguous()
-    y = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.float32, device=obs.device)
-    mask = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.uint8, device=obs.device)
-    head = (_ptr(obs), _ptr(w), _optr(bias.detach().contiguous() if bias is not None else None), _ptr(state), _ptr(y),
-            C.c_void_p(mask.data_ptr()))
-    yp = _planes_like(y) if want_planes else None
-    if yp is None:
-        _check(lib.aurppo_first_block_fwd_f32(*head, B, Ci, Co, Hh, Ww, _stream()), "aurppo_first_block_fwd_f32")
-    else:
-        _check(lib.aurppo_first_block_planes_fwd_f32(*head, _ptr(yp, torch.int16), B, Ci, Co, Hh, Ww, _stream()),
-               "aurppo_first_block_planes_fwd_f32")
-    ctx.save_for_backward(obs, state, mask)
-    ctx.dims = (B, Ci, Co, Hh, Ww, bias is not None)
-    if yp is None:
-        return y
-    ctx.mark_non_differentiable(yp)
-    return y, yp
-
-
 class _FirstBlock(torch.autograd.Function):
+    """K10: y, or with ``want_planes`` y and its planes (not differentiable); what is saved and the backward are the same."""
     @staticmethod
-    def forward(ctx, obs, state, weight, bias):
-        return _first_block_fwd(ctx, obs, state, weight, bias, False)
+    def forward(ctx, obs, state, weight, bias, want_planes):
+        lib = _lib_or_raise()
+        obs = obs.detach().contiguous()
+        state = state.detach().reshape(-1).to(torch.float32).contiguous()
+        B, Ci, Hh, Ww = obs.shape
+        Co = weight.shape[0]
+        w = weight.detach().contiguous()
+        y = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.float32, device=obs.device)
+        mask = torch.empty((B, Co, Hh // 2, Ww // 2), dtype=torch.uint8, device=obs.device)
+        head = (_ptr(obs), _ptr(w), _optr(bias.detach().contiguous() if bias is not None else None), _ptr(state), _ptr(y),
+                C.c_void_p(mask.data_ptr()))
+        yp = _planes_like(y) if want_planes else None
+        if yp is None:
+            _check(lib.aurppo_first_block_fwd_f32(*head, B, Ci, Co, Hh, Ww, _stream()), "aurppo_first_block_fwd_f32")
+        else:
+            _check(lib.aurppo_first_block_planes_fwd_f32(*head, _ptr(yp, torch.int16), B, Ci, Co, Hh, Ww, _stream()),
+                   "aurppo_first_block_planes_fwd_f32")
+        ctx.save_for_backward(obs, state, mask)
+        ctx.dims = (B, Ci, Co, Hh, Ww, bias is not None)
+        if yp is None:
+            return y
+        ctx.mark_non_differentiable(yp)
+        return y, yp
 
     @staticmethod
     def backward(ctx, dy, _dyp=None):
@@ -821,14 +817,7 @@ class _FirstBlock(torch.autograd.Function):
         # (B, Co/16, 16, taps) -> sum over the samples -> (Co, Ci+1, 3, 3)
         dw = dw_part.view(B, Co // 16, 16, (Ci + 1) * 9).sum(0).reshape(Co, Ci + 1, 3, 3)
         db = db_part.view(B, Co // 16, 16).sum(0).reshape(Co) if has_bias else None
-        return None, None, dw, db
-
-
-class _FirstBlockPlanes(_FirstBlock):
-    """K10 that also returns its output's planes (not differentiable); saves and backpropagates what ``_FirstBlock`` does."""
-    @staticmethod
-    def forward(ctx, obs, state, weight, bias):
-        return _first_block_fwd(ctx, obs, state, weight, bias, True)
+        return None, None, dw, db, None
 
 
 CONV3X3_MIN_PIXELS = 131072
@@ -838,30 +827,58 @@ NARROW_MIN_PIXELS = 262144      # output pixels of the batch from which K11n / K
 
 
 class _Conv3x3(torch.autograd.Function):
+    """The hidden 3x3 convolution behind ``conv3x3``, ``conv3x3_pool``, ``conv3x3_planes`` and ``conv3x3_pool_planes``.  ``pool``: the
+    whole block (K11p: ``bias``, ReLU and the 2x2 max-pool in the epilogue; the mask is saved); ``xp``: the planes of ``x`` to read
+    instead of it (K11x; fp32 ``x`` is saved for the backward all the same); ``want_planes``: ``(y, yp)``, the pooled output and its
+    planes (not differentiable).  These options alone decide which C entry runs.  The backward is K9's (when pooled), then K11's mode 1
+    and K12 (``_conv3x3_grads``), whatever the forward read or wrote."""
     @staticmethod
-    def forward(ctx, x, w, pad):
+    def forward(ctx, x, w, bias, xp, pad, pool, want_planes):
         lib = _lib_or_raise()
         x, w = x.contiguous(), w.contiguous()
         B, Ci, Hh, Ww = x.shape
         Co = w.shape[0]
-        z = torch.empty((B, Co, Hh + 2 * pad - 2, Ww + 2 * pad - 2), dtype=torch.float32, device=x.device)
+        Ho, Wo = Hh + 2 * pad - 2, Ww + 2 * pad - 2
+        y = torch.empty((B, Co, Ho // 2, Wo // 2) if pool else (B, Co, Ho, Wo), dtype=torch.float32, device=x.device)
+        mask = torch.empty(y.shape, dtype=torch.uint8, device=x.device) if pool else None
+        yp = _planes_like(y) if want_planes else None
         ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
-        _check(lib.aurppo_conv3x3_f32(_ptr(x.detach()), _ptr(w.detach()), _ptr(z), B, Ci, Co, Hh, Ww, int(pad), 0,
-                                      *_ws_stream(ws)), "aurppo_conv3x3_f32")
-        ctx.save_for_backward(x, w)
-        ctx.pad = int(pad)
-        return z
+        src = _planes_of(x, xp) if xp is not None else _ptr(x.detach())
+        dims = (B, Ci, Co, Hh, Ww, int(pad))
+        if not pool:
+            assert bias is None and yp is None, "the bias and the planes are written by the pooled epilogue"
+            name, args = ("aurppo_conv3x3_f32", (*dims, 0)) if xp is None else ("aurppo_conv3x3_planes_f32", dims)
+            args = (src, _ptr(w.detach()), _ptr(y), *args)
+        else:
+            args = (_ptr(w.detach()), _optr(bias.detach().contiguous() if bias is not None else None), _ptr(y), C.c_void_p(mask.data_ptr()))
+            if xp is None and yp is None:
+                name, args = "aurppo_conv3x3_pool_f32", (src, *args, *dims)
+            else:
+                name, args = "aurppo_conv3x3_pool_planes_f32", (src, int(xp is not None), *args, _optr(yp, torch.int16), *dims)
+        _check(getattr(lib, name)(*args, *_ws_stream(ws)), name)
+        ctx.pad, ctx.has_bias = int(pad), bias is not None
+        if not pool:
+            ctx.save_for_backward(x, w)
+            return y
+        ctx.save_for_backward(x, w, mask)
+        if yp is None:
+            return y
+        ctx.mark_non_differentiable(yp)
+        return y, yp
 
     @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
+    def backward(ctx, g, _gyp=None):
+        x, w, *mask = ctx.saved_tensors
+        dbias = None
+        if mask:      # K9's backward rebuilds dz from the pooled gradient and the mask alone; from there on it is the unpooled backward
+            g, dbias = _pool2_bwd(g, mask[0], mask[0].shape[:2] + (x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2), ctx.has_bias)
         dx, dw = _conv3x3_grads(g.contiguous(), x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return dx, dw, None
+        return dx, dw, dbias, None, None, None, None
 
 
 def _conv3x3_grads(g, x, w, pad, need_dx, need_dw):
     """(dx, dw) of ``conv2d(x, w, padding=pad)`` under the output gradient ``g`` (contiguous): K11's mode 1 and K12 where their
-    shape rules hold, the library's kernels elsewhere.  The backward of ``conv3x3`` and of ``conv3x3_pool``."""
+    shape rules hold, the library's kernels elsewhere.  The backward of ``_Conv3x3``, pooled or not."""
     lib = _lib_or_raise()
     B, Ci, Hh, Ww = x.shape
     Co = w.shape[0]
@@ -890,12 +907,30 @@ def _conv3x3_grads(g, x, w, pad, need_dx, need_dw):
     return dx, dw
 
 
+def _conv_tensor_ok(t, pad=0):
+    """The tensor rule every shape predicate of this family starts from: a CUDA fp32 4-d tensor (and a padding of 0..2)."""
+    return t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and pad in (0, 1, 2)
+
+
+def _conv_grad(name, query, qargs, kind, g, other, out_shape, dims):
+    """One gradient of the K12 / K11n / K12n family, ``name(g, other, out, *dims, workspace, stream)``: the byte query (0: the entry
+    does not take the shape), the workspace of ``kind``, the output, the checked call."""
+    lib = _lib_or_raise()
+    nb = getattr(lib, query)(*qargs)
+    if nb == 0:
+        raise RuntimeError(f"aur_ppo_amd: {name} does not take this shape")
+    ws = _workspace(kind, nb, g.device)
+    out = torch.empty(out_shape, dtype=torch.float32, device=g.device)
+    _check(getattr(lib, name)(_ptr(g), _ptr(other.detach()), _ptr(out), *dims, *_ws_stream(ws)), name)
+    return out
+
+
 def conv3x3_wgrad_ok(x, cin, cout, pad):
     """K12's shape rule: the product's tile is 128 (64 for cout <= 64) output channels x 128 (192) filter columns (cin * 9), and
     the layers below 64 output channels / 32 input channels leave most of it empty (the library's small-tile kernels win there).
     ``AURPPO_NO_K12=1`` switches it off, ``AURPPO_K12_ALL=1`` takes every shape the kernel accepts (tests)."""
     env = os.environ
-    if env.get("AURPPO_NO_K12") == "1" or not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and pad in (0, 1, 2)):
+    if env.get("AURPPO_NO_K12") == "1" or not _conv_tensor_ok(x, pad):
         return False
     if _lib_or_raise().aurppo_conv3x3_wgrad_ws_bytes(x.shape[0], cin, cout, x.shape[2], x.shape[3], pad) == 0:
         return False
@@ -908,21 +943,15 @@ def conv3x3_wgrad_ok(x, cin, cout, pad):
 def conv3x3_wgrad(g, x, cout, pad):
     """K12: the gradient of ``conv2d(x, w (cout, cin, 3, 3), padding=pad)`` with respect to ``w`` given the output gradient ``g``
     (csrc/conv.hip::k_conv3x3_wgrad: a product over the batch's output pixels, both operands split once per workgroup)."""
-    lib = _lib_or_raise()
     g, x = g.contiguous(), x.contiguous()
     B, Ci, Hh, Ww = x.shape
     assert g.shape == (B, cout, Hh + 2 * pad - 2, Ww + 2 * pad - 2), (g.shape, x.shape, cout, pad)
-    nb = lib.aurppo_conv3x3_wgrad_ws_bytes(B, Ci, cout, Hh, Ww, int(pad))
-    if nb == 0:
-        raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_wgrad_f32 does not take this shape")
-    ws = _workspace("wgrad", nb, x.device)
-    dw = torch.empty((cout, Ci, 3, 3), dtype=torch.float32, device=x.device)
-    _check(lib.aurppo_conv3x3_wgrad_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), *_ws_stream(ws)), "aurppo_conv3x3_wgrad_f32")
-    return dw
+    dims = (B, Ci, cout, Hh, Ww, int(pad))
+    return _conv_grad("aurppo_conv3x3_wgrad_f32", "aurppo_conv3x3_wgrad_ws_bytes", dims, "wgrad", g, x, (cout, Ci, 3, 3), dims)
 
 
 def _narrow_tensor_ok(t):
-    return t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+    return _conv_tensor_ok(t) and t.is_contiguous()
 
 
 def conv3x3_dgrad_narrow_ok(g, w, pad):
@@ -941,18 +970,11 @@ def conv3x3_dgrad_narrow_ok(g, w, pad):
 def conv3x3_dgrad_narrow(g, w, pad):
     """K11n: the gradient of ``conv2d(x, w (Co, Ci <= 16, 3, 3), padding=pad)`` with respect to ``x`` given the output gradient ``g``
     (csrc/conv_narrow.hip::k_conv3x3_narrow_dgrad: 16-wide matrix blocks, the dy tile split once for all nine taps)."""
-    lib = _lib_or_raise()
     B, Co, Ho, Wo = g.shape
     Ci = w.shape[1]
     Hh, Ww = Ho + 2 - 2 * pad, Wo + 2 - 2 * pad
-    nb = lib.aurppo_conv3x3_dgrad_narrow_wop_bytes(Ci, Co)
-    if nb == 0:
-        raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_dgrad_narrow_f32 does not take this shape")
-    ws = _workspace("dgrad_narrow", nb, g.device)
-    dx = torch.empty((B, Ci, Hh, Ww), dtype=torch.float32, device=g.device)
-    _check(lib.aurppo_conv3x3_dgrad_narrow_f32(_ptr(g), _ptr(w.detach()), _ptr(dx), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
-           "aurppo_conv3x3_dgrad_narrow_f32")
-    return dx
+    return _conv_grad("aurppo_conv3x3_dgrad_narrow_f32", "aurppo_conv3x3_dgrad_narrow_wop_bytes", (Ci, Co), "dgrad_narrow", g, w,
+                      (B, Ci, Hh, Ww), (B, Ci, Co, Hh, Ww, int(pad)))
 
 
 def conv3x3_wgrad_narrow_ok(g, x, cout, pad):
@@ -972,23 +994,17 @@ def conv3x3_wgrad_narrow_ok(g, x, cout, pad):
 def conv3x3_wgrad_narrow(g, x, cout, pad):
     """K12n: the gradient of ``conv2d(x, w (cout <= 32, Ci <= 16, 3, 3), padding=pad)`` with respect to ``w`` given ``g``
     (csrc/conv_narrow.hip::k_conv3x3_narrow_wgrad: a wave owns the whole 32 x 144 filter and a slice of the pixels; slices folded in order)."""
-    lib = _lib_or_raise()
     B, Ci, Hh, Ww = x.shape
     assert g.shape == (B, cout, Hh + 2 * pad - 2, Ww + 2 * pad - 2), (g.shape, x.shape, cout, pad)
-    nb = lib.aurppo_conv3x3_wgrad_narrow_ws_bytes(B, Ci, cout, Hh, Ww, int(pad))
-    if nb == 0:
-        raise RuntimeError("aur_ppo_amd: aurppo_conv3x3_wgrad_narrow_f32 does not take this shape")
-    ws = _workspace("wgrad_narrow", nb, x.device)
-    dw = torch.empty((cout, Ci, 3, 3), dtype=torch.float32, device=x.device)
-    _check(lib.aurppo_conv3x3_wgrad_narrow_f32(_ptr(g), _ptr(x.detach()), _ptr(dw), B, Ci, cout, Hh, Ww, int(pad), *_ws_stream(ws)),
-           "aurppo_conv3x3_wgrad_narrow_f32")
-    return dw
+    dims = (B, Ci, cout, Hh, Ww, int(pad))
+    return _conv_grad("aurppo_conv3x3_wgrad_narrow_f32", "aurppo_conv3x3_wgrad_narrow_ws_bytes", dims, "wgrad_narrow", g, x,
+                      (cout, Ci, 3, 3), dims)
 
 
 def _conv3x3_shape_ok(x, cin, cout, pixels):
-    """What K11 and K11p ask of a 4-d ``x`` and a product of ``pixels`` rows (``conv3x3_ok`` says why)."""
+    """What K11 and K11p ask of the channels of ``x`` (``_conv_tensor_ok``) and of a product of ``pixels`` rows (``conv3x3_ok`` says why)."""
     # a workgroup takes 256 output pixels x 128 output channels: the launch needs a few hundred of them to fill 256 CUs
-    return (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
+    return (x.shape[1] == cin and cin % 16 == 0 and cout % 32 == 0
             and (pixels >= CONV3X3_MIN_PIXELS or ((pixels + 255) // 256) * ((cout + 127) // 128) >= CONV3X3_MIN_WGS))
 
 
@@ -1003,7 +1019,7 @@ def conv3x3_ok(x, cin, cout, pad):
     of 16 (one k-step = 16 channels of a tap), cout a multiple of 32 (whole matrix blocks), and enough output pixels -- a workgroup
     takes 256 of them, and below ~512 workgroups (the encoder's last 3x3 -> 1x1 layers) the launch is a handful of long serial K
     loops that the library's kernels beat."""
-    return x.dim() == 4 and pad in (0, 1, 2) and _conv3x3_shape_ok(x, cin, cout, x.shape[0] * (x.shape[2] + 2 * pad - 2) * (x.shape[3] + 2 * pad - 2))
+    return _conv_tensor_ok(x, pad) and _conv3x3_shape_ok(x, cin, cout, x.shape[0] * (x.shape[2] + 2 * pad - 2) * (x.shape[3] + 2 * pad - 2))
 
 
 def conv3x3_supported(x, conv):
@@ -1014,40 +1030,13 @@ def conv3x3_supported(x, conv):
 def conv3x3(x, weight, padding):
     """K11: ``conv2d(x, weight, None, stride=1, padding=padding)`` for a 3x3 filter on the bf16 matrix pipe (fp32 products from
     three-way bf16 splits), forward and input gradient (src/nets/base_cnns.py:32-45's hidden convolutions)."""
-    return _Conv3x3.apply(x, weight, int(padding))
-
-
-class _Conv3x3Pool(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, bias, pad):
-        lib = _lib_or_raise()
-        x, w = x.contiguous(), w.contiguous()
-        B, Ci, Hh, Ww = x.shape
-        Co = w.shape[0]
-        Ho, Wo = Hh + 2 * pad - 2, Ww + 2 * pad - 2
-        y = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.float32, device=x.device)
-        mask = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.uint8, device=x.device)
-        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
-        _check(lib.aurppo_conv3x3_pool_f32(_ptr(x.detach()), _ptr(w.detach()), _optr(bias.detach().contiguous() if bias is not None else None),
-                                           _ptr(y), C.c_void_p(mask.data_ptr()), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
-               "aurppo_conv3x3_pool_f32")
-        ctx.save_for_backward(x, w, mask)
-        ctx.pad, ctx.has_bias = int(pad), bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, mask = ctx.saved_tensors
-        # K9's backward rebuilds dz from the pooled gradient and the mask alone; from there on it is conv3x3's backward
-        dz, dbias = _pool2_bwd(dy, mask, mask.shape[:2] + (x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2), ctx.has_bias)
-        dx, dw = _conv3x3_grads(dz, x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return dx, dw, dbias, None
+    return _Conv3x3.apply(x, weight, None, None, int(padding), False, False)
 
 
 def conv3x3_pool_ok(x, cin, cout, pad):
     """K11p's shape rule: ``conv3x3_ok``'s with the pixel count taken as the four positions of every whole pooling window
     (4 * B * Hp * Wp: an odd trailing row / column is never computed), and at least one window."""
-    if x.dim() != 4 or pad not in (0, 1, 2):
+    if not _conv_tensor_ok(x, pad):
         return False
     hp, wp = (x.shape[2] + 2 * pad - 2) // 2, (x.shape[3] + 2 * pad - 2) // 2
     return hp >= 1 and wp >= 1 and _conv3x3_shape_ok(x, cin, cout, 4 * x.shape[0] * hp * wp)
@@ -1062,7 +1051,7 @@ def conv3x3_pool(x, weight, bias, padding):
     """K11p: ``max_pool2d(relu(conv2d(x, weight, bias, padding=padding)), 2)`` in one launch -- K11 with K9's bias / ReLU / pool in
     its epilogue, bit for bit ``bias_relu_pool2(conv3x3(x, weight, padding), bias)`` without the full-resolution tensor in
     between.  The backward is K9's (the mask is saved) followed by ``conv3x3``'s."""
-    return _Conv3x3Pool.apply(x, weight, bias, int(padding))
+    return _Conv3x3.apply(x, weight, bias, None, int(padding), True, False)
 
 
 # ------------------------------------------------------------------ K11x: activations kept as bf16 planes
@@ -1084,73 +1073,18 @@ def _planes_of(x, xp):
     return _ptr(xp, torch.int16)
 
 
-class _Conv3x3Planes(torch.autograd.Function):
-    """``_Conv3x3`` whose forward reads ``xp``, the planes of ``x``; ``x`` itself is saved for the unchanged backward."""
-    @staticmethod
-    def forward(ctx, x, xp, w, pad):
-        lib = _lib_or_raise()
-        x, w = x.contiguous(), w.contiguous()
-        B, Ci, Hh, Ww = x.shape
-        Co = w.shape[0]
-        z = torch.empty((B, Co, Hh + 2 * pad - 2, Ww + 2 * pad - 2), dtype=torch.float32, device=x.device)
-        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
-        _check(lib.aurppo_conv3x3_planes_f32(_planes_of(x, xp), _ptr(w.detach()), _ptr(z), B, Ci, Co, Hh, Ww, int(pad), *_ws_stream(ws)),
-               "aurppo_conv3x3_planes_f32")
-        ctx.save_for_backward(x, w)
-        ctx.pad = int(pad)
-        return z
-
-    @staticmethod
-    def backward(ctx, g):
-        x, w = ctx.saved_tensors
-        dx, dw = _conv3x3_grads(g.contiguous(), x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
-        return dx, None, dw, None
-
-
 def conv3x3_planes(x, xp, weight, padding):
     """K11 on planes: ``conv3x3(x, weight, padding)``, bit for bit, computed from ``xp`` -- the planes of ``x`` that its producer
     wrote (``first_block`` / ``conv3x3_pool_planes`` with ``want_planes``, or ``split_planes``).  ``x`` takes the gradient."""
-    return _Conv3x3Planes.apply(x, xp, weight, int(padding))
-
-
-class _Conv3x3PoolPlanes(torch.autograd.Function):
-    """``_Conv3x3Pool`` that reads ``xp`` (when given) instead of ``x`` and / or also returns the planes of ``y`` (not differentiable).
-    It saves what ``_Conv3x3Pool`` saves -- fp32 ``x``, ``w``, the mask -- and its backward is that function's."""
-    @staticmethod
-    def forward(ctx, x, xp, w, bias, pad, want_planes):
-        lib = _lib_or_raise()
-        x, w = x.contiguous(), w.contiguous()
-        B, Ci, Hh, Ww = x.shape
-        Co = w.shape[0]
-        Ho, Wo = Hh + 2 * pad - 2, Ww + 2 * pad - 2
-        y = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.float32, device=x.device)
-        mask = torch.empty((B, Co, Ho // 2, Wo // 2), dtype=torch.uint8, device=x.device)
-        yp = _planes_like(y) if want_planes else None
-        ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Ci, Co), x.device)
-        src = _planes_of(x, xp) if xp is not None else _ptr(x.detach())
-        _check(lib.aurppo_conv3x3_pool_planes_f32(src, int(xp is not None), _ptr(w.detach()),
-                                                  _optr(bias.detach().contiguous() if bias is not None else None), _ptr(y),
-                                                  C.c_void_p(mask.data_ptr()), _optr(yp, torch.int16), B, Ci, Co, Hh, Ww, int(pad),
-                                                  *_ws_stream(ws)), "aurppo_conv3x3_pool_planes_f32")
-        ctx.save_for_backward(x, w, mask)
-        ctx.pad, ctx.has_bias = int(pad), bias is not None
-        if yp is None:
-            return y
-        ctx.mark_non_differentiable(yp)
-        return y, yp
-
-    @staticmethod
-    def backward(ctx, dy, _dyp=None):
-        x, w, mask = ctx.saved_tensors
-        dz, dbias = _pool2_bwd(dy, mask, mask.shape[:2] + (x.shape[2] + 2 * ctx.pad - 2, x.shape[3] + 2 * ctx.pad - 2), ctx.has_bias)
-        dx, dw = _conv3x3_grads(dz, x, w, ctx.pad, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
-        return dx, None, dw, dbias, None, None
+    if xp is None:
+        raise ValueError("conv3x3_planes: no planes given (conv3x3 reads x itself)")
+    return _Conv3x3.apply(x, weight, None, xp, int(padding), False, False)
 
 
 def conv3x3_pool_planes(x, xp, weight, bias, padding, want_planes=False):
     """K11p on planes: ``conv3x3_pool(x, weight, bias, padding)``, bit for bit, reading ``xp`` (the planes of ``x``; None: ``x`` itself)
     and, with ``want_planes``, returning ``(y, yp)`` -- ``yp == split_planes(y)``, written by the same launch for the next block."""
-    return _Conv3x3PoolPlanes.apply(x, xp, weight, bias, int(padding), bool(want_planes))
+    return _Conv3x3.apply(x, weight, bias, xp, int(padding), True, bool(want_planes))
 
 
 def like_gpu(shape):
@@ -1240,7 +1174,7 @@ def first_block(obs, state, weight, bias, want_planes=False):
     src/nets/base_cnns.py:28-31 on the input of src/models/robot_actor_critic.py:58-59 -- forward and backward without the
     full-resolution tensors.  ``weight``: (Co, Ci + 1, 3, 3), state plane last; Ci in 1..3, Co a multiple of 16.
     ``want_planes``: returns ``(y, yp)``, ``yp`` the planes of ``y`` (``split_planes``) written by the same launch."""
-    return (_FirstBlockPlanes if want_planes else _FirstBlock).apply(obs, state, weight, bias)
+    return _FirstBlock.apply(obs, state, weight, bias, bool(want_planes))
 
 
 def linear_rows_bias_act(x, rows, w, bias, act=0):

@@ -143,13 +143,13 @@ def _conv_case(h):
     assert x.grad.shape == x.shape and w.grad.shape == w.shape
 
 
-def _pool_case(planes_in, want, with_bias=True):
+def _pool_case(planes_in, want, with_bias=True, fp32_wrapper=False):
     def run(h):
         Bn, Ci, Co, Hh, Ww, pad = 2, 32, 64, 5, 7, 1
         x, w = h.t("x", Bn, Ci, Hh, Ww).requires_grad_(True), h.t("w", Co, Ci, 3, 3).requires_grad_(True)
         bias = h.t("bias", Co).requires_grad_(True) if with_bias else None
         xp = _planes(h, "xp", x) if planes_in else None
-        y = H.conv3x3_pool_planes(x, xp, w, bias, pad, want_planes=want)
+        y = H.conv3x3_pool(x, w, bias, pad) if fp32_wrapper else H.conv3x3_pool_planes(x, xp, w, bias, pad, want_planes=want)
         if want:
             y, yp = y
             assert yp.dtype == torch.int16 and tuple(yp.shape) == (Bn, Co // 8, 3, 6, 8) and not yp.requires_grad
@@ -184,6 +184,7 @@ CASES["conv3x3_pool_planes/in"] = _pool_case(True, False)
 CASES["conv3x3_pool_planes/out"] = _pool_case(False, True)
 CASES["conv3x3_pool_planes/in_out"] = _pool_case(True, True)
 CASES["conv3x3_pool_planes/in_out/no_bias"] = _pool_case(True, True, with_bias=False)
+CASES["conv3x3_pool_planes/neither"] = _pool_case(False, False)
 CASES["first_block/planes"] = _first_case
 
 
@@ -216,6 +217,37 @@ def test_every_call_fits_the_bound_argtypes(monkeypatch, bound):
     for name in sorted(CASES):
         with monkeypatch.context() as m:
             assert run_case(name, m.setattr, bound)
+
+
+def test_planes_neither_in_nor_out_is_conv3x3_pool_call_for_call(monkeypatch):
+    def transcript(run):
+        h = TC.Harness()
+        with monkeypatch.context() as m:
+            h.install(m.setattr)
+            run(h)
+        return h.transcript()
+
+    got = transcript(CASES["conv3x3_pool_planes/neither"])
+    assert got == transcript(_pool_case(False, False, fp32_wrapper=True))
+    assert [c[0] for c in got][:3] == ["aurppo_conv3x3_wop_bytes", "_workspace", "aurppo_conv3x3_pool_f32"]
+
+
+def test_one_autograd_function_stands_behind_the_four_wrappers_and_one_behind_first_block(monkeypatch):
+    h = TC.Harness()
+    h.install(monkeypatch.setattr)
+    x, w, bias = h.t("x", 2, 32, 5, 7).requires_grad_(True), h.t("w", 64, 32, 3, 3).requires_grad_(True), h.t("bias", 64)
+    xp = _planes(h, "xp", x)
+    outs = [H.conv3x3(x, w, 1), H.conv3x3_pool(x, w, bias, 1), H.conv3x3_planes(x, xp, w, 1), H.conv3x3_pool_planes(x, xp, w, bias, 1),
+            H.conv3x3_pool_planes(x, None, w, bias, 1), H.conv3x3_pool_planes(x, xp, w, bias, 1, want_planes=True)[0]]
+    kinds = {type(y.grad_fn) for y in outs}
+    assert len(kinds) == 1 and None not in {y.grad_fn for y in outs}
+    assert [len(y.grad_fn.saved_tensors) for y in outs] == [2, 3, 2, 3, 3, 3]
+    obs, state = h.t("obs", 2, 1, 8, 8), h.t("state", 2)
+    fw, fb = h.t("fw", 16, 2, 3, 3).requires_grad_(True), h.t("fb", 16).requires_grad_(True)
+    first = [H.first_block(obs, state, fw, fb), H.first_block(obs, state, fw, fb, want_planes=False),
+             H.first_block(obs, state, fw, fb, want_planes=True)[0]]
+    assert len({type(y.grad_fn) for y in first}) == 1 and first[0].grad_fn is not None
+    assert not kinds & {type(first[0].grad_fn)}
 
 
 def test_the_backwards_are_the_fp32_functions(monkeypatch):
