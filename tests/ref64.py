@@ -522,7 +522,11 @@ def make_emulated_net(sd, prods_of):
 
 
 class _FastTanh(nn.Module):
-    def forward(self, x):              # tanh(x) = 1 - 2 / (e^{2x} + 1) (csrc/mlp_common.h): absolute error ~1e-7 everywhere
+    """The forward formula only: its backward is autograd's of the formula, 2 e^{2x} / (e^{2x} + 1)^2 * 2, which is inf / inf = NaN once
+    e^{2x} overflows (x > 44.4).  The kernels form tanh' as 1 - t * t from the output, which is clean there; the extremes
+    (tests/ref64_extremes.py) therefore use renditions with that backward, and this one serves as their first mutant."""
+
+    def forward(self, x):             # tanh(x) = 1 - 2 / (e^{2x} + 1) (csrc/mlp_common.h): absolute error ~1e-7 everywhere
         return 1.0 - 2.0 / (torch.exp(2.0 * x) + 1.0)
 
 
