@@ -31,6 +31,8 @@ SYMBOLS = (
     "aurppo_conv3x3_wgrad_narrow_f32",
     "aurppo_planes_bytes", "aurppo_split_planes_f32", "aurppo_conv3x3_planes_f32", "aurppo_conv3x3_pool_planes_f32",
     "aurppo_first_block_planes_fwd_f32",
+    "aurppo_linear_small_bias_act_f32", "aurppo_linear_pair_wop_bytes", "aurppo_linear_pair_bias_act_f32",
+    "aurppo_mlp_layered_act_paired_f32",
 )
 
 _lib = None
@@ -111,6 +113,9 @@ def _declare(lib):
     lib.aurppo_conv3x3_pool_f32.argtypes = [vp] * 5 + [i32] * 6 + ws_stream
     lib.aurppo_linear_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
     lib.aurppo_linear_bias_act_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
+    lib.aurppo_linear_small_bias_act_f32.argtypes = [vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
+    lib.aurppo_linear_pair_wop_bytes.argtypes = [i32, i32]
+    lib.aurppo_linear_pair_bias_act_f32.argtypes = [vp] * 8 + [C.c_longlong, i32, i32, i32] + ws_stream
     lib.aurppo_linear_wgrad_ws_bytes.argtypes = [C.c_longlong, i32, i32]
     lib.aurppo_linear_wgrad_f32.argtypes = [vp, vp, vp, C.c_longlong, i32, i32] + ws_stream
     lib.aurppo_linear_rows_bias_act_f32.argtypes = [vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32] + ws_stream
@@ -123,6 +128,7 @@ def _declare(lib):
     lib.aurppo_mlp_layered_prep_f32.argtypes = [vp, pi32, i32, i32, i32, i32, vp, vp]
     lib.aurppo_mlp_layered_act_workspace_bytes.argtypes = [i32, i32]
     lib.aurppo_mlp_layered_act_f32.argtypes = [vp, vp] + [i32] * 6 + [vp, pi32, i32, vp, vp, vp, vp] + ws_stream
+    lib.aurppo_mlp_layered_act_paired_f32.argtypes = lib.aurppo_mlp_layered_act_f32.argtypes
     lib.aurppo_head_act_f32.argtypes = [vp, vp, vp] + [i32] * 4 + [vp, pi32, i32, vp, vp, vp, vp]
     # the layered update step
     lib.aurppo_linear_wgrad_bias_ws_bytes.argtypes = [C.c_longlong, i32, i32]
@@ -172,6 +178,7 @@ def _declare(lib):
              "aurppo_linear_wgrad_ws_bytes", "aurppo_conv3x3_wgrad_ws_bytes", "aurppo_mlp_wide_workspace_bytes",
              "aurppo_head_ppo_workspace_bytes", "aurppo_mlp_layered_wop_bytes", "aurppo_mlp_layered_act_workspace_bytes",
              "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes",
-             "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes", "aurppo_planes_bytes")
+             "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes", "aurppo_planes_bytes",
+             "aurppo_linear_pair_wop_bytes")
     for name in SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

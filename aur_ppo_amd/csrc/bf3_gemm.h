@@ -74,6 +74,25 @@ inline Bf3Grid bf3_grid(long long M, int N) {
     const int nblk = (N + 31) / 32, NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
     return {(M + 32 * 4 * kMB - 1) / (32 * 4 * kMB), NB, (nblk + NB - 1) / NB};
 }
+// The small-M tile of the forward linear products (linear_small_body.h): 4 waves x ONE block of 32 rows, NB of 1 or 2 -- n_mb
+// workgroups of 128 rows x n_ng groups of NB blocks, for each of the launch's `nets` same-shaped products (the paired form: 2).
+// The NB rule, from measurement (DESIGN 4.12 has the table): 2 where the launch then still has two workgroups for each of the
+// chip's 256 CUs, else 1 -- twice the workgroups, each splitting its A values for one column block only.  Below that NB 1 won
+// every time (a pair at 4096 x 256: 512 workgroups 40 us per rollout step, 256 workgroups 46; at 1024 rows 31 against 40), from
+// 512 NB-2 workgroups on NB 2 was level or ahead (a pair at 4096 x 512: 72 against 76; at 16384 x 256: 95 against 106).
+// 4096 rows x 256 columns: one product 32 x 8 = 256 workgroups, a pair 512.  -DLINEAR_SMALL_NB=1|2: a measuring build that takes
+// that NB wherever the product has two column blocks.
+constexpr long long kSmallFillWgs = 2 * 256;
+inline Bf3Grid bf3_small_grid(long long M, int N, int nets) {
+    const int nblk = (N + 31) / 32;
+    const long long n_mb = (M + 32 * 4 - 1) / (32 * 4);
+#ifdef LINEAR_SMALL_NB
+    const int NB = nblk >= 2 ? LINEAR_SMALL_NB : 1;
+#else
+    const int NB = nblk >= 2 && n_mb * ((nblk + 1) / 2) * nets >= kSmallFillWgs ? 2 : 1;
+#endif
+    return {n_mb, NB, (nblk + NB - 1) / NB};
+}
 template <class F>
 void bf3_with_nb(int NB, F&& f) {
     if (NB == 4) f(std::integral_constant<int, 4>{});

@@ -75,6 +75,11 @@ constexpr int kLayeredMaxLayers = 16;
 size_t aurppo_linear_wop_bytes(int K, int N);
 int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s);
 int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N, void* stream);
+// the same product on the small-M tile (k_linear_small), and two nets' same-shaped products in one launch (k_linear_pair): same bits
+int aurppo_linear_small_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
+                                 void* stream);
+int aurppo_linear_pair_prepared(const float* xA, const float* xC, const void* wopA, const void* wopC, const float* biasA, const float* biasC,
+                                int act, float* yA, float* yC, long long M, int K, int N, void* stream);
 // K13 / K14's shape rule and K14 on checked operands (head.hip), for the layered steps
 bool head_shape_ok(int H, int A, int continuous);
 int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,

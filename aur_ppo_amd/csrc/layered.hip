@@ -145,40 +145,82 @@ extern "C" size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden) {
     return 4 * layered_act_plane_bytes(N, hidden);      // two activation planes per net, written in turn
 }
 
-extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
-                                          int num_layers, const float* params, const int* offsets, int n_params, float* actions,
-                                          float* logp, float* value, const void* wop, void* workspace, void* stream) {
-    AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL,
-                   "aurppo_mlp_layered_act_f32: null pointer");
-    AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_act_f32: N=%d, D=%d, %d layers (1..%d)", N, D, num_layers, kLayeredMaxLayers);
+namespace {
+
+// The rollout step behind both entries.  paired: per layer ONE launch of the paired small-tile product for both nets (k_linear_pair),
+// L + 1 launches with K14; without noise the critic alone on the single small-tile product (k_linear_small), L + 1 as well.  The
+// bits are the unpaired route's: a row's result does not depend on the tile (linear_small_body.h).
+int layered_act_impl(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden, int num_layers,
+                     const float* params, const int* offsets, int n_params, float* actions, float* logp, float* value, const void* wop,
+                     void* workspace, void* stream, bool paired, const char* who) {
+    AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL, "%s: null pointer",
+                   who);
+    AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE, "%s: N=%d, D=%d, %d layers (1..%d)",
+                   who, N, D, num_layers, kLayeredMaxLayers);
     AURPPO_REQUIRE(head_shape_ok(hidden, A, continuous), AURPPO_ESHAPE,
-                   "aurppo_mlp_layered_act_f32: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", hidden, A);
+                   "%s: hidden=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", who, hidden, A);
     AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
-                   "aurppo_mlp_layered_act_f32: obs / operand copies not 16-byte / workspace not 64-byte aligned");
+                   "%s: obs / operand copies not 16-byte / workspace not 64-byte aligned", who);
     AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
-                   AURPPO_EINVAL, "aurppo_mlp_layered_act_f32: noise / outputs not 4-byte aligned");
+                   AURPPO_EINVAL, "%s: noise / outputs not 4-byte aligned", who);
     const int L = num_layers, per = 2 * (L + 1);
-    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, "aurppo_mlp_layered_act_f32")) return rc;
+    if (const int rc = layered_offsets_check(offsets, D, A, continuous, hidden, L, n_params, who)) return rc;
     const size_t plane = layered_act_plane_bytes(N, hidden);
     const char* const wbase = reinterpret_cast<const char*>(wop);
     const size_t net_wop = aurppo_linear_wop_bytes(D, hidden) + (size_t)(L - 1) * aurppo_linear_wop_bytes(hidden, hidden);
+    auto out = [&](int net, int l) { return reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane); };
     const float* last[2] = {nullptr, nullptr};
-    for (int net = noise ? 0 : 1; net < 2; ++net) {
-        const int* o = offsets + net * per;
-        const char* w = wbase + net * net_wop;
-        const float* x = obs;
+    if (paired && noise) {
+        const int *oA = offsets, *oC = offsets + per;
+        const char* w = wbase;
+        const float *xA = obs, *xC = obs;
         for (int l = 0; l < L; ++l) {
             const int K = l ? hidden : D;
-            float* y = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane);
-            if (const int rc = aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream)) return rc;
+            if (const int rc = aurppo_linear_pair_prepared(xA, xC, w, w + net_wop, params + oA[2 * l + 1], params + oC[2 * l + 1], 1, out(0, l),
+                                                           out(1, l), N, K, hidden, stream))
+                return rc;
             w += aurppo_linear_wop_bytes(K, hidden);
-            x = y;
+            xA = out(0, l);
+            xC = out(1, l);
         }
-        last[net] = x;
+        last[0] = xA;
+        last[1] = xC;
+    } else {
+        for (int net = noise ? 0 : 1; net < 2; ++net) {
+            const int* o = offsets + net * per;
+            const char* w = wbase + net * net_wop;
+            const float* x = obs;
+            for (int l = 0; l < L; ++l) {
+                const int K = l ? hidden : D;
+                float* y = out(net, l);
+                const int rc = paired ? aurppo_linear_small_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream)
+                                      : aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream);
+                if (rc != AURPPO_OK) return rc;
+                w += aurppo_linear_wop_bytes(K, hidden);
+                x = y;
+            }
+            last[net] = x;
+        }
     }
     const int lay[5] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per]};
     return head_act_launch(last[0], last[1], noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                          int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                          float* logp, float* value, const void* wop, void* workspace, void* stream) {
+    return layered_act_impl(obs, noise, N, D, A, continuous, hidden, num_layers, params, offsets, n_params, actions, logp, value, wop,
+                            workspace, stream, false, "aurppo_mlp_layered_act_f32");
+}
+
+// The same step on the small-M products, both nets' layer l in one launch: same arguments, same buffers, same bits, L + 1 launches.
+extern "C" int aurppo_mlp_layered_act_paired_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                                 int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                                 float* logp, float* value, const void* wop, void* workspace, void* stream) {
+    return layered_act_impl(obs, noise, N, D, A, continuous, hidden, num_layers, params, offsets, n_params, actions, logp, value, wop,
+                            workspace, stream, true, "aurppo_mlp_layered_act_paired_f32");
 }
 
 extern "C" size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {

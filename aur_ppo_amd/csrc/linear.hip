@@ -53,6 +53,58 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
 #include "linear_body.h"
 }
 
+// ---- the small-M builds of the forward product (linear_small_body.h says what they keep of k_linear: everything a row's bits depend
+// on).  New templates with a body text of their own, not parameters on the templates above: those keep their symbols and their
+// instruction streams.  k_linear_small / k_linear_small_tail: one product.  k_linear_pair / k_linear_pair_tail: the same-shaped product
+// of two nets (the layered rollout's actor and critic, layer by layer) in one launch -- workgroups [0, per_net) are net 0's grid,
+// [per_net, 2 per_net) net 1's; the net's four pointers are selected once, ahead of the body, so the k loop has no branch on the net.
+// The two x pointers may be equal (layer 0: both nets read the observations).
+struct LinPairArgs {
+    const float* x[2];               // (M, K) each
+    const unsigned short* wop[2];    // each net's operand copy, the layout above
+    float* y[2];                     // (M, N) each
+    const float* bias[2];            // (N,) or nullptr
+    long long M;
+    int K, N, n_mb, act;
+    unsigned per_net;                // workgroups of one net's product
+};
+template <int NB>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_small(const LinArgs a) {
+    constexpr bool KTAIL = false;
+    const unsigned wg = blockIdx.x;
+#include "linear_small_body.h"
+}
+template <int NB>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_small_tail(const LinArgs a) {
+    constexpr bool KTAIL = true;
+    const unsigned wg = blockIdx.x;
+#include "linear_small_body.h"
+}
+__device__ __forceinline__ LinArgs pair_net_args(const LinPairArgs& p, unsigned net) {
+    LinArgs a;
+    a.x = net ? p.x[1] : p.x[0];
+    a.wop = net ? p.wop[1] : p.wop[0];
+    a.y = net ? p.y[1] : p.y[0];
+    a.bias = net ? p.bias[1] : p.bias[0];
+    a.M = p.M; a.K = p.K; a.N = p.N; a.n_mb = p.n_mb; a.act = p.act;
+    a.rows = nullptr; a.h = nullptr;
+    return a;
+}
+template <int NB>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_pair(const LinPairArgs p) {
+    constexpr bool KTAIL = false;
+    const unsigned net = blockIdx.x >= p.per_net ? 1u : 0u, wg = blockIdx.x - net * p.per_net;
+    const LinArgs a = pair_net_args(p, net);
+#include "linear_small_body.h"
+}
+template <int NB>
+__global__ __launch_bounds__(kConvThreads, 2) void k_linear_pair_tail(const LinPairArgs p) {
+    constexpr bool KTAIL = true;
+    const unsigned net = blockIdx.x >= p.per_net ? 1u : 0u, wg = blockIdx.x - net * p.per_net;
+    const LinArgs a = pair_net_args(p, net);
+#include "linear_small_body.h"
+}
+
 // ---- nn.Linear's weight gradient on the same arithmetic: dW (N, K) = dY^T (N, M) . X (M, K), both operands row-major with the
 // minibatch's rows as the product's inner dimension.  Both operands change every k-step, so both are split; to split every
 // element once per WORKGROUP (not once per wave that uses it) the workgroup stages 32 rows of its 128 dY columns and its 128 X
@@ -181,6 +233,104 @@ int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, i
     AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_prepared: x / operand copy not 16-byte aligned");
     AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_prepared: act %d", act);
     return linear_launch(x, reinterpret_cast<const unsigned short*>(wop), bias, act, y, M, K, N, (hipStream_t)stream, nullptr, nullptr);
+}
+
+// ---- the small-M forward products.  One product (nets = 1: entry 0 of every array) or the pair (nets = 2), from operand copies that
+// exist; the tile and its NB are bf3_small_grid's.  Checked operands only: the entries below refuse first.
+static int linear_small_launch(int nets, const float* const x[2], const unsigned short* const wop[2], const float* const bias[2], int act,
+                               float* const y[2], long long M, int K, int N, hipStream_t s) {
+    const Bf3Grid gr = bf3_small_grid(M, N, nets);
+    const long long per_net = gr.n_mb * gr.n_ng;
+    AURPPO_REQUIRE(per_net * nets < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_small_bias_act_f32: grid too large");
+    const dim3 g((unsigned)(per_net * nets)), blk(kConvThreads);
+    const bool tail = K % 16 != 0, nb2 = gr.NB == 2;
+    if (nets == 1) {
+        LinArgs a;
+        a.x = x[0]; a.wop = wop[0]; a.y = y[0]; a.bias = bias[0]; a.M = M; a.K = K; a.N = N; a.n_mb = (int)gr.n_mb; a.act = act;
+        a.rows = nullptr; a.h = nullptr;
+        if (tail && nb2) hipLaunchKernelGGL(k_linear_small_tail<2>, g, blk, 0, s, a);
+        else if (tail) hipLaunchKernelGGL(k_linear_small_tail<1>, g, blk, 0, s, a);
+        else if (nb2) hipLaunchKernelGGL(k_linear_small<2>, g, blk, 0, s, a);
+        else hipLaunchKernelGGL(k_linear_small<1>, g, blk, 0, s, a);
+        AURPPO_LAUNCH_CHECK("k_linear_small");
+        return AURPPO_OK;
+    }
+    LinPairArgs p;
+    for (int net = 0; net < 2; ++net) {
+        p.x[net] = x[net]; p.wop[net] = wop[net]; p.y[net] = y[net]; p.bias[net] = bias[net];
+    }
+    p.M = M; p.K = K; p.N = N; p.n_mb = (int)gr.n_mb; p.act = act; p.per_net = (unsigned)per_net;
+    if (tail && nb2) hipLaunchKernelGGL(k_linear_pair_tail<2>, g, blk, 0, s, p);
+    else if (tail) hipLaunchKernelGGL(k_linear_pair_tail<1>, g, blk, 0, s, p);
+    else if (nb2) hipLaunchKernelGGL(k_linear_pair<2>, g, blk, 0, s, p);
+    else hipLaunchKernelGGL(k_linear_pair<1>, g, blk, 0, s, p);
+    AURPPO_LAUNCH_CHECK("k_linear_pair");
+    return AURPPO_OK;
+}
+
+// aurppo_linear_prepared on the small tile, and its paired form: both nets' same-shaped products in one launch (layered.hip)
+int aurppo_linear_small_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
+                                 void* stream) {
+    AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_small_prepared: null pointer");
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_small_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
+    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_small_prepared: x / operand copy not 16-byte aligned");
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_small_prepared: act %d", act);
+    const float* const xs[2] = {x, nullptr};
+    const unsigned short* const ws[2] = {reinterpret_cast<const unsigned short*>(wop), nullptr};
+    const float* const bs[2] = {bias, nullptr};
+    float* const ys[2] = {y, nullptr};
+    return linear_small_launch(1, xs, ws, bs, act, ys, M, K, N, (hipStream_t)stream);
+}
+int aurppo_linear_pair_prepared(const float* xA, const float* xC, const void* wopA, const void* wopC, const float* biasA, const float* biasC,
+                                int act, float* yA, float* yC, long long M, int K, int N, void* stream) {
+    AURPPO_REQUIRE(xA && xC && wopA && wopC && yA && yC, AURPPO_EINVAL, "aurppo_linear_pair_prepared: null pointer");
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_pair_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
+    AURPPO_REQUIRE(aligned_to(xA, 16) && aligned_to(xC, 16) && aligned_to(wopA, 16) && aligned_to(wopC, 16), AURPPO_EINVAL,
+                   "aurppo_linear_pair_prepared: x / operand copy not 16-byte aligned");
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_pair_prepared: act %d", act);
+    const float* const xs[2] = {xA, xC};
+    const unsigned short* const ws[2] = {reinterpret_cast<const unsigned short*>(wopA), reinterpret_cast<const unsigned short*>(wopC)};
+    const float* const bs[2] = {biasA, biasC};
+    float* const ys[2] = {yA, yC};
+    return linear_small_launch(2, xs, ws, bs, act, ys, M, K, N, (hipStream_t)stream);
+}
+
+// aurppo_linear_bias_act_f32 on the small tile, whatever M: same argument list, same checks, same bits
+extern "C" int aurppo_linear_small_bias_act_f32(const float* x, const float* w, const float* bias, float* y, long long M, int K_w, int N_w,
+                                                int act, void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_small_bias_act_f32: act %d", act);
+    AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_small_bias_act_f32: null pointer");
+    AURPPO_REQUIRE(M > 0 && K_w > 0 && N_w > 0, AURPPO_ESHAPE, "aurppo_linear_small_bias_act_f32: M=%lld, inner dimension %d, %d columns", M,
+                   K_w, N_w);
+    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL,
+                   "aurppo_linear_small_bias_act_f32: x / workspace not 16-byte aligned");
+    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
+    if (const int rc = linear_prep(w, K_w, N_w, 0, wop, (hipStream_t)stream)) return rc;
+    return aurppo_linear_small_prepared(x, wop, bias, act, y, M, K_w, N_w, stream);
+}
+
+// Both nets' operand copies, one behind the other: 2 x aurppo_linear_wop_bytes (a multiple of 1 KB, so the second is aligned too)
+extern "C" size_t aurppo_linear_pair_wop_bytes(int K_w, int N_w) {
+    if (K_w <= 0 || N_w <= 0) return 0;
+    return 2 * aurppo_linear_wop_bytes(K_w, N_w);
+}
+// yA = act(xA . wA^T + biasA) and yC = act(xC . wC^T + biasC), two (N_w, K_w) weights on the same M rows: two operand copies into
+// wop_ws (aurppo_linear_pair_wop_bytes), then ONE launch of the paired small-tile product.  Each result is bit for bit what
+// aurppo_linear_bias_act_f32 gives for its net.  xA may be xC.
+extern "C" int aurppo_linear_pair_bias_act_f32(const float* xA, const float* xC, const float* wA, const float* wC, const float* biasA,
+                                               const float* biasC, float* yA, float* yC, long long M, int K_w, int N_w, int act,
+                                               void* wop_ws, void* stream) {
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_pair_bias_act_f32: act %d", act);
+    AURPPO_REQUIRE(xA && xC && wA && wC && yA && yC && wop_ws, AURPPO_EINVAL, "aurppo_linear_pair_bias_act_f32: null pointer");
+    AURPPO_REQUIRE(M > 0 && K_w > 0 && N_w > 0, AURPPO_ESHAPE, "aurppo_linear_pair_bias_act_f32: M=%lld, inner dimension %d, %d columns", M,
+                   K_w, N_w);
+    AURPPO_REQUIRE(aligned_to(xA, 16) && aligned_to(xC, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL,
+                   "aurppo_linear_pair_bias_act_f32: x / workspace not 16-byte aligned");
+    char* const wopA = reinterpret_cast<char*>(wop_ws);
+    char* const wopC = wopA + aurppo_linear_wop_bytes(K_w, N_w);
+    if (const int rc = linear_prep(wA, K_w, N_w, 0, reinterpret_cast<unsigned short*>(wopA), (hipStream_t)stream)) return rc;
+    if (const int rc = linear_prep(wC, K_w, N_w, 0, reinterpret_cast<unsigned short*>(wopC), (hipStream_t)stream)) return rc;
+    return aurppo_linear_pair_prepared(xA, xC, wopA, wopC, biasA, biasC, act, yA, yC, M, K_w, N_w, stream);
 }
 
 // the weight gradient's slice count (slices_for, conv.hip, says how the slices are used)

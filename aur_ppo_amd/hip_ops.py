@@ -1169,6 +1169,42 @@ def linear_bias_act(x, w, bias, act=0):
     return _linear_bias_act(x, None, w, bias, act)
 
 
+def linear_small_bias_act(x, w, bias, act=0):
+    """``linear_bias_act`` on the tile for small M (csrc/linear.hip::k_linear_small: a workgroup takes 128 rows x 32 or 64 columns,
+    so a few thousand rows reach every CU): the same bits, forward only."""
+    lib = _lib_or_raise()
+    x, w = x.contiguous(), w.contiguous()
+    M = x.shape[0]
+    Nw, Kw = w.shape
+    if x.dim() != 2 or x.shape[1] != Kw or (bias is not None and bias.numel() != Nw):
+        raise ValueError("linear_small_bias_act: shape mismatch")
+    y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
+    ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
+    _check(lib.aurppo_linear_small_bias_act_f32(_ptr(x), _ptr(w), _optr(bias.contiguous() if bias is not None else None), _ptr(y), M, Kw, Nw,
+                                                int(act), *_ws_stream(ws)), "aurppo_linear_small_bias_act_f32")
+    return y
+
+
+def linear_pair_bias_act(xA, xC, wA, wC, bA, bC, act=0):
+    """``(act(xA @ wA.T + bA), act(xC @ wC.T + bC))`` -- two products of one shape, an actor's and a critic's layer -- from ONE
+    launch of the small-M product behind the two operand copies (csrc/linear.hip::k_linear_pair).  Each result is ``linear_bias_act``'s
+    bit for bit.  ``xA`` may be ``xC``; each bias may be None."""
+    lib = _lib_or_raise()
+    xA, xC, wA, wC = xA.contiguous(), xC.contiguous(), wA.contiguous(), wC.contiguous()
+    Nw, Kw = wA.shape
+    if (xA.dim() != 2 or xA.shape != xC.shape or xA.shape[1] != Kw or wC.shape != wA.shape
+            or any(b is not None and b.numel() != Nw for b in (bA, bC))):
+        raise ValueError("linear_pair_bias_act: the two products do not have one shape")
+    M = xA.shape[0]
+    yA = torch.empty((M, Nw), dtype=torch.float32, device=xA.device)
+    yC = torch.empty((M, Nw), dtype=torch.float32, device=xA.device)
+    ws = _workspace("conv_pair", lib.aurppo_linear_pair_wop_bytes(Kw, Nw), xA.device)
+    _check(lib.aurppo_linear_pair_bias_act_f32(_ptr(xA), _ptr(xC), _ptr(wA), _ptr(wC), _optr(bA.contiguous() if bA is not None else None),
+                                               _optr(bC.contiguous() if bC is not None else None), _ptr(yA), _ptr(yC), M, Kw, Nw, int(act),
+                                               *_ws_stream(ws)), "aurppo_linear_pair_bias_act_f32")
+    return yA, yC
+
+
 def first_block(obs, state, weight, bias, want_planes=False):
     """K10: ``max_pool2d(relu(conv2d(cat[obs, state tiled to a plane], weight, bias, padding=1)), 2)`` -- the first block of
     src/nets/base_cnns.py:28-31 on the input of src/models/robot_actor_critic.py:58-59 -- forward and backward without the
@@ -1436,10 +1472,12 @@ def mlp_layered_prepare(flat_param, layout):
     return wop
 
 
-def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None, wop=None):
+def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, value=None, wop=None, paired=False):
     """``mlp_act``'s contract and return value for the MLP policies wider than the fused kernels (``mlp_layered_layout``): per net the
     hidden layers on k_linear (bias + tanh in the epilogue) from the prepared operand copies ``wop`` (``mlp_layered_prepare``;
-    None: prepared here, from ``flat_param`` as it stands), then K14.  No host synchronisation; capturable."""
+    None: prepared here, from ``flat_param`` as it stands), then K14.  No host synchronisation; capturable.
+    ``paired``: the same step, bit for bit, on the small-M products -- per layer one launch for both nets (k_linear_pair), L + 1
+    launches where the default has 2 L + 1; same prepared buffer, same workspace."""
     lib = _lib_or_raise()
     N = obs.shape[0]
     if not layout.get("layered") or obs.dim() != 2 or obs.shape[1] != layout["D"]:
@@ -1453,7 +1491,7 @@ def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, val
         raise ValueError("mlp_layered_act: the prepared buffer is smaller than the policy's operand copies")
     lay, shape = _layout_shape(layout, N)
     ws = _workspace("layered_act", lib.aurppo_mlp_layered_act_workspace_bytes(N, layout["hidden"]), dev)
-    _check(lib.aurppo_mlp_layered_act_f32(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"],
-                                          *_act_outputs_ptrs(noise, actions, logp, value), C.c_void_p(wop.data_ptr()), *_ws_stream(ws)),
-           "aurppo_mlp_layered_act_f32")
+    entry = "aurppo_mlp_layered_act_paired_f32" if paired else "aurppo_mlp_layered_act_f32"
+    _check(getattr(lib, entry)(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"],
+                               *_act_outputs_ptrs(noise, actions, logp, value), C.c_void_p(wop.data_ptr()), *_ws_stream(ws)), entry)
     return actions, logp, value

@@ -61,6 +61,12 @@ class torch_buffer:
 LAYERED_STEP_DEFAULT = "0"      # AURPPO_LAYERED_STEP when the environment does not set it
 LAYERED_ACT_DEFAULT = "0"       # AURPPO_LAYERED_ACT when the environment does not set it
 LAYERED_NATIVE_DEFAULT = "0"    # AURPPO_LAYERED_NATIVE when the environment does not set it
+LAYERED_ACT_PAIRED_DEFAULT = "0"    # AURPPO_LAYERED_ACT_PAIRED when the environment does not set it
+
+
+def _layered_act_paired(act_layout):
+    """AURPPO_LAYERED_ACT_PAIRED, read only where the layered rollout step is on (``act_layout`` is its layout, or None)."""
+    return act_layout is not None and os.environ.get("AURPPO_LAYERED_ACT_PAIRED", LAYERED_ACT_PAIRED_DEFAULT) != "0"
 
 
 class ppo(FlatAdamMixin):
@@ -166,7 +172,10 @@ class ppo(FlatAdamMixin):
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_act")
                 and os.environ.get("AURPPO_LAYERED_ACT", LAYERED_ACT_DEFAULT) != "0"):
             self._mlp_layered_act = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
-        self._act_wop = None       # the rollout's prepared operand copies (layered act), None outside _rollout_steps
+        # ... on the small-M products, both nets' layer in one launch (ops.mlp_layered_act(paired=True): the same bits in L + 1
+        # launches).  Opt-in (AURPPO_LAYERED_ACT_PAIRED=1), and read only where the layered rollout step is on.
+        self._act_paired = _layered_act_paired(self._mlp_layered_act)
+        self._act_wop = None      # the rollout's prepared operand copies (layered act), None outside _rollout_steps
         # the flat bucket holds the MLP policy and nothing else (up to alignment padding): K7 + clip + Adam can chain
         self._bucket_is_policy = self._mlp is not None and self.bucket.numel == self._mlp["n_params"]
         self._ro_state, self._ro_graph, self._ro_obs, self._ro_done, self._ro_out = 0, None, None, None, None   # captured rollout
@@ -284,7 +293,9 @@ class ppo(FlatAdamMixin):
     def _act(self, lay, obs, noise, *outs):
         """K8 / K8w in one launch, or the layered rollout step (from the rollout's prepared copies when ``_rollout_steps`` made them)."""
         if lay.get("layered"):
-            return self.ops.mlp_layered_act(obs, noise, self.bucket.flat_param, lay, *outs, wop=self._act_wop if noise is not None else None)
+            paired = {"paired": True} if self._act_paired else {}        # (unset: the call is what it was, keyword for keyword)
+            return self.ops.mlp_layered_act(obs, noise, self.bucket.flat_param, lay, *outs, wop=self._act_wop if noise is not None else None,
+                                            **paired)
         return self.ops.mlp_act(obs, noise, self.bucket.flat_param, lay, *outs)
 
     def rewards_to_go(self, step, next_obs, global_step, writer):

@@ -305,6 +305,23 @@ int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int
  * (src/nets/nets.py:21-27) in its epilogue: y = act(x . w^T + bias). */
 int aurppo_linear_bias_act_f32(const float* x, const float* w, const float* bias, float* y, long long M, int K_w, int N_w,
                                int act, void* wop_ws, void* stream);
+/* The same forward product on a tile for small M (k_linear_small): a workgroup takes 128 rows x 32 or 64 columns where
+ * aurppo_linear_bias_act_f32's takes 256 x 128, so a few thousand rows reach every CU.  A row's k-steps, their order and their
+ * arithmetic are unchanged: every result is bit for bit aurppo_linear_bias_act_f32's.  Forward only.
+ *   aurppo_linear_small_bias_act_f32: argument list, limits, alignment and wop_ws of aurppo_linear_bias_act_f32; always the
+ *     small tile, whatever M.
+ *   aurppo_linear_pair_bias_act_f32: two products of one shape -- yA = act(xA . wA^T + biasA), yC = act(xC . wC^T + biasC), both
+ *     weights (N_w, K_w), both inputs (M, K_w) -- in ONE launch behind the two operand copies (three launches in all): the actor's
+ *     and the critic's layer of an MLP policy.  xA may be xC; each bias may be NULL; xA, xC 16-byte aligned at their bases.
+ *     wop_ws: aurppo_linear_pair_wop_bytes(K_w, N_w) bytes (0 for a non-positive size), 16-byte aligned.
+ * Both refuse before their first launch: AURPPO_EINVAL for a NULL pointer, an act outside {0, 1} or a misaligned x / wop_ws,
+ * AURPPO_ESHAPE for M, K_w or N_w below 1. */
+int aurppo_linear_small_bias_act_f32(const float* x, const float* w, const float* bias, float* y, long long M, int K_w, int N_w,
+                                     int act, void* wop_ws, void* stream);
+size_t aurppo_linear_pair_wop_bytes(int K_w, int N_w);
+int aurppo_linear_pair_bias_act_f32(const float* xA, const float* xC, const float* wA, const float* wC, const float* biasA,
+                                    const float* biasC, float* yA, float* yC, long long M, int K_w, int N_w, int act, void* wop_ws,
+                                    void* stream);
 /* nn.Linear's weight gradient on the same arithmetic: dw (N, K) = dy (M, N)^T . x (M, K) (what loss.backward() leaves in
  * <layer>.weight.grad, src/ppo.py:266).  Both operands are split once per workgroup through LDS; the minibatch's rows are cut
  * into slices whose partial products are summed in slice order (deterministic).  N a multiple of 4, any K >= 1; dy and x
@@ -380,6 +397,10 @@ int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC
  *     softmax(logits)); actions (N, A) | (N,), logp (N,), value (N,) go wherever the caller points them; noise and the outputs
  *     need 4-byte alignment only.  workspace: aurppo_mlp_layered_act_workspace_bytes(N, hidden) bytes, 64-byte aligned (the
  *     activations).  The log-prob is bit for bit the one aurppo_head_ppo_f32 forms from the stored action at the same parameters.
+ *   aurppo_mlp_layered_act_paired_f32: the same step -- same arguments, same checks, same wop and workspace, same bits in
+ *     actions, logp and value -- on the small-M products: per layer ONE launch for both nets (aurppo_linear_pair_bias_act_f32's
+ *     kernel, from the prepared copies), then K14: L + 1 launches; noise == NULL: the critic alone on the single small-tile
+ *     product, L + 1 launches.  For rollouts of a few thousand environments, where the step above leaves most CUs idle.
  *   aurppo_head_act_f32: K14 alone, from the last hidden activations hA, hC (N, H), 16-byte aligned (hA may be NULL without
  *     noise); layout_h: 5 float offsets {actor head weight (A, H), actor head bias, critic head weight (1, H), critic head bias,
  *     actor_logstd (ignored for the Categorical head)}.
@@ -393,6 +414,9 @@ size_t aurppo_mlp_layered_act_workspace_bytes(int N, int hidden);
 int aurppo_mlp_layered_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
                                int num_layers, const float* params, const int* offsets, int n_params, float* actions, float* logp,
                                float* value, const void* wop, void* workspace, void* stream);
+int aurppo_mlp_layered_act_paired_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                      int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                      float* logp, float* value, const void* wop, void* workspace, void* stream);
 int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
                         const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
                         void* stream);

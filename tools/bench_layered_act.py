@@ -1,9 +1,13 @@
 """One rollout step of an MLP policy wider than the fused kernels at N = 4096 (D 64, A 6, Gaussian head; 2 x 256 and 3 x 256): the
 torch-modules route (``policy.evaluate`` under no_grad + the three buffer row stores, what ``ppo.rewards_to_go`` does with
-AURPPO_LAYERED_ACT=0) against ``hip_ops.mlp_layered_act`` with weights prepared once (a rollout) and prepared in every call, all eager.
+AURPPO_LAYERED_ACT=0) against ``hip_ops.mlp_layered_act`` with weights prepared once (a rollout) and prepared in every call, and against
+its paired route (``paired=True``: the small-M products, both nets' layer in one launch; weights prepared once), all eager.
 The arms run in the same process, alternating: ROUNDS rounds of one batch of STEPS steps per arm between device events, after a
-warm-up; every batch's time is printed so the spread shows.  Prints one JSON object (``profiles/layered_act_bench.json`` holds one); run on the GPU box:
-    python tools/bench_layered_act.py > layered_act_bench.json"""
+warm-up; every batch's time is printed so the spread shows.  Prints one JSON object (``profiles/layered_act_bench.json`` and
+``profiles/layered_act_paired_bench.json`` hold one each); run on the GPU box:
+    python tools/bench_layered_act.py > layered_act_bench.json
+Arm names as arguments keep those arms only (a kernel trace of two routes:
+    rocprofv3 --kernel-trace --stats -- python tools/bench_layered_act.py layered_act_prepared layered_act_paired)."""
 import json
 import os
 import sys
@@ -28,7 +32,7 @@ def batch(fn):
     return e0.elapsed_time(e1) / STEPS * 1e3
 
 
-def main():
+def main(only=()):
     rows = []
     for hidden, layers in [(256, 2), (256, 3)]:
         torch.manual_seed(0)
@@ -51,7 +55,11 @@ def main():
 
         arms = {"torch_modules": torch_route,
                 "layered_act_prepared": lambda: H.mlp_layered_act(obs, noise, bucket.flat_param, lay, actions, logp, value, wop=wop),
-                "layered_act_unprepared": lambda: H.mlp_layered_act(obs, noise, bucket.flat_param, lay, actions, logp, value)}
+                "layered_act_unprepared": lambda: H.mlp_layered_act(obs, noise, bucket.flat_param, lay, actions, logp, value),
+                "layered_act_paired": lambda: H.mlp_layered_act(obs, noise, bucket.flat_param, lay, actions, logp, value, wop=wop,
+                                                                paired=True)}
+        if only:
+            arms = {k: fn for k, fn in arms.items() if k in only}
         for fn in arms.values():
             for _ in range(WARMUP):
                 fn()
@@ -60,7 +68,8 @@ def main():
         for _ in range(ROUNDS):
             for k, fn in arms.items():
                 times[k].append(round(batch(fn), 2))
-        row = dict(hidden=hidden, layers=layers, launches_prepared=2 * layers + 1, launches_unprepared=4 * layers + 1)
+        row = dict(hidden=hidden, layers=layers, launches_prepared=2 * layers + 1, launches_unprepared=4 * layers + 1,
+                   launches_paired=layers + 1)
         for k, ts in times.items():
             s = sorted(ts)
             row[k] = dict(us_per_step=ts, median=s[len(s) // 2], min=s[0], max=s[-1])
@@ -71,4 +80,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(tuple(sys.argv[1:]))
