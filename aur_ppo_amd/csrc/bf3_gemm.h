@@ -74,7 +74,7 @@ inline Bf3Grid bf3_grid(long long M, int N) {
     const int nblk = (N + 31) / 32, NB = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
     return {(M + 32 * 4 * kMB - 1) / (32 * 4 * kMB), NB, (nblk + NB - 1) / NB};
 }
-// The small-M tile of the forward linear products (linear_small_body.h): 4 waves x ONE block of 32 rows, NB of 1 or 2 -- n_mb
+// The small-M tile of the forward linear products (linear_body.h at MB = 1): 4 waves x ONE block of 32 rows, NB of 1 or 2 -- n_mb
 // workgroups of 128 rows x n_ng groups of NB blocks, for each of the launch's `nets` same-shaped products (the paired form: 2).
 // The NB rule, from measurement (DESIGN 4.12 has the table): 2 where the launch then still has two workgroups for each of the
 // chip's 256 CUs, else 1 -- twice the workgroups, each splitting its A values for one column block only.  Below that NB 1 won

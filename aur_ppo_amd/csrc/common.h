@@ -70,16 +70,19 @@ int launch_dyn_lds(const char* name, int grid, int threads, size_t lds, size_t l
 int aurppo_cu_count(int fallback);
 // The prepared-operand half of the linear products (linear.hip), for the layered steps (layered.hip): bytes of one forward operand
 // copy of a (N, K) weight, the launch that writes it (conv.hip; mode 0; 1: the input gradient's), and y (M, N) = act(x (M, K) . w^T + bias)
-// from such a copy (act: 0 none, 1 tanh).
+// from such copies (act: 0 none, 1 tanh): `nets` same-shaped products, one operand set each, in one launch -- on k_linear's tile
+// (nets = 1), or with `small` on the small-M tile (k_linear_small; nets = 2: k_linear_pair).  Same bits on either tile.  Refusals carry
+// the calling entry's name `who`.
 constexpr int kLayeredMaxLayers = 16;
 size_t aurppo_linear_wop_bytes(int K, int N);
 int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop, hipStream_t s);
-int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N, void* stream);
-// the same product on the small-M tile (k_linear_small), and two nets' same-shaped products in one launch (k_linear_pair): same bits
-int aurppo_linear_small_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                                 void* stream);
-int aurppo_linear_pair_prepared(const float* xA, const float* xC, const void* wopA, const void* wopC, const float* biasA, const float* biasC,
-                                int act, float* yA, float* yC, long long M, int K, int N, void* stream);
+struct LinOps {
+    const float* x;                  // (M, K)
+    const void* wop;                 // the operand copy of the (N, K) weight
+    const float* bias;               // (N,) or nullptr
+    float* y;                        // (M, N)
+};
+int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream);
 // K13 / K14's shape rule and K14 on checked operands (head.hip), for the layered steps
 bool head_shape_ok(int H, int A, int continuous);
 int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,

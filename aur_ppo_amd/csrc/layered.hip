@@ -149,7 +149,7 @@ namespace {
 
 // The rollout step behind both entries.  paired: per layer ONE launch of the paired small-tile product for both nets (k_linear_pair),
 // L + 1 launches with K14; without noise the critic alone on the single small-tile product (k_linear_small), L + 1 as well.  The
-// bits are the unpaired route's: a row's result does not depend on the tile (linear_small_body.h).
+// bits are the unpaired route's: a row's result does not depend on the tile (linear_body.h).
 int layered_act_impl(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden, int num_layers,
                      const float* params, const int* offsets, int n_params, float* actions, float* logp, float* value, const void* wop,
                      void* workspace, void* stream, bool paired, const char* who) {
@@ -169,41 +169,20 @@ int layered_act_impl(const float* obs, const float* noise, int N, int D, int A, 
     const char* const wbase = reinterpret_cast<const char*>(wop);
     const size_t net_wop = aurppo_linear_wop_bytes(D, hidden) + (size_t)(L - 1) * aurppo_linear_wop_bytes(hidden, hidden);
     auto out = [&](int net, int l) { return reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)(2 * net + (l & 1)) * plane); };
-    const float* last[2] = {nullptr, nullptr};
-    if (paired && noise) {
-        const int *oA = offsets, *oC = offsets + per;
-        const char* w = wbase;
-        const float *xA = obs, *xC = obs;
-        for (int l = 0; l < L; ++l) {
-            const int K = l ? hidden : D;
-            if (const int rc = aurppo_linear_pair_prepared(xA, xC, w, w + net_wop, params + oA[2 * l + 1], params + oC[2 * l + 1], 1, out(0, l),
-                                                           out(1, l), N, K, hidden, stream))
-                return rc;
-            w += aurppo_linear_wop_bytes(K, hidden);
-            xA = out(0, l);
-            xC = out(1, l);
-        }
-        last[0] = xA;
-        last[1] = xC;
-    } else {
-        for (int net = noise ? 0 : 1; net < 2; ++net) {
-            const int* o = offsets + net * per;
-            const char* w = wbase + net * net_wop;
-            const float* x = obs;
-            for (int l = 0; l < L; ++l) {
-                const int K = l ? hidden : D;
-                float* y = out(net, l);
-                const int rc = paired ? aurppo_linear_small_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream)
-                                      : aurppo_linear_prepared(x, w, params + o[2 * l + 1], 1, y, N, K, hidden, stream);
-                if (rc != AURPPO_OK) return rc;
-                w += aurppo_linear_wop_bytes(K, hidden);
-                x = y;
-            }
-            last[net] = x;
-        }
+    const int first = noise ? 0 : 1;                   // the live nets are [first, 2): both, or the critic alone
+    const bool pair = paired && first == 0;
+    LinOps ops[2] = {};                                // (a net that does not run keeps its null pointers: K14 is not handed an actor)
+    size_t at = 0;                                     // layer l's operand copy inside its net's
+    for (int l = 0; l < L; ++l) {
+        const int K = l ? hidden : D;
+        for (int net = first; net < 2; ++net)
+            ops[net] = {l ? out(net, l - 1) : obs, wbase + net * net_wop + at, params + offsets[net * per + 2 * l + 1], out(net, l)};
+        for (int net = first; net < (pair ? 1 : 2); ++net)          // one launch for both nets, or one per live net on the chosen tile
+            if (const int rc = aurppo_linear_forward(who, paired, pair ? 2 : 1, ops + net, 1, N, K, hidden, stream)) return rc;
+        at += aurppo_linear_wop_bytes(K, hidden);
     }
     const int lay[5] = {offsets[2 * L], offsets[2 * L + 1], offsets[per + 2 * L], offsets[per + 2 * L + 1], offsets[2 * per]};
-    return head_act_launch(last[0], last[1], noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
+    return head_act_launch(ops[0].y, ops[1].y, noise, N, hidden, A, continuous, params, lay, actions, logp, value, (hipStream_t)stream);
 }
 
 }  // namespace

@@ -33,15 +33,20 @@ struct LinArgs {
 // k-steps against an operand copy whose columns >= K are zero planes (k_linear_prep_tail).  A row is K floats and nothing more: it
 // starts at a 4-byte boundary, what follows it is another row, somebody else's memory or an unmapped page.  So every k-step's A values
 // are eight dword loads per lane, each one issued only where its column is < K, and the columns >= K enter split3 as a selected 0.
-// The two kernel templates share one body text, linear_body.h (it says why a text): KTAIL is a constant of the including kernel.
+// Every product kernel below shares one body text, linear_body.h (it says why a text): KTAIL, MB (32-row blocks per wave) and `wg` (the
+// workgroup's index inside its product's grid) are names of the including kernel.
 template <int NB, bool ROWS = false, bool GATE = false>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
     constexpr bool KTAIL = false, GRAD = GATE;
+    constexpr int MB = kMB;
+    const unsigned wg = blockIdx.x;
 #include "linear_body.h"
 }
 template <int NB, bool ROWS>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_tail(const LinArgs a) {
     constexpr bool GATE = false, GRAD = false, KTAIL = true;
+    constexpr int MB = kMB;
+    const unsigned wg = blockIdx.x;
 #include "linear_body.h"
 }
 // GRAD: the product is an input gradient (mode 1), whose k-steps change sign in another order in every other block of 32 rows
@@ -50,15 +55,16 @@ template <int NB, bool ROWS, bool GATE, bool GRAD>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear(const LinArgs a) {
     static_assert(GRAD && !ROWS && !GATE, "the plain input gradient");
     constexpr bool KTAIL = false;
+    constexpr int MB = kMB;
+    const unsigned wg = blockIdx.x;
 #include "linear_body.h"
 }
 
-// ---- the small-M builds of the forward product (linear_small_body.h says what they keep of k_linear: everything a row's bits depend
-// on).  New templates with a body text of their own, not parameters on the templates above: those keep their symbols and their
-// instruction streams.  k_linear_small / k_linear_small_tail: one product.  k_linear_pair / k_linear_pair_tail: the same-shaped product
-// of two nets (the layered rollout's actor and critic, layer by layer) in one launch -- workgroups [0, per_net) are net 0's grid,
-// [per_net, 2 per_net) net 1's; the net's four pointers are selected once, ahead of the body, so the k loop has no branch on the net.
-// The two x pointers may be equal (layer 0: both nets read the observations).
+// ---- the small-M builds of the forward product: the same body text at MB = 1 (linear_body.h says why the bits are k_linear's).  New
+// templates, not parameters on the templates above: those keep their symbols.  k_linear_small / k_linear_small_tail: one product.
+// k_linear_pair / k_linear_pair_tail: the same-shaped product of two nets (the layered rollout's actor and critic, layer by layer) in
+// one launch -- workgroups [0, per_net) are net 0's grid, [per_net, 2 per_net) net 1's; the net's four pointers are selected once,
+// ahead of the body, so the k loop has no branch on the net.  The two x pointers may be equal (layer 0: both nets read the observations).
 struct LinPairArgs {
     const float* x[2];               // (M, K) each
     const unsigned short* wop[2];    // each net's operand copy, the layout above
@@ -70,15 +76,17 @@ struct LinPairArgs {
 };
 template <int NB>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_small(const LinArgs a) {
-    constexpr bool KTAIL = false;
+    constexpr bool KTAIL = false, ROWS = false, GATE = false, GRAD = false;
+    constexpr int MB = 1;
     const unsigned wg = blockIdx.x;
-#include "linear_small_body.h"
+#include "linear_body.h"
 }
 template <int NB>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_small_tail(const LinArgs a) {
-    constexpr bool KTAIL = true;
+    constexpr bool KTAIL = true, ROWS = false, GATE = false, GRAD = false;
+    constexpr int MB = 1;
     const unsigned wg = blockIdx.x;
-#include "linear_small_body.h"
+#include "linear_body.h"
 }
 __device__ __forceinline__ LinArgs pair_net_args(const LinPairArgs& p, unsigned net) {
     LinArgs a;
@@ -92,17 +100,19 @@ __device__ __forceinline__ LinArgs pair_net_args(const LinPairArgs& p, unsigned 
 }
 template <int NB>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_pair(const LinPairArgs p) {
-    constexpr bool KTAIL = false;
+    constexpr bool KTAIL = false, ROWS = false, GATE = false, GRAD = false;
+    constexpr int MB = 1;
     const unsigned net = blockIdx.x >= p.per_net ? 1u : 0u, wg = blockIdx.x - net * p.per_net;
     const LinArgs a = pair_net_args(p, net);
-#include "linear_small_body.h"
+#include "linear_body.h"
 }
 template <int NB>
 __global__ __launch_bounds__(kConvThreads, 2) void k_linear_pair_tail(const LinPairArgs p) {
-    constexpr bool KTAIL = true;
+    constexpr bool KTAIL = true, ROWS = false, GATE = false, GRAD = false;
+    constexpr int MB = 1;
     const unsigned net = blockIdx.x >= p.per_net ? 1u : 0u, wg = blockIdx.x - net * p.per_net;
     const LinArgs a = pair_net_args(p, net);
-#include "linear_small_body.h"
+#include "linear_body.h"
 }
 
 // ---- nn.Linear's weight gradient on the same arithmetic: dW (N, K) = dY^T (N, M) . X (M, K), both operands row-major with the
@@ -149,30 +159,71 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const Wgr
 
 }  // namespace
 
-// The two halves of a product, host side: the filter into operand order (linear_prep, conv.hip) and k_linear from an operand copy that
-// exists.  linear_impl does both per call; the layered rollout step (layered.hip) builds the copies once per rollout.
-static int linear_launch(const float* x, const unsigned short* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                         hipStream_t s, const int32_t* rows, const float* h, bool grad = false) {
-    LinArgs a;
-    a.x = x; a.wop = wop; a.y = y; a.M = M; a.K = K; a.N = N;
-    a.bias = bias; a.act = act; a.rows = rows; a.h = h;
-    const Bf3Grid gr = bf3_grid(M, N);
-    AURPPO_REQUIRE(gr.n_mb * gr.n_ng < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_f32: grid too large");
-    a.n_mb = (int)gr.n_mb;
+// The two halves of a product, host side: the filter into operand order (linear_prep, conv.hip) and a k_linear* kernel from an operand
+// copy that exists.  linear_impl and the small / paired entries do both per call; the layered rollout step (layered.hip) builds the
+// copies once per rollout and comes in through aurppo_linear_forward.
+// linear_launch is the second half for every product on checked operands: `small` the tile (k_linear's 256 rows x NB <= 4 blocks, or
+// the small-M tile with its NB from bf3_small_grid), `nets` same-shaped products in ONE launch (2: the small tile only, k_linear_pair)
+// from ops[0 .. nets).  rows, h, grad: the large tile's index, gate and input-gradient builds.
+static int linear_launch(bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, hipStream_t s,
+                         const int32_t* rows = nullptr, const float* h = nullptr, bool grad = false) {
+    const Bf3Grid gr = small ? bf3_small_grid(M, N, nets) : bf3_grid(M, N);
+    const long long per_net = gr.n_mb * gr.n_ng;
+    AURPPO_REQUIRE(per_net * nets < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", small ? "aurppo_linear_small_bias_act_f32" : "aurppo_linear_f32");
     AURPPO_REQUIRE(K % 16 == 0 || !(h || grad), AURPPO_ESHAPE, "aurppo_linear_f32: the input gradient's inner dimension %d (a multiple of 16)", K);
     AURPPO_REQUIRE(!(grad && rows), AURPPO_EINVAL, "aurppo_linear_f32: an input gradient through an index");
-    const dim3 g((unsigned)(gr.n_mb * gr.n_ng)), blk(kConvThreads);
-    bf3_with_nb(gr.NB, [&](auto nb) {
-        constexpr int NB = decltype(nb)::value;
-        if (K % 16 != 0) {
-            if (rows) hipLaunchKernelGGL((k_linear_tail<NB, true>), g, blk, 0, s, a);
-            else hipLaunchKernelGGL((k_linear_tail<NB, false>), g, blk, 0, s, a);
-        } else if (h) hipLaunchKernelGGL((k_linear<NB, false, true>), g, blk, 0, s, a);
-        else if (grad) hipLaunchKernelGGL((k_linear<NB, false, false, true>), g, blk, 0, s, a);
-        else if (rows) hipLaunchKernelGGL((k_linear<NB, true, false>), g, blk, 0, s, a);
-        else hipLaunchKernelGGL(k_linear<NB>, g, blk, 0, s, a);
-    });
-    AURPPO_LAUNCH_CHECK("k_linear");
+    LinArgs a;
+    LinPairArgs p;
+    for (int net = 0; net < nets; ++net) {
+        p.x[net] = ops[net].x; p.wop[net] = reinterpret_cast<const unsigned short*>(ops[net].wop); p.y[net] = ops[net].y; p.bias[net] = ops[net].bias;
+    }
+    a.x = p.x[0]; a.wop = p.wop[0]; a.y = p.y[0]; a.bias = p.bias[0]; a.rows = rows; a.h = h;
+    a.M = p.M = M; a.K = p.K = K; a.N = p.N = N; a.n_mb = p.n_mb = (int)gr.n_mb; a.act = p.act = act;
+    p.per_net = (unsigned)per_net;
+    const dim3 g((unsigned)(per_net * nets)), blk(kConvThreads);
+    const bool tail = K % 16 != 0, nb2 = gr.NB == 2;
+    if (nets == 2) {
+        if (tail && nb2) hipLaunchKernelGGL(k_linear_pair_tail<2>, g, blk, 0, s, p);
+        else if (tail) hipLaunchKernelGGL(k_linear_pair_tail<1>, g, blk, 0, s, p);
+        else if (nb2) hipLaunchKernelGGL(k_linear_pair<2>, g, blk, 0, s, p);
+        else hipLaunchKernelGGL(k_linear_pair<1>, g, blk, 0, s, p);
+        AURPPO_LAUNCH_CHECK("k_linear_pair");
+    } else if (small) {
+        if (tail && nb2) hipLaunchKernelGGL(k_linear_small_tail<2>, g, blk, 0, s, a);
+        else if (tail) hipLaunchKernelGGL(k_linear_small_tail<1>, g, blk, 0, s, a);
+        else if (nb2) hipLaunchKernelGGL(k_linear_small<2>, g, blk, 0, s, a);
+        else hipLaunchKernelGGL(k_linear_small<1>, g, blk, 0, s, a);
+        AURPPO_LAUNCH_CHECK("k_linear_small");
+    } else {
+        bf3_with_nb(gr.NB, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            if (tail) {
+                if (rows) hipLaunchKernelGGL((k_linear_tail<NB, true>), g, blk, 0, s, a);
+                else hipLaunchKernelGGL((k_linear_tail<NB, false>), g, blk, 0, s, a);
+            } else if (h) hipLaunchKernelGGL((k_linear<NB, false, true>), g, blk, 0, s, a);
+            else if (grad) hipLaunchKernelGGL((k_linear<NB, false, false, true>), g, blk, 0, s, a);
+            else if (rows) hipLaunchKernelGGL((k_linear<NB, true, false>), g, blk, 0, s, a);
+            else hipLaunchKernelGGL(k_linear<NB>, g, blk, 0, s, a);
+        });
+        AURPPO_LAUNCH_CHECK("k_linear");
+    }
+    return AURPPO_OK;
+}
+
+// What every forward entry on operand copies refuses, once per call and under the entry's name `who`: `copy` is what the entry calls
+// the memory behind ops[].wop, `others` whether the pointers that only the entry knows (its weights) are there.
+static int linear_forward_check(const char* who, const char* copy, bool others, bool small, int nets, const LinOps* ops, int act,
+                                long long M, int K, int N) {
+    AURPPO_REQUIRE(nets == 1 || (nets == 2 && small), AURPPO_EINVAL, "%s: %d products in one launch", who, nets);
+    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "%s: act %d", who, act);
+    bool there = others, aligned = true;
+    for (int net = 0; net < nets; ++net) {
+        there = there && ops[net].x && ops[net].wop && ops[net].y;
+        aligned = aligned && aligned_to(ops[net].x, 16) && aligned_to(ops[net].wop, 16);
+    }
+    AURPPO_REQUIRE(there, AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "%s: M=%lld, inner dimension %d, %d columns", who, M, K, N);
+    AURPPO_REQUIRE(aligned, AURPPO_EINVAL, "%s: x / %s not 16-byte aligned", who, copy);
     return AURPPO_OK;
 }
 
@@ -190,7 +241,8 @@ static int linear_impl(const float* x, const float* w, const float* bias, int ac
     hipStream_t s = (hipStream_t)stream;
     unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
     if (const int rc = linear_prep(w, K_w, N_w, mode, wop, s)) return rc;
-    return linear_launch(x, wop, bias, act, y, M, K, N, s, rows, h, mode == 1);
+    const LinOps ops = {x, wop, bias, y};
+    return linear_launch(false, 1, &ops, act, M, K, N, s, rows, h, mode == 1);
 }
 
 extern "C" int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,
@@ -225,88 +277,21 @@ extern "C" int aurppo_linear_dx_tanh_f32(const float* gz, const float* w, const 
 // ---- prepared weights for the layered rollout step (layered.hip).  Bytes of one forward operand copy: the blocks k_conv_prep writes and one group of slack, as a workgroup reads whole groups.
 size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + kNBW) * (size_t)((K + 15) / 16) * 3 * 1024; }
 
-// y (M, N) = act(x (M, K) . B + bias) from the operand copy `wop` of a (N, K) weight: linear_impl without its k_conv_prep launch.
-int aurppo_linear_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                           void* stream) {
-    AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_prepared: null pointer");
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_prepared: x / operand copy not 16-byte aligned");
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_prepared: act %d", act);
-    return linear_launch(x, reinterpret_cast<const unsigned short*>(wop), bias, act, y, M, K, N, (hipStream_t)stream, nullptr, nullptr);
-}
-
-// ---- the small-M forward products.  One product (nets = 1: entry 0 of every array) or the pair (nets = 2), from operand copies that
-// exist; the tile and its NB are bf3_small_grid's.  Checked operands only: the entries below refuse first.
-static int linear_small_launch(int nets, const float* const x[2], const unsigned short* const wop[2], const float* const bias[2], int act,
-                               float* const y[2], long long M, int K, int N, hipStream_t s) {
-    const Bf3Grid gr = bf3_small_grid(M, N, nets);
-    const long long per_net = gr.n_mb * gr.n_ng;
-    AURPPO_REQUIRE(per_net * nets < (1ll << 31), AURPPO_ESHAPE, "aurppo_linear_small_bias_act_f32: grid too large");
-    const dim3 g((unsigned)(per_net * nets)), blk(kConvThreads);
-    const bool tail = K % 16 != 0, nb2 = gr.NB == 2;
-    if (nets == 1) {
-        LinArgs a;
-        a.x = x[0]; a.wop = wop[0]; a.y = y[0]; a.bias = bias[0]; a.M = M; a.K = K; a.N = N; a.n_mb = (int)gr.n_mb; a.act = act;
-        a.rows = nullptr; a.h = nullptr;
-        if (tail && nb2) hipLaunchKernelGGL(k_linear_small_tail<2>, g, blk, 0, s, a);
-        else if (tail) hipLaunchKernelGGL(k_linear_small_tail<1>, g, blk, 0, s, a);
-        else if (nb2) hipLaunchKernelGGL(k_linear_small<2>, g, blk, 0, s, a);
-        else hipLaunchKernelGGL(k_linear_small<1>, g, blk, 0, s, a);
-        AURPPO_LAUNCH_CHECK("k_linear_small");
-        return AURPPO_OK;
-    }
-    LinPairArgs p;
-    for (int net = 0; net < 2; ++net) {
-        p.x[net] = x[net]; p.wop[net] = wop[net]; p.y[net] = y[net]; p.bias[net] = bias[net];
-    }
-    p.M = M; p.K = K; p.N = N; p.n_mb = (int)gr.n_mb; p.act = act; p.per_net = (unsigned)per_net;
-    if (tail && nb2) hipLaunchKernelGGL(k_linear_pair_tail<2>, g, blk, 0, s, p);
-    else if (tail) hipLaunchKernelGGL(k_linear_pair_tail<1>, g, blk, 0, s, p);
-    else if (nb2) hipLaunchKernelGGL(k_linear_pair<2>, g, blk, 0, s, p);
-    else hipLaunchKernelGGL(k_linear_pair<1>, g, blk, 0, s, p);
-    AURPPO_LAUNCH_CHECK("k_linear_pair");
-    return AURPPO_OK;
-}
-
-// aurppo_linear_prepared on the small tile, and its paired form: both nets' same-shaped products in one launch (layered.hip)
-int aurppo_linear_small_prepared(const float* x, const void* wop, const float* bias, int act, float* y, long long M, int K, int N,
-                                 void* stream) {
-    AURPPO_REQUIRE(x && wop && y, AURPPO_EINVAL, "aurppo_linear_small_prepared: null pointer");
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_small_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop, 16), AURPPO_EINVAL, "aurppo_linear_small_prepared: x / operand copy not 16-byte aligned");
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_small_prepared: act %d", act);
-    const float* const xs[2] = {x, nullptr};
-    const unsigned short* const ws[2] = {reinterpret_cast<const unsigned short*>(wop), nullptr};
-    const float* const bs[2] = {bias, nullptr};
-    float* const ys[2] = {y, nullptr};
-    return linear_small_launch(1, xs, ws, bs, act, ys, M, K, N, (hipStream_t)stream);
-}
-int aurppo_linear_pair_prepared(const float* xA, const float* xC, const void* wopA, const void* wopC, const float* biasA, const float* biasC,
-                                int act, float* yA, float* yC, long long M, int K, int N, void* stream) {
-    AURPPO_REQUIRE(xA && xC && wopA && wopC && yA && yC, AURPPO_EINVAL, "aurppo_linear_pair_prepared: null pointer");
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0, AURPPO_ESHAPE, "aurppo_linear_pair_prepared: M=%lld, inner dimension %d, %d columns", M, K, N);
-    AURPPO_REQUIRE(aligned_to(xA, 16) && aligned_to(xC, 16) && aligned_to(wopA, 16) && aligned_to(wopC, 16), AURPPO_EINVAL,
-                   "aurppo_linear_pair_prepared: x / operand copy not 16-byte aligned");
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_pair_prepared: act %d", act);
-    const float* const xs[2] = {xA, xC};
-    const unsigned short* const ws[2] = {reinterpret_cast<const unsigned short*>(wopA), reinterpret_cast<const unsigned short*>(wopC)};
-    const float* const bs[2] = {biasA, biasC};
-    float* const ys[2] = {yA, yC};
-    return linear_small_launch(2, xs, ws, bs, act, ys, M, K, N, (hipStream_t)stream);
+// y (M, N) = act(x (M, K) . B + bias) for each of ops[0 .. nets), from the operand copies of (N, K) weights: the forward products without
+// their k_conv_prep launch, on the large tile or the small one (common.h)
+int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream) {
+    if (const int rc = linear_forward_check(who, "operand copy", true, small, nets, ops, act, M, K, N)) return rc;
+    return linear_launch(small, nets, ops, act, M, K, N, (hipStream_t)stream);
 }
 
 // aurppo_linear_bias_act_f32 on the small tile, whatever M: same argument list, same checks, same bits
 extern "C" int aurppo_linear_small_bias_act_f32(const float* x, const float* w, const float* bias, float* y, long long M, int K_w, int N_w,
                                                 int act, void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_small_bias_act_f32: act %d", act);
-    AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_small_bias_act_f32: null pointer");
-    AURPPO_REQUIRE(M > 0 && K_w > 0 && N_w > 0, AURPPO_ESHAPE, "aurppo_linear_small_bias_act_f32: M=%lld, inner dimension %d, %d columns", M,
-                   K_w, N_w);
-    AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL,
-                   "aurppo_linear_small_bias_act_f32: x / workspace not 16-byte aligned");
-    unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    if (const int rc = linear_prep(w, K_w, N_w, 0, wop, (hipStream_t)stream)) return rc;
-    return aurppo_linear_small_prepared(x, wop, bias, act, y, M, K_w, N_w, stream);
+    const LinOps ops = {x, wop_ws, bias, y};
+    if (const int rc = linear_forward_check("aurppo_linear_small_bias_act_f32", "workspace", w != nullptr, true, 1, &ops, act, M, K_w, N_w))
+        return rc;
+    if (const int rc = linear_prep(w, K_w, N_w, 0, reinterpret_cast<unsigned short*>(wop_ws), (hipStream_t)stream)) return rc;
+    return linear_launch(true, 1, &ops, act, M, K_w, N_w, (hipStream_t)stream);
 }
 
 // Both nets' operand copies, one behind the other: 2 x aurppo_linear_wop_bytes (a multiple of 1 KB, so the second is aligned too)
@@ -320,17 +305,13 @@ extern "C" size_t aurppo_linear_pair_wop_bytes(int K_w, int N_w) {
 extern "C" int aurppo_linear_pair_bias_act_f32(const float* xA, const float* xC, const float* wA, const float* wC, const float* biasA,
                                                const float* biasC, float* yA, float* yC, long long M, int K_w, int N_w, int act,
                                                void* wop_ws, void* stream) {
-    AURPPO_REQUIRE(act == 0 || act == 1, AURPPO_EINVAL, "aurppo_linear_pair_bias_act_f32: act %d", act);
-    AURPPO_REQUIRE(xA && xC && wA && wC && yA && yC && wop_ws, AURPPO_EINVAL, "aurppo_linear_pair_bias_act_f32: null pointer");
-    AURPPO_REQUIRE(M > 0 && K_w > 0 && N_w > 0, AURPPO_ESHAPE, "aurppo_linear_pair_bias_act_f32: M=%lld, inner dimension %d, %d columns", M,
-                   K_w, N_w);
-    AURPPO_REQUIRE(aligned_to(xA, 16) && aligned_to(xC, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL,
-                   "aurppo_linear_pair_bias_act_f32: x / workspace not 16-byte aligned");
     char* const wopA = reinterpret_cast<char*>(wop_ws);
-    char* const wopC = wopA + aurppo_linear_wop_bytes(K_w, N_w);
+    char* const wopC = wopA ? wopA + aurppo_linear_wop_bytes(K_w, N_w) : nullptr;
+    const LinOps ops[2] = {{xA, wopA, biasA, yA}, {xC, wopC, biasC, yC}};
+    if (const int rc = linear_forward_check("aurppo_linear_pair_bias_act_f32", "workspace", wA && wC, true, 2, ops, act, M, K_w, N_w)) return rc;
     if (const int rc = linear_prep(wA, K_w, N_w, 0, reinterpret_cast<unsigned short*>(wopA), (hipStream_t)stream)) return rc;
     if (const int rc = linear_prep(wC, K_w, N_w, 0, reinterpret_cast<unsigned short*>(wopC), (hipStream_t)stream)) return rc;
-    return aurppo_linear_pair_prepared(xA, xC, wopA, wopC, biasA, biasC, act, yA, yC, M, K_w, N_w, stream);
+    return linear_launch(true, 2, ops, act, M, K_w, N_w, (hipStream_t)stream);
 }
 
 // the weight gradient's slice count (slices_for, conv.hip, says how the slices are used)

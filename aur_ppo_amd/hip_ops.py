@@ -450,6 +450,11 @@ def _optr(t, dtype=torch.float32):
     return _ptr(t, dtype) if t is not None else None
 
 
+def _obias(b):
+    """A linear wrapper's optional bias: its contiguous form's pointer, or None."""
+    return _optr(b.contiguous() if b is not None else None)
+
+
 # The argument order of the fused-step family (include/aurppo.h) lives in the builders below and nowhere else in this layer; each
 # returns one run of a call's arguments, and _lib._declare spells the matching run of argtypes.  A transposition inside a run of
 # same-typed pointers raises nothing on the host and faults on the GPU: tests/test_hip_ops_calls.py pins what every call passes.
@@ -1155,7 +1160,7 @@ def _linear_bias_act(x, rows, w, bias, act):
     Nw, Kw = w.shape
     y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
     ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
-    tail = (_ptr(w), _optr(bias.contiguous() if bias is not None else None), _ptr(y), M, Kw, Nw, int(act), *_ws_stream(ws))
+    tail = (_ptr(w), _obias(bias), _ptr(y), M, Kw, Nw, int(act), *_ws_stream(ws))
     if rows is None:
         _check(lib.aurppo_linear_bias_act_f32(_ptr(x), *tail), "aurppo_linear_bias_act_f32")
     else:
@@ -1180,8 +1185,8 @@ def linear_small_bias_act(x, w, bias, act=0):
         raise ValueError("linear_small_bias_act: shape mismatch")
     y = torch.empty((M, Nw), dtype=torch.float32, device=x.device)
     ws = _workspace("conv", lib.aurppo_conv3x3_wop_bytes(Kw, Nw), x.device)
-    _check(lib.aurppo_linear_small_bias_act_f32(_ptr(x), _ptr(w), _optr(bias.contiguous() if bias is not None else None), _ptr(y), M, Kw, Nw,
-                                                int(act), *_ws_stream(ws)), "aurppo_linear_small_bias_act_f32")
+    _check(lib.aurppo_linear_small_bias_act_f32(_ptr(x), _ptr(w), _obias(bias), _ptr(y), M, Kw, Nw, int(act), *_ws_stream(ws)),
+           "aurppo_linear_small_bias_act_f32")
     return y
 
 
@@ -1199,9 +1204,8 @@ def linear_pair_bias_act(xA, xC, wA, wC, bA, bC, act=0):
     yA = torch.empty((M, Nw), dtype=torch.float32, device=xA.device)
     yC = torch.empty((M, Nw), dtype=torch.float32, device=xA.device)
     ws = _workspace("conv_pair", lib.aurppo_linear_pair_wop_bytes(Kw, Nw), xA.device)
-    _check(lib.aurppo_linear_pair_bias_act_f32(_ptr(xA), _ptr(xC), _ptr(wA), _ptr(wC), _optr(bA.contiguous() if bA is not None else None),
-                                               _optr(bC.contiguous() if bC is not None else None), _ptr(yA), _ptr(yC), M, Kw, Nw, int(act),
-                                               *_ws_stream(ws)), "aurppo_linear_pair_bias_act_f32")
+    _check(lib.aurppo_linear_pair_bias_act_f32(_ptr(xA), _ptr(xC), _ptr(wA), _ptr(wC), _obias(bA), _obias(bC), _ptr(yA), _ptr(yC), M, Kw, Nw,
+                                               int(act), *_ws_stream(ws)), "aurppo_linear_pair_bias_act_f32")
     return yA, yC
 
 
