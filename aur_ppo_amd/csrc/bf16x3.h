@@ -6,7 +6,7 @@
 // through one accumulator, as mma32x3 does, a third-order product is dropped once the sum has grown past 2^8 terms or so, and the
 // pipe cuts towards minus infinity: 11 % of the third-order products are gone at a reduction of 256, 70 % at 1024.  The convolutions
 // and the linear kernels -- K11, K12, K11n, K12n, k_linear*, k_linear_wgrad* -- sum every k-step from zero instead,
-// bf3_gemm.h::mma32x3_step, DESIGN 2.5.  Who still chains: the fused MLP steps K7 / K7w (mlp3.hip, mlp_wide.hip), whose products stay
+// bf3_gemm.h::mma32x3_step, DESIGN 2.5.  Who still chains: the fused MLP steps K7 / K7w (mlp3.hip, mlp_wide3.hip), whose products stay
 // inside one kernel and leave nothing to probe; DESIGN 2.1 holds them to fp64 bars.)  Six
 // v_mfma_f32_32x32x16_bf16 (32 cycles, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles, K = 2): 192 instead of
 // 512 matrix-pipe cycles per 32 x 32 x 16 block, at fp32 accuracy (tools/bf16x3_check.hip measures both).

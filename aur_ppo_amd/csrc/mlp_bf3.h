@@ -1,4 +1,4 @@
-// What the bf16-plane step kernels (k_mlp_step3 in mlp3.hip, k_mlpw3_step in mlp_wide.hip) share beyond bf16x3.h: the two epilogues
+// What the bf16-plane step kernels (k_mlp_step3 in mlp3.hip, k_mlpw3_step in mlp_wide3.hip) share beyond bf16x3.h: the two epilogues
 // that write a 32x32 accumulator block into an F image.  PL = bytes per plane of that image (64 features: bf3::kFPlane; K7w's 128).
 // Both includers say `#pragma clang fp contract(fast)` in front of their includes, and this code is written for that mode.
 #pragma once

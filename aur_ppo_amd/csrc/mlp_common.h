@@ -202,7 +202,7 @@ int launch_mlp_step2(const MlpArgs& a, int grid, hipStream_t s);
 size_t mlp_step3_lds_bytes();
 size_t mlp_step3_wop_bytes();
 int launch_mlp_step3(const MlpArgs& a, int grid, hipStream_t s);
-// mlp.hip: k_mlp_reduce alone (grads[p] = fixed-order sum over n_slabs slabs, loss scalars folded) -- mlp_wide.hip's tail.
+// mlp.hip: k_mlp_reduce alone (grads[p] = fixed-order sum over n_slabs slabs, loss scalars folded) -- K7w's tail (mlp_wide.hip: wide_step_impl).
 // sq_part / step_dev != nullptr: also leave the clip's partial sums of squares (one per 64 parameters) and advance the
 // Adam step count -- what launch_adam_tail (k_adam_chain without K7's extras: clip + Adam in one launch) then consumes.
 int launch_mlp_reduce(const float* slabs, const double* loss_part, int n_slabs, int n_params, const PpoHyper& h, float* grads,

@@ -69,7 +69,7 @@ __device__ __forceinline__ PpoSample ppo_sample(float newlogp, float oldlogp, fl
 }
 
 // ---- Per-element terms of the action distributions (src/models/actor_critic.py:36-50), shared by every fused step (mlp2.hip, mlp3.hip,
-// mlp_wide.hip, head.hip) and rollout kernel (mlp.hip, mlp_wide.hip, head.hip).  The loss terms are scalars: the sums over a row's outputs
+// mlp_wide.hip, mlp_wide3.hip, head.hip) and rollout kernel (mlp.hip, mlp_wide.hip, head.hip).  The loss terms are scalars: the sums over a row's outputs
 // stay in the loss lanes, whose layouts differ.  Sampling is here whole (below the terms): a Gaussian dimension is a scalar, and the
 // Categorical rows of K8, K8w and k_mlpw_step<> share one layout -- one lane per row, its logits behind a pointer into LDS.  The kernels
 // that hold a row elsewhere (k_head_ppo / k_head_act: registers; k_mlpw3_step: spread over lanes) keep their own Categorical sums.

@@ -1,4 +1,4 @@
-"""GPU: K7w / K8w (csrc/mlp_wide.hip) -- the fused minibatch step and rollout step for the MLP shapes the reference's CLI
+"""GPU: K7w / K8w (csrc/mlp_wide.hip, mlp_wide3.hip; shared text in mlp_wide.h) -- the fused minibatch step and rollout step for the MLP shapes the reference's CLI
 can ask for besides the default 64-64 (src/run_ppo.py:33,37 -d / -nl; src/nets/nets.py:19-53) -- against the per-op autograd
 path (K3 gather -> torch evaluate -> K5 loss -> autograd), the same treatment K7 gets in test_mlp_fused.py."""
 import numpy as np

@@ -17,8 +17,10 @@ import numpy as np
 
 # (layers, hidden, D, A, Gaussian head, packed records)
 K7_SHAPES = [(2, 64, 64, 6, True, False), (2, 64, 17, 3, True, False), (2, 64, 64, 12, True, True), (2, 64, 32, 5, False, False)]
+# (2 x 100 over 17: k_mlpw3_step's run-time trip counts over a ragged state, and under variant 2 k_mlpw_step's own-out-block dW_1;
+# 2 x 96 over 100: the <., 6, 8> build; 3 x 128 Categorical: the three-layer builds' other head)
 K7W_SHAPES = [(1, 64, 64, 6, True, False), (3, 64, 64, 6, True, False), (3, 128, 64, 6, True, False), (2, 128, 128, 16, True, False),
-              (1, 96, 64, 4, False, False)]
+              (1, 96, 64, 4, False, False), (2, 100, 17, 4, True, False), (2, 96, 100, 6, True, False), (3, 128, 64, 5, False, False)]
 MS, B = (1, 65, 70001), 71000
 HEAD_HS, HEAD_KINDS, HEAD_NS, HEAD_B = (32, 96, 256, 512, 1024), ((1, True), (16, True), (2, False), (16, False)), (1, 65, 4099), 4200
 # (layers, hidden, D): widths no fused kernel takes, or (32, 96) a state no fused kernel takes

@@ -6,7 +6,9 @@ Where code moved between files:  python tools/isa_diff.py --by-kernel <tree A> a
 pairs the kernels of the two file lists by mangled name (an anonymous-namespace kernel keeps its name whichever file holds it) and
 compares each pair's ordered code lines without their trailing comments, block labels .LBB<function index>_<n> taken without the
 index, which moves as soon as a file gains or loses a function.  Prints the kernels found on one side only, the table above for every
-pair that differs, and the counts."""
+pair that differs, and the counts.  Where a move also renamed a type in the kernels' signatures (out of an anonymous namespace, say):
+    python tools/isa_diff.py --by-kernel --rename OLD=NEW <tree A> ...
+replaces OLD by NEW in the first tree's kernel names before pairing."""
 import collections, difflib, os, re, subprocess, sys, tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -60,7 +62,7 @@ def table(names, ka, kb):
         print(f"  {k}\n" + "\n".join(f"    {n:28s} {str(u):>8s} {str(w):>8s}" for n, u, w in rows))
 
 
-def by_kernel(tree_a, names_a, tree_b, names_b):
+def by_kernel(tree_a, names_a, tree_b, names_b, rename=None):
     with tempfile.TemporaryDirectory() as tmp:
         ka, kb = {}, {}
         for tree, names, into in ((tree_a, names_a, ka), (tree_b, names_b, kb)):
@@ -70,6 +72,8 @@ def by_kernel(tree_a, names_a, tree_b, names_b):
                 assert not twice, f"{name}: defined in another file of the same tree too: {twice}"
                 into.update(found)
                 print(f"{tree} {name}: {len(found)} kernels")
+    if rename:
+        ka = {k.replace(*rename): v for k, v in ka.items()}
     for side, only in (("first", sorted(set(ka) - set(kb))), ("second", sorted(set(kb) - set(ka)))):
         print(f"in the {side} tree only: {len(only)}" + "".join(f"\n  {k}" for k in only))
     both = sorted(set(ka) & set(kb))
@@ -96,7 +100,9 @@ def main(tree_a, tree_b, names):
 
 if __name__ == "__main__":
     if sys.argv[1] == "--by-kernel":
-        cut = sys.argv.index("--")
-        by_kernel(sys.argv[2], sys.argv[3:cut], sys.argv[cut + 1], sys.argv[cut + 2:])
+        rename = sys.argv[3].split("=", 1) if sys.argv[2] == "--rename" else None
+        args = sys.argv[4 if rename else 2:]
+        cut = args.index("--")
+        by_kernel(args[0], args[1:cut], args[cut + 1], args[cut + 2:], rename)
     else:
         main(sys.argv[1], sys.argv[2], sys.argv[3:])
