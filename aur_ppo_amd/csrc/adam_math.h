@@ -1,6 +1,6 @@
 // Shared pieces of the fused clip + Adam step (K6b): the clip coefficient from the partial sums of squares and
 // torch's single-tensor Adam update for one element (src/ppo.py:80,268-269).  Used by clip.hip (flat bucket) and
-// mlp.hip (the chained minibatch step).
+// mlp_tail.hip (k_adam_chain: the chained minibatch step).
 #pragma once
 #include "common.h"
 

@@ -1,5 +1,6 @@
-// Shared pieces of the fused MLP kernels (K7 k_mlp_step2 / k_mlp_step3, K8 k_mlp_act): tile constants, the
-// argument block, the fp32 MFMA micro-kernels and the tanh used by every variant.
+// Shared pieces of the fused MLP kernels (K7 k_mlp_step2 / k_mlp_step3, K8 k_mlp_act, K7w / K8w): tile constants, the
+// argument block, the fp32 MFMA micro-kernels and the tanh used by every variant; the workspace carver; what K7's and K7w's
+// host paths do alike in front of their step kernel; the advantage partial sums; every operand-copy layout's index function.
 #pragma once
 #include "ppo_math.h"
 
@@ -20,7 +21,7 @@ constexpr int kMaxGrid = 256;
 constexpr int kStatBlocks = 256;
 
 // K7's gradient slabs: (kMaxGrid, slab_stride) floats, slab b's parameter p at b * slab_stride + p (bucket order).  The stride is
-// padded to 64 floats so that every slab row starts on a 256-B boundary: k_mlp_reduce then reads a row's 64 parameters of a
+// padded to 64 floats so that every slab row starts on a 256-B boundary: k_mlp_reduce_x4 (mlp_tail.hip) then reads a row's 64 parameters of a
 // workgroup as 16 aligned 16-byte loads (two whole 128-B lines).  The padding is never written and never read.
 __host__ __device__ constexpr int slab_stride(int n_params) { return (n_params + 63) & ~63; }
 
@@ -198,17 +199,35 @@ struct WsCarver {
 size_t mlp_step2_lds_bytes();
 int launch_mlp_step2(const MlpArgs& a, int grid, hipStream_t s);
 // mlp3.hip: the same step on bf16 MFMAs over three-way bf16 splits (AURPPO_K7_VARIANT=3); its operand-order weight copies (bf16x3.h:
-// wop3_prepare, run by k_adv_stats_idx; refreshed by k_adam_chain)
+// wop3_prepare, run by k_adv_stats_idx; refreshed by k_adam_chain, mlp_tail.hip)
 size_t mlp_step3_lds_bytes();
 size_t mlp_step3_wop_bytes();
 int launch_mlp_step3(const MlpArgs& a, int grid, hipStream_t s);
-// mlp.hip: k_mlp_reduce alone (grads[p] = fixed-order sum over n_slabs slabs, loss scalars folded) -- K7w's tail (mlp_wide.hip: wide_step_impl).
-// sq_part / step_dev != nullptr: also leave the clip's partial sums of squares (one per 64 parameters) and advance the
-// Adam step count -- what launch_adam_tail (k_adam_chain without K7's extras: clip + Adam in one launch) then consumes.
-int launch_mlp_reduce(const float* slabs, const double* loss_part, int n_slabs, int n_params, const PpoHyper& h, float* grads,
-                      float* out_scalars, hipStream_t s, double* sq_part = nullptr, float* step_dev = nullptr,
-                      unsigned* scratch_counter = nullptr,    // (with step_dev: a device word the kernel may clear)
-                      double beta1 = 0.0, double beta2 = 0.0, double* bc_out = nullptr);   // bc_out: {1 - beta1^t, 1 - beta2^t} for launch_adam_tail
+// ---- What K7's step path (mlp.hip: mlp_step_impl) and K7w's (mlp_wide.hip: wide_step_impl) do alike before their main kernel.  The
+// tail behind it -- slab reduce, optimizer launch -- is mlp_tail.h.
+// The refusals both make, in their order: null pointer, packed records, then the family's own shape checks (`shape_checks`: () -> return
+// code), M / n_params, vloss_mode.
+template <class ShapeChecks>
+int check_step_args(const char* who, bool pointers, const float* actions, int continuous, int A, int M, int n_params, int vloss_mode,
+                    ShapeChecks shape_checks) {
+    AURPPO_REQUIRE(pointers, AURPPO_EINVAL, "%s: null pointer", who);
+    // actions == NULL: packed records -- rec is (B, 16), floats 4.. of a record hold the sample's action row
+    AURPPO_REQUIRE(actions || (continuous ? A : 1) <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (action_dim=%d)", who, A);
+    if (const int rc = shape_checks()) return rc;
+    AURPPO_REQUIRE(M > 0 && n_params > 0, AURPPO_ESHAPE, "%s: M=%d n_params=%d", who, M, n_params);
+    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: bad vloss_mode %d", who, vloss_mode);
+    return AURPPO_OK;
+}
+// CUs the step kernels leave to the side stream's shuffle kernels: AURPPO_MLP_SPARE_CUS, default 8 (one per XCD)
+inline int spare_cus() {
+    const int k = aurppo_knobs().k7_spare_cus;
+    return k >= 0 ? k : 8;
+}
+// workgroups that form a minibatch's advantage partial sums: four elements per thread, at most kStatBlocks
+inline int stat_blocks_for(int M) {
+    const int sb = (M + kThreads * 4 - 1) / (kThreads * 4);
+    return sb > kStatBlocks ? kStatBlocks : sb;
+}
 // One thread's share of a minibatch's advantage partial sums: elements first, first + step, ... in that order (the sums are the
 // same bits as the plain loop's), four index loads and then four record loads in flight at a time -- the plain loop paid two
 // dependent memory round trips per element.
@@ -233,7 +252,7 @@ __device__ __forceinline__ void adv_partial_sums(const float4* __restrict__ rec,
 
 // ---- Operand-order copies of the weights.  Each layout has ONE index function, here, with its inverse beside it (tied by the
 // static_assert below): the kernel that builds a copy walks its entries and asks the inverse what each holds, the optimizer launch
-// that refreshes a copy in place (mlp.hip: refresh_operand_copies) asks the index where a weight sits.
+// that refreshes a copy in place (mlp_tail.hip: refresh_operand_copies) asks the index where a weight sits.
 // k_mlp_step2's w1op (built by k_adv_stats_idx): W1 of both nets as the B operand of the layer-1 chain, [4 roles][32 steps][64 lanes]:
 // role net * 2 + cb, step m, lane l hold W1[net][cb*32 + (l & 31)][2m + (l >> 5)], zero beyond D -- wave `role` reads its slice with 32
 // fully coalesced loads per tile.  (k_mlp_step3's bf16 planes of W1 / W2: bf3::wop3_places / wop3_prepare, bf16x3.h.)
@@ -309,10 +328,5 @@ struct WideCopies {
     float* wop;
     unsigned short* wop3;   // != nullptr: k_mlpw3_step's bf16-plane copies are the ones to refresh
 };
-// next_idx != nullptr: the launch also forms the next minibatch's advantage partial sums (stats: (kStatBlocks, 2) doubles).
-int launch_adam_tail(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int n_params, const double* sq_part,
-                     double max_norm, const float* lr_dev, const float* step_dev, double beta1, double beta2, double eps,
-                     float* out_norm, hipStream_t s, const WideCopies* wide = nullptr, const float4* rec = nullptr, int rec_stride = 1,
-                     const int32_t* next_idx = nullptr, int next_M = 0, double* stats = nullptr, const double* bc = nullptr);
 
 }  // namespace aurppo_mlp

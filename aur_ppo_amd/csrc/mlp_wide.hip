@@ -1,7 +1,7 @@
 // K7w / K8w: the fused PPO minibatch step (as K7, mlp.hip / mlp2.hip) and the rollout step (as K8) for every MLP
 // actor-critic the reference's CLI can ask for that is NOT the default 64-64 one: hidden_dim <= 128, num_layers 1..3,
 // state_dim <= 128 (src/nets/nets.py:19-53 builds `num_layers` Tanh layers of `hidden_dim`; flags src/run_ppo.py:33,37).
-// Same inputs, same outputs (per-workgroup gradient slabs + loss partials, folded by k_mlp_reduce; the optimizer
+// Same inputs, same outputs (per-workgroup gradient slabs + loss partials, folded by k_mlp_reduce, mlp_tail.hip; the optimizer
 // step is K6b's), same fp32 MFMA arithmetic -- what differs is where things live, because at 128 x 3 neither the
 // weights (2 x 192 KB) nor the weight-gradient accumulators (2 x 200 KB) of BOTH nets fit one CU:
 //   * a workgroup (4 waves, one per SIMD) works on ONE net: actor and critic share nothing but the input rows and the
@@ -25,6 +25,7 @@
 
 #pragma clang fp contract(fast)
 #include "mlp_wide.h"
+#include "mlp_tail.h"
 
 using namespace aurppo_mlp;
 
@@ -615,22 +616,6 @@ extern "C" int aurppo_k7w_kernel(int hidden, int state_dim) {
     return aurppo_knobs().k7w_variant == 3 ? 3 : 2;
 }
 
-namespace {
-struct WideTail {   // the optimizer half of aurppo_mlp_wide_ppo_minibatch_f32
-    float* params_rw;
-    float* exp_avg;
-    float* exp_avg_sq;
-    double max_norm;
-    const float* lr_dev;
-    float* step_dev;
-    double beta1, beta2, eps;
-    float* out_norm;
-    const int32_t* next_idx;   // the slice stepped next: its statistics (and the refreshed operand copies) are left by this call
-    int next_M;
-    int chained;               // the previous call named this idx as its next_idx: no prepare pass
-};
-}  // namespace
-
 // The prepare pass: the operand copies the kernel behind it streams (bf3k: k_mlpw3_step's bf16 planes), and in front of them sb
 // workgroups of advantage partial sums (0: K8w, which needs neither them nor the counters)
 static int wide_prep(bool bf3k, const WideArgs& a, int num_layers, int M, int sb, const WideWs& wv, hipStream_t s) {
@@ -653,15 +638,11 @@ static int launch_mlpw_step(const WideArgs& a, int num_layers, bool dual, int gr
 static int wide_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
                           int continuous, int hidden, int num_layers, const float* params, const int* layout_h, int n_params,
                           float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
-                          float* out_scalars, void* workspace, void* stream, void* ev_begin, void* ev_end, const WideTail* tail,
+                          float* out_scalars, void* workspace, void* stream, void* ev_begin, void* ev_end, const MlpTail* tail,
                           const char* who) {
-    AURPPO_REQUIRE(obs && rec && idx && params && layout_h && grads && out_scalars && workspace, AURPPO_EINVAL, "%s: null pointer", who);
-    AURPPO_REQUIRE(actions || (continuous ? A : 1) <= 12, AURPPO_ESHAPE,
-                   "%s: packed records hold at most 12 action floats (action_dim=%d)", who, A);
-    int rc = check_shape(D, A, continuous, hidden, num_layers, who);
+    int rc = check_step_args(who, obs && rec && idx && params && layout_h && grads && out_scalars && workspace, actions, continuous, A, M,
+                             n_params, vloss_mode, [&] { return check_shape(D, A, continuous, hidden, num_layers, who); });
     if (rc != AURPPO_OK) return rc;
-    AURPPO_REQUIRE(M > 0 && n_params > 0, AURPPO_ESHAPE, "%s: M=%d n_params=%d", who, M, n_params);
-    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: bad vloss_mode %d", who, vloss_mode);
     AURPPO_REQUIRE(aligned_to(workspace, 64) && aligned_to(rec, 16), AURPPO_EINVAL, "%s: workspace not 64-byte / rec not 16-byte aligned", who);
     WideArgs a;
     rc = wide_args(a, obs, params, D, A, continuous, hidden, num_layers, layout_h, n_params, who);
@@ -673,8 +654,7 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
     a.stats = wv.stats; a.loss_part = wv.loss_part; a.wop = wv.wop; a.slabs = wv.slabs; a.tile_counter = wv.tile_counter;
     a.wop3 = wv.wop3;
     hipStream_t s = (hipStream_t)stream;
-    int sb = (M + 1023) / 1024;
-    if (sb > kStatBlocks) sb = kStatBlocks;
+    const int sb = stat_blocks_for(M);
     a.n_stat_blocks = sb;
     // layers and state at most two 32-column blocks wide: one workgroup carries both nets (k_mlpw_step<., true>, fp32 MFMA);
     // anything wider: one net per workgroup on the bf16 pipe (k_mlpw3_step; AURPPO_K7W_VARIANT=2 keeps the fp32-MFMA k_mlpw_step)
@@ -690,8 +670,7 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
     const int n_tiles = (M + R - 1) / R;
     // 8 CUs left to the side stream's shuffle kernels, as K7; a both-net workgroup is built to share its CU with a second one
     a.static_tiles = knobs.static_tiles ? 1 : 0;
-    const int spare = knobs.k7_spare_cus >= 0 ? knobs.k7_spare_cus : 8;
-    int pairs = dual ? 2 * (cus - spare) : (cus - spare) / 2;
+    int pairs = dual ? 2 * (cus - spare_cus()) : (cus - spare_cus()) / 2;
     if (pairs > (dual ? kMaxSlabs : kMaxGrid / 2)) pairs = dual ? kMaxSlabs : kMaxGrid / 2;
     if (pairs > n_tiles) pairs = n_tiles;
     if (pairs < 1) pairs = 1;
@@ -700,20 +679,19 @@ static int wide_step_impl(const float* obs, const float* actions, const float* r
     rc = bf3k ? launch_mlpw3_step(a, num_layers, grid, s) : launch_mlpw_step(a, num_layers, dual, grid, s);
     if (rc != AURPPO_OK) return rc;
     if (ev_end) AURPPO_HIP_TRY(hipEventRecord((hipEvent_t)ev_end, s));
-    if (!tail) return launch_mlp_reduce(wv.slabs, wv.loss_part, pairs, n_params, a.h, grads, out_scalars, s);
-    // (the reduce clears the tile counters for the launch that follows: the next chained call has no prepare pass to do it)
-    double* const bc = reinterpret_cast<double*>(wv.tile_counter + 8);     // Adam's bias corrections, reduce -> optimizer launch
-    rc = launch_mlp_reduce(wv.slabs, wv.loss_part, pairs, n_params, a.h, grads, out_scalars, s, wv.sq_part, tail->step_dev,
-                           wv.tile_counter, tail->beta1, tail->beta2, bc);
-    if (rc != AURPPO_OK) return rc;
+    // (with a tail the reduce clears the tile counters for the launch that follows: the next chained call has no prepare pass to do it)
+    TailWork w = {};
+    w.slabs = wv.slabs; w.slab_strided = false; w.loss_part = wv.loss_part; w.n_slabs = pairs; w.n_params = n_params; w.h = a.h;
+    w.grads = grads; w.out_scalars = out_scalars; w.sq_part = wv.sq_part; w.counters = wv.tile_counter;
+    w.rec = a.rec; w.rec_stride = a.rec_stride; w.stats = wv.stats;
     WideCopies wc;
     for (int n = 0; n < 2; ++n)
         for (int l = 0; l < MAXL; ++l) wc.w[n][l] = l < num_layers ? a.L.w[n][l] : n_params;
     wc.NL = num_layers; wc.Hd = hidden; wc.D = D; wc.wop = wv.wop;
     wc.wop3 = bf3k ? wv.wop3 : nullptr;
-    return launch_adam_tail(tail->params_rw, grads, tail->exp_avg, tail->exp_avg_sq, n_params, wv.sq_part, tail->max_norm,
-                            tail->lr_dev, tail->step_dev, tail->beta1, tail->beta2, tail->eps, tail->out_norm, s,
-                            tail->next_idx ? &wc : nullptr, a.rec, a.rec_stride, tail->next_idx, tail->next_M, wv.stats, bc);
+    // no K7 operand copies (offsets past the bucket); K7w's if a next slice is named
+    w.copies = operand_copies(n_params, nullptr, 1, nullptr, nullptr, tail && tail->next_idx ? &wc : nullptr);
+    return launch_mlp_tail(w, tail, s);
 }
 
 extern "C" int aurppo_mlp_wide_ppo_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M,
@@ -736,10 +714,10 @@ extern "C" int aurppo_mlp_wide_ppo_minibatch_f32(const float* obs, const float* 
     AURPPO_REQUIRE(exp_avg && exp_avg_sq && lr_dev && step_dev && out_norm, AURPPO_EINVAL,
                    "aurppo_mlp_wide_ppo_minibatch_f32: null optimizer pointer");
     AURPPO_REQUIRE(!next_idx || next_M > 0, AURPPO_ESHAPE, "aurppo_mlp_wide_ppo_minibatch_f32: next_M=%d", next_M);
-    WideTail t;
+    MlpTail t;
     t.params_rw = params; t.exp_avg = exp_avg; t.exp_avg_sq = exp_avg_sq; t.max_norm = max_norm; t.lr_dev = lr_dev;
     t.step_dev = step_dev; t.beta1 = beta1; t.beta2 = beta2; t.eps = eps; t.out_norm = out_norm;
-    t.next_idx = next_idx; t.next_M = next_idx ? next_M : 0; t.chained = chained ? 1 : 0;
+    t.next_idx = next_idx; t.next_M = next_idx ? next_M : 0; t.chained = chained ? 1 : 0; t.grad_only = 0;
     return wide_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, layout_h, n_params, grads, clip,
                           ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, nullptr, nullptr, &t,
                           "aurppo_mlp_wide_ppo_minibatch_f32");

@@ -3,7 +3,8 @@ the head kernels (K13, K14) and the layered rollout step?
     AURPPO_LIB=<build> python tools/build_bitdiff.py run OUT.npz     (once per build, each in a process of its own)
     python tools/build_bitdiff.py cmp A.npz B.npz                    (raw bytes of every array; exit 1 + the first that differs)
 `run` drives every build of the step (K7 ids 3, 2; K7w ids 1, 3, 2) with AURPPO_STATIC_TILES=1 (a fixed summation order; the
-counter-dealt order is not reproducible by construction) over the smallest shapes that reach every path, at M = 1, 65 and 70001, and
+counter-dealt order is not reproducible by construction) over the smallest shapes that reach every path, at M = 1, 65, 1071 (17 slabs
+for K7, 34 for the 64-wide K7w shapes: neither one, two nor the full grid) and 70001, and
 stores gradient, scalars and the whole workspace after mlp_ppo_step; parameters, moments, norms, step count and workspace after two
 chained mlp_ppo_minibatch calls (the first names next_idx) and after mlp_ppo_grad + mlp_ppo_apply (K7); the mlp_act outputs.  The
 workspace is zero-filled before each sequence, so that bytes no kernel writes are equal across processes.
@@ -21,7 +22,7 @@ K7_SHAPES = [(2, 64, 64, 6, True, False), (2, 64, 17, 3, True, False), (2, 64, 6
 # 2 x 96 over 100: the <., 6, 8> build; 3 x 128 Categorical: the three-layer builds' other head)
 K7W_SHAPES = [(1, 64, 64, 6, True, False), (3, 64, 64, 6, True, False), (3, 128, 64, 6, True, False), (2, 128, 128, 16, True, False),
               (1, 96, 64, 4, False, False), (2, 100, 17, 4, True, False), (2, 96, 100, 6, True, False), (3, 128, 64, 5, False, False)]
-MS, B = (1, 65, 70001), 71000
+MS, B = (1, 65, 1071, 70001), 71000
 HEAD_HS, HEAD_KINDS, HEAD_NS, HEAD_B = (32, 96, 256, 512, 1024), ((1, True), (16, True), (2, False), (16, False)), (1, 65, 4099), 4200
 # (layers, hidden, D): widths no fused kernel takes, or (32, 96) a state no fused kernel takes
 LAYERED_SHAPES = [(2, 32, 144), (1, 96, 144), (2, 256, 16), (1, 512, 16), (1, 1024, 16)]

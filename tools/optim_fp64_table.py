@@ -1,6 +1,7 @@
 """Run the case lists of tests/test_optim_fp64_gpu.py once and print, per entry point, case and quantity, the metric against the fp64
 clip + Adam of tests/ref64_optim.py, the yardstick Y (torch's clip_grad_norm_ + single-tensor Adam in fp32 on the GPU, same metric) and
-their ratio.  DESIGN 2.2 quotes this table (profiles/optim_fp64_table.txt).
+their ratio.  DESIGN 2.2 quotes this table (profiles/optim_fp64_table.txt).  The kernels judged: clip.hip (K6, K6b) and mlp_tail.hip (the
+reduce kernels and k_adam_chain behind mlp_ppo_minibatch / mlp_ppo_apply).
 
     python tools/optim_fp64_table.py          AURPPO_LIB=<other build of the library> to judge that build instead
 Exit status 1 if any ratio exceeds its margin (tests/ref64_optim.py)."""
@@ -68,7 +69,7 @@ for pol in R.APPLY_POLICIES:
         n_part = p2p if isinstance(parts, str) else parts
         got, _, _ = R.run_apply(case, lay, parts=R.host_sq_parts(case["g"], n_part, sparse=parts == "p2p-sparse"))
         row(f"apply_parts[{parts}]", case, got)
-print("== mlp_ppo_minibatch: the chained tail (k_mlp_reduce_x4 / k_mlp_reduce<1,2> -> k_adam_chain), static tiles")
+print("== mlp_ppo_minibatch: the chained tail (mlp_tail.hip: k_mlp_reduce_x4 / k_mlp_reduce<1,2> -> k_adam_chain), static tiles")
 for c, k in T._TAIL:
     for t0, lr in T._TAIL_T:
         for label, case, got in T.tail_runs(c, k, t0, lr, setenv):
