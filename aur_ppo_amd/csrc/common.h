@@ -82,10 +82,31 @@ struct LinOps {
     const float* bias;               // (N,) or nullptr
     float* y;                        // (M, N)
 };
-int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream);
-// K13 / K14's shape rule and K14 on checked operands (head.hip), for the layered steps
+int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream,
+                          int n_bias = 0);
+// The layered steps at a hidden width `hidden` that is no multiple of 32 run as the policy of width Hp = layered_padded(hidden) whose
+// extra weights and biases are zero (layered.hip says why that is exact).  Where the padded shape meets the unpadded bucket:
+//   linear_prep_pad (conv.hip): the operand copy of a Kg x Ng product from a smaller (N_w, K_w) weight, zero planes outside it.
+//   n_bias (aurppo_linear_forward; 0: N): the bias has n_bias floats and the columns from there on add 0 -- bias[n_bias ...] is the
+//     bucket's next parameter.
+//   linear_product / linear_wgrad_product (linear.hip): the products behind aurppo_linear_*_f32 with the product's own dimensions
+//     apart from the weight's -- Kg x Ng where the weight is (N_w, K_w) and the bias N_w floats, and (N, K) planes whose (Nr, Kr)
+//     corner is the bucket's dw (db: the Nr bias gradients).  Equal dimensions: the entries' own path.
+//   head_ppo_run / head_act_launch (head.hip): K13 / K14 on (rows, H) planes with head rows of Hr <= H floats in the bucket.
+inline int layered_padded(int hidden) { return (hidden + 31) / 32 * 32; }
+int linear_prep_pad(const float* w, int K_w, int N_w, int mode, int Kg, int Ng, unsigned short* wop, hipStream_t s);
+int linear_product(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode, int Kg,
+                   int Ng, void* wop_ws, void* stream, const int32_t* rows, const float* h);
+int linear_wgrad_product(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N, int K, int Nr, int Kr,
+                         void* ws, void* stream);
+int fold_slices_pad_launch(const float* part, int S, int Np, int Kp, int Nr, int Kr, float* out, const double* bpart, float* db, hipStream_t s);
+// K13 / K14's shape rule (H a multiple of 32) and the two kernels on checked operands (head.hip), for the layered steps
 bool head_shape_ok(int H, int A, int continuous);
-int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,
+int head_ppo_run(const char* who, const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                 const int32_t* idx, int M, int H, int Hr, int A, int continuous, const float* params, const int* layout_h, int n_params,
+                 float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace,
+                 void* stream);
+int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int Hr, int A, int continuous, const float* params,
                     const int* lay, float* actions, float* logp, float* value, hipStream_t s);
 // The kernels conv.hip and linear.hip both run live in conv.hip: linear_prep above (k_conv_prep / k_linear_prep_tail), the fold of a
 // weight gradient's S slices (db != nullptr: k_fold_slices_bias, with the column sums bpart (S, N) -> db), and the slice count.

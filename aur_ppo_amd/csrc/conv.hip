@@ -100,6 +100,33 @@ __global__ __launch_bounds__(256) void k_linear_prep_tail(const float* __restric
     conv_prep_body<true>(w, N_w, K_w, k_gemm, N_w, 0, wop, 1);
 }
 
+// k_linear_prep_pad: the operand copy of a linear product that runs wider than its weight -- the layered steps at a hidden width
+// that is no multiple of 32 (layered.hip), whose products from layer 1 on run at Hp = the width rounded up.  The product is
+// k_gemm (whole k-steps) x n_gemm; the weight is (N_w, K_w) and ends where it ends -- behind the bucket's last matrix there is nothing
+// -- so an element is read only where BOTH its indices lie inside the weight, and every other one is a zero plane: mode 0 the
+// columns n >= N_w and the k-rows >= K_w, mode 1 (B[k = n_w][n = k_w]) the k-rows >= N_w and the columns >= K_w.
+__global__ __launch_bounds__(256) void k_linear_prep_pad(const float* __restrict__ w, int N_w, int K_w, int mode, int k_gemm, int n_gemm,
+                                                         unsigned short* __restrict__ wop) {
+    const int KS = k_gemm >> 4, NBLK = (n_gemm + 31) >> 5;
+    const long long total = (long long)NBLK * KS * 64 * 8;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int j = (int)(e & 7), lane = (int)((e >> 3) & 63);
+        const long long r = e >> 9;
+        const int ks = (int)(r % KS), nblk = (int)(r / KS);
+        const int n = nblk * 32 + (lane & 31), k = ks * 16 + 8 * (lane >> 5) + j;
+        float v = 0.0f;
+        if (mode == 0) {
+            if (n < N_w && k < K_w) v = w[(size_t)n * K_w + k];
+        } else if (k < N_w && n < K_w) v = w[(size_t)k * K_w + n];
+        unsigned p0, p1, p2;
+        split3(v, 0.0f, p0, p1, p2);
+        const size_t at = (((size_t)(nblk * KS + ks) * 3) * 64 + lane) * 8 + j;
+        wop[at] = (unsigned short)p0;
+        wop[at + 512] = (unsigned short)p1;
+        wop[at + 1024] = (unsigned short)p2;
+    }
+}
+
 // Workgroup = 4 waves x (2 x 32 pixels) = 256 consecutive output pixels x NB 32-channel blocks.  The filter's fragments of two
 // k-steps at a time (kKC x NB x 3 KB) are brought into LDS ONCE per workgroup by LDS-DMA, double-buffered, one barrier per chunk;
 // every wave reads its B fragments from there (with each wave fetching its own from L2, the CU's L2 path -- about 16 B per
@@ -438,6 +465,28 @@ __global__ __launch_bounds__(256) void k_fold_slices_bias(const float* __restric
     out[i] = fold_slices_at(part, S, n, i);
 }
 
+// The fold of a weight gradient that ran on padded planes (the layered steps at a hidden width that is no multiple of 32): the slices
+// are (Np, Kp) -- n_p floats apart -- and out is the bucket's (Nr, Kr) matrix at its own row stride, so thread i = (r, c) of Nr x Kr
+// sums element r * Kp + c of every slice, in k_fold_slices' order, and nothing is written for a pad row or column.  The workgroups
+// past the last of the fold add the BIAS builds' bpart (S, Np) for the Nr real columns only (launched where db != nullptr).
+__global__ __launch_bounds__(256) void k_fold_slices_pad(const float* __restrict__ part, int S, long long n_p, int Kp, int Nr, int Kr,
+                                                         float* __restrict__ out, const double* __restrict__ bpart, int Np,
+                                                         float* __restrict__ db) {
+    const long long n = (long long)Nr * Kr, n_fold = (n + 255) / 256;
+    if ((long long)blockIdx.x >= n_fold) {
+        const long long j = ((long long)blockIdx.x - n_fold) * 256 + threadIdx.x;
+        if (j >= Nr) return;
+        double t = 0.0;
+        for (int sl = 0; sl < S; ++sl) t += bpart[(size_t)sl * Np + j];
+        db[j] = (float)t;
+        return;
+    }
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long r = i / Kr;
+    out[i] = fold_slices_at(part, S, n_p, r * Kp + (i - r * Kr));
+}
+
 // The host side of K11's four forward entries (first_block_fwd of pool.hip is the model): every refusal under the entry's name `who`, then
 // the argument block, the grid and the build, the filter's operand copy (k_conv_prep of the (Co_w, Ci_w, 3, 3) filter, transposed and
 // flipped for an input gradient) and the product -- every refusal before the first launch.  cin / cout / p are the product's own (the
@@ -527,6 +576,21 @@ int linear_prep(const float* w, int K_w, int N_w, int mode, unsigned short* wop,
     }
     hipLaunchKernelGGL(k_conv_prep, dim3(64), dim3(256), 0, s, w, N_w, K_w, K, N, mode, wop, 1);
     AURPPO_LAUNCH_CHECK("k_conv_prep");
+    return AURPPO_OK;
+}
+// the same copy for a product of Kg x Ng that is wider than its weight (k_linear_prep_pad; Kg may be ragged as above: the product runs
+// on the tail builds, and the copy has whole k-steps)
+int linear_prep_pad(const float* w, int K_w, int N_w, int mode, int Kg, int Ng, unsigned short* wop, hipStream_t s) {
+    hipLaunchKernelGGL(k_linear_prep_pad, dim3(64), dim3(256), 0, s, w, N_w, K_w, mode, (Kg + 15) / 16 * 16, Ng, wop);
+    AURPPO_LAUNCH_CHECK("k_linear_prep_pad");
+    return AURPPO_OK;
+}
+// the fold of (S, Np, Kp) slices into the (Nr, Kr) matrix `out` (k_fold_slices_pad; db != nullptr: the Nr bias gradients too)
+int fold_slices_pad_launch(const float* part, int S, int Np, int Kp, int Nr, int Kr, float* out, const double* bpart, float* db, hipStream_t s) {
+    const long long n_fold = ((long long)Nr * Kr + 255) / 256;
+    hipLaunchKernelGGL(k_fold_slices_pad, dim3((unsigned)(n_fold + (db ? (Nr + 255) / 256 : 0))), dim3(256), 0, s, part, S, (long long)Np * Kp, Kp,
+                       Nr, Kr, out, bpart, Np, db);
+    AURPPO_LAUNCH_CHECK("k_fold_slices_pad");
     return AURPPO_OK;
 }
 int fold_slices_launch(const float* part, int S, long long n, float* out, const double* bpart, int N, float* db, hipStream_t s) {

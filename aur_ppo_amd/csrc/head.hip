@@ -48,6 +48,8 @@ struct HeadArgs {
     double* loss_part;               // (grid, 8)
     int slab_stride;
     int M, H, A, continuous, n_iter;
+    int Hr;                          // floats of a head row in the bucket: H, or fewer (the layered steps at a hidden width that is no
+                                     // multiple of 32: H is the width rounded up, the activations' columns >= Hr are zeros)
     PpoHyper h;
 };
 
@@ -111,7 +113,14 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = a.H, A = a.A;
     head_fold_stats(a.stats, a.n_stat, a.h.M, s_dred, s_ms);
-    for (int e = tid; e < (A + 1) * H; e += kHT) sW[e] = e < A * H ? a.params[a.off_wa + e] : a.params[a.off_wc + (e - A * H)];
+    if (a.Hr == H) {
+        for (int e = tid; e < (A + 1) * H; e += kHT) sW[e] = e < A * H ? a.params[a.off_wa + e] : a.params[a.off_wc + (e - A * H)];
+    } else {                                           // head rows of Hr floats: zero columns from Hr on, and no read behind a row's end
+        for (int k = 0; k <= A; ++k) {
+            const float* const src = k < A ? a.params + a.off_wa + (size_t)k * a.Hr : a.params + a.off_wc;
+            for (int c = tid; c < H; c += kHT) sW[k * H + c] = c < a.Hr ? src[c] : 0.0f;
+        }
+    }
     if (tid < 16) {
         s_small[tid] = tid < A ? a.params[a.off_ba + tid] : 0.0f;
         const float ls = (a.continuous && tid < A) ? a.params[a.off_ls + tid] : 0.0f;
@@ -409,7 +418,10 @@ __global__ __launch_bounds__(kHT) void k_head_fold(const HeadArgs a, int n_slabs
 #pragma unroll
     for (int q = 0; q < 8; ++q) total += s_run[q][el];
     int dst = -1;
-    if (e < A * H) dst = a.off_wa + e;
+    if (e < (A + 3) * H && a.Hr != H) {                // slab rows of H floats, bucket rows of Hr: the real columns at the bucket's stride
+        const int k = e / H, c = e - k * H;
+        if (c < a.Hr) dst = (k < A ? a.off_wa + k * a.Hr : k == A ? a.off_wc : k == A + 1 ? a.off_bla : a.off_blc) + c;
+    } else if (e < A * H) dst = a.off_wa + e;
     else if (e < (A + 1) * H) dst = a.off_wc + (e - A * H);
     else if (e < (A + 2) * H) dst = a.off_bla + (e - (A + 1) * H);
     else if (e < (A + 3) * H) dst = a.off_blc + (e - (A + 2) * H);
@@ -471,6 +483,7 @@ struct HeadActArgs {
     float* value;                    // (N,)
     int off_wa, off_ba, off_wc, off_bc, off_ls;
     int N, H, A, continuous, n_iter;
+    int Hr;                          // floats of a head row in the bucket (HeadArgs::Hr)
 };
 
 template <int TPR>
@@ -484,9 +497,16 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = a.H, A = a.A;
     const int nA = a.noise ? A : 0;                    // actor outputs to form: none for the value alone
-    for (int e = tid; e < (A + 1) * H; e += kHT) {
-        if (e >= A * H) sW[e] = a.params[a.off_wc + (e - A * H)];
-        else if (nA) sW[e] = a.params[a.off_wa + e];
+    if (a.Hr == H) {
+        for (int e = tid; e < (A + 1) * H; e += kHT) {
+            if (e >= A * H) sW[e] = a.params[a.off_wc + (e - A * H)];
+            else if (nA) sW[e] = a.params[a.off_wa + e];
+        }
+    } else {                                           // head rows of Hr floats: zero columns from Hr on, and no read behind a row's end
+        for (int k = nA ? 0 : A; k <= A; ++k) {
+            const float* const src = k < A ? a.params + a.off_wa + (size_t)k * a.Hr : a.params + a.off_wc;
+            for (int c = tid; c < H; c += kHT) sW[k * H + c] = c < a.Hr ? src[c] : 0.0f;
+        }
     }
     if (tid < 16) {
         s_small[tid] = tid < nA ? a.params[a.off_ba + tid] : 0.0f;
@@ -647,13 +667,13 @@ int head_layout_check(const int* layout, const long long* need, int count, int n
 bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
 
 // K14 on checked operands; lay = {actor head w, b; critic head w, b; actor_logstd}  (this and head_shape_ok: also layered.hip's)
-int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,
+int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int Hr, int A, int continuous, const float* params,
                     const int* lay, float* actions, float* logp, float* value, hipStream_t s) {
     HeadActArgs a;
     a.hA = hA; a.hC = hC; a.noise = noise; a.params = params;
     a.actions = actions; a.logp = logp; a.value = value;
     a.off_wa = lay[0]; a.off_ba = lay[1]; a.off_wc = lay[2]; a.off_bc = lay[3]; a.off_ls = lay[4];
-    a.N = N; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0;
+    a.N = N; a.H = H; a.Hr = Hr; a.A = A; a.continuous = continuous ? 1 : 0;
     const int grid = head_act_grid(N, H);
     a.n_iter = head_n_iter(N, H, grid);
     return launch_k_head_act(a, grid, s);
@@ -664,33 +684,34 @@ extern "C" size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A) {
     return head_carve(nullptr, M, H, A).bytes;
 }
 
-extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
-                                   const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
-                                   int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
-                                   int vloss_mode, float* out_scalars, void* workspace, void* stream) {
+// K13's three launches under the entry's name `who`: (M, H) planes, head rows and last-layer biases of Hr <= H floats in the bucket
+int head_ppo_run(const char* who, const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                 const int32_t* idx, int M, int H, int Hr, int A, int continuous, const float* params, const int* layout_h, int n_params,
+                 float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace,
+                 void* stream) {
     AURPPO_REQUIRE(hA && hC && gzA && gzC && rec && idx && params && layout_h && grads && out_scalars && workspace, AURPPO_EINVAL,
-                   "aurppo_head_ppo_f32: null pointer");
-    AURPPO_REQUIRE(M > 0, AURPPO_ESHAPE, "aurppo_head_ppo_f32: M=%d", M);
-    AURPPO_REQUIRE(head_shape_ok(H, A, continuous), AURPPO_ESHAPE,
-                   "aurppo_head_ppo_f32: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", H, A);
-    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "aurppo_head_ppo_f32: vloss_mode %d", vloss_mode);
+                   "%s: null pointer", who);
+    AURPPO_REQUIRE(M > 0, AURPPO_ESHAPE, "%s: M=%d", who, M);
+    AURPPO_REQUIRE(head_shape_ok(H, A, continuous) && Hr >= 1 && Hr <= H, AURPPO_ESHAPE,
+                   "%s: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", who, H, A);
+    AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: vloss_mode %d", who, vloss_mode);
     const int aw = continuous ? A : 1;
-    AURPPO_REQUIRE(actions || aw <= 12, AURPPO_ESHAPE, "aurppo_head_ppo_f32: packed records hold at most 12 action floats (A=%d)", A);
+    AURPPO_REQUIRE(actions || aw <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (A=%d)", who, A);
     AURPPO_REQUIRE(aligned_to(hA, 16) && aligned_to(hC, 16) && aligned_to(gzA, 16) && aligned_to(gzC, 16) && aligned_to(rec, 16) &&
                        aligned_to(workspace, 64),
-                   AURPPO_EINVAL, "aurppo_head_ppo_f32: operands not 16-byte / workspace not 64-byte aligned");
+                   AURPPO_EINVAL, "%s: operands not 16-byte / workspace not 64-byte aligned", who);
     HeadArgs a;
     a.off_wa = layout_h[0]; a.off_ba = layout_h[1]; a.off_wc = layout_h[2]; a.off_bc = layout_h[3]; a.off_ls = layout_h[4];
     a.off_bla = layout_h[5]; a.off_blc = layout_h[6];
-    const long long need[7] = {(long long)A * H, A, H, 1, continuous ? A : 0, H, H};
-    if (const int rc = head_layout_check(layout_h, need, 7, n_params, "aurppo_head_ppo_f32")) return rc;
+    const long long need[7] = {(long long)A * Hr, A, Hr, 1, continuous ? A : 0, Hr, Hr};
+    if (const int rc = head_layout_check(layout_h, need, 7, n_params, who)) return rc;
     const HeadWs w = head_carve(workspace, M, H, A);
     a.hA = hA; a.hC = hC; a.gzA = gzA; a.gzC = gzC;
     a.actions = actions; a.rec = reinterpret_cast<const float4*>(rec); a.rec_stride = actions ? 1 : 4; a.aw = aw;
     a.idx = idx; a.params = params;
     a.stats = w.stats; a.slabs = w.slabs; a.loss_part = w.loss_part;
     a.slab_stride = head_slab_stride(H, A);
-    a.M = M; a.H = H; a.A = A; a.continuous = continuous ? 1 : 0;
+    a.M = M; a.H = H; a.Hr = Hr; a.A = A; a.continuous = continuous ? 1 : 0;
     a.h = make_hyper(M, clip, ent_coef, vf_coef, norm_adv, vloss_mode);
     const int grid = head_grid(M, H);
     a.n_iter = head_n_iter(M, H, grid);
@@ -707,6 +728,14 @@ extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA,
     return AURPPO_OK;
 }
 
+extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                                   const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
+                                   int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                   int vloss_mode, float* out_scalars, void* workspace, void* stream) {
+    return head_ppo_run("aurppo_head_ppo_f32", hA, hC, gzA, gzC, actions, rec, idx, M, H, H, A, continuous, params, layout_h, n_params, grads,
+                        clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream);
+}
+
 // K14 alone: layout_h = {actor head w, b; critic head w, b; actor_logstd}.
 extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
                                    const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
@@ -721,5 +750,5 @@ extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float
                    AURPPO_EINVAL, "aurppo_head_act_f32: noise / outputs not 4-byte aligned");
     const long long need[5] = {(long long)A * H, A, H, 1, continuous ? A : 0};
     if (const int rc = head_layout_check(layout_h, need, 5, n_params, "aurppo_head_act_f32")) return rc;
-    return head_act_launch(hA, hC, noise, N, H, A, continuous, params, layout_h, actions, logp, value, (hipStream_t)stream);
+    return head_act_launch(hA, hC, noise, N, H, H, A, continuous, params, layout_h, actions, logp, value, (hipStream_t)stream);
 }

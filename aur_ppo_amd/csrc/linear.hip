@@ -18,13 +18,14 @@ struct LinArgs {
     const float* x;                  // (M, K)
     const unsigned short* wop;       // [n-block][k-step][plane][lane][8]
     float* y;                        // (M, N)
-    const float* bias;               // (N,) or nullptr
+    const float* bias;               // (n_bias,) or nullptr
     long long M;
     int K, N, n_mb;
     int act;                         // 0: none, 1: tanh (1 - 2 / (e^{2x} + 1), as the fused MLP steps form it)
                                      // 2 (GATE builds): y = acc * (1 - h * h), tanh' of the layer below from its output h
     const int32_t* rows;             // ROWS builds: (M,) lane row m reads x row rows[m] (the minibatch index); y stays in minibatch order
     const float* h;                  // GATE builds: (M, N), read at the address the store uses
+    int n_bias;                      // N, or fewer: the columns from n_bias on add 0 (a product that runs wider than its layer, common.h)
 };
 
 // ROWS (layer 0 of the layered PPO step, hip_ops.mlp_layered_step: x through the minibatch index) and GATE (its input gradients:
@@ -69,9 +70,9 @@ struct LinPairArgs {
     const float* x[2];               // (M, K) each
     const unsigned short* wop[2];    // each net's operand copy, the layout above
     float* y[2];                     // (M, N) each
-    const float* bias[2];            // (N,) or nullptr
+    const float* bias[2];            // (n_bias,) or nullptr
     long long M;
-    int K, N, n_mb, act;
+    int K, N, n_mb, n_bias, act;
     unsigned per_net;                // workgroups of one net's product
 };
 template <int NB>
@@ -94,7 +95,7 @@ __device__ __forceinline__ LinArgs pair_net_args(const LinPairArgs& p, unsigned 
     a.wop = net ? p.wop[1] : p.wop[0];
     a.y = net ? p.y[1] : p.y[0];
     a.bias = net ? p.bias[1] : p.bias[0];
-    a.M = p.M; a.K = p.K; a.N = p.N; a.n_mb = p.n_mb; a.act = p.act;
+    a.M = p.M; a.K = p.K; a.N = p.N; a.n_mb = p.n_mb; a.n_bias = p.n_bias; a.act = p.act;
     a.rows = nullptr; a.h = nullptr;
     return a;
 }
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(kConvThreads, 2) void k_linear_wgrad_tail(const Wgr
 // the small-M tile with its NB from bf3_small_grid), `nets` same-shaped products in ONE launch (2: the small tile only, k_linear_pair)
 // from ops[0 .. nets).  rows, h, grad: the large tile's index, gate and input-gradient builds.
 static int linear_launch(bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, hipStream_t s,
-                         const int32_t* rows = nullptr, const float* h = nullptr, bool grad = false) {
+                         const int32_t* rows = nullptr, const float* h = nullptr, bool grad = false, int n_bias = 0) {
     const Bf3Grid gr = small ? bf3_small_grid(M, N, nets) : bf3_grid(M, N);
     const long long per_net = gr.n_mb * gr.n_ng;
     AURPPO_REQUIRE(per_net * nets < (1ll << 31), AURPPO_ESHAPE, "%s: grid too large", small ? "aurppo_linear_small_bias_act_f32" : "aurppo_linear_f32");
@@ -179,6 +180,7 @@ static int linear_launch(bool small, int nets, const LinOps* ops, int act, long 
     }
     a.x = p.x[0]; a.wop = p.wop[0]; a.y = p.y[0]; a.bias = p.bias[0]; a.rows = rows; a.h = h;
     a.M = p.M = M; a.K = p.K = K; a.N = p.N = N; a.n_mb = p.n_mb = (int)gr.n_mb; a.act = p.act = act;
+    a.n_bias = p.n_bias = n_bias > 0 && n_bias < N ? n_bias : N;
     p.per_net = (unsigned)per_net;
     const dim3 g((unsigned)(per_net * nets)), blk(kConvThreads);
     const bool tail = K % 16 != 0, nb2 = gr.NB == 2;
@@ -230,19 +232,28 @@ static int linear_forward_check(const char* who, const char* copy, bool others, 
 // mode 0: y (M, N_w) = x (M, K_w) . w (N_w, K_w)^T      -- nn.Linear without its bias; any K_w >= 1 (no multiple of 16: the tail builds)
 // mode 1: y (M, K_w) = x (M, N_w) . w (N_w, K_w)         -- the gradient with respect to the input (x is dY); N_w a multiple of 16
 // wop_ws: aurppo_conv3x3_wop_bytes(product's K, product's N) / 9 bytes suffice; the same function's size is accepted.
+// Kg, Ng (0: the weight's own): the product's dimensions where it runs wider than its weight (common.h) -- x, y and h are then (M, Kg)
+// and (M, Ng) planes, the copy comes from linear_prep_pad and the bias (mode 0) is added to the weight's N_w columns alone.
 static int linear_impl(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode,
-                       void* wop_ws, void* stream, const int32_t* rows = nullptr, const float* h = nullptr) {
+                       void* wop_ws, void* stream, const int32_t* rows = nullptr, const float* h = nullptr, int Kg = 0, int Ng = 0) {
     AURPPO_REQUIRE(x && w && y && wop_ws, AURPPO_EINVAL, "aurppo_linear_f32: null pointer");
     AURPPO_REQUIRE(mode == 0 || mode == 1, AURPPO_EINVAL, "aurppo_linear_f32: mode %d", mode);
-    const int K = mode == 0 ? K_w : N_w, N = mode == 0 ? N_w : K_w;
-    AURPPO_REQUIRE(M > 0 && K > 0 && N > 0 && (mode == 0 || K % 16 == 0), AURPPO_ESHAPE,
+    const int K_own = mode == 0 ? K_w : N_w, N_own = mode == 0 ? N_w : K_w;
+    const int K = Kg ? Kg : K_own, N = Ng ? Ng : N_own;
+    const bool pad = K != K_own || N != N_own;
+    AURPPO_REQUIRE(M > 0 && K_own > 0 && N_own > 0 && K >= K_own && N >= N_own && (mode == 0 || K % 16 == 0), AURPPO_ESHAPE,
                    "aurppo_linear_f32: M=%lld, inner dimension %d (mode 1: a multiple of 16), %d columns", M, K, N);
     AURPPO_REQUIRE(aligned_to(x, 16) && aligned_to(wop_ws, 16), AURPPO_EINVAL, "aurppo_linear_f32: x / workspace not 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     unsigned short* wop = reinterpret_cast<unsigned short*>(wop_ws);
-    if (const int rc = linear_prep(w, K_w, N_w, mode, wop, s)) return rc;
+    if (const int rc = pad ? linear_prep_pad(w, K_w, N_w, mode, K, N, wop, s) : linear_prep(w, K_w, N_w, mode, wop, s)) return rc;
     const LinOps ops = {x, wop, bias, y};
-    return linear_launch(false, 1, &ops, act, M, K, N, s, rows, h, mode == 1);
+    return linear_launch(false, 1, &ops, act, M, K, N, s, rows, h, mode == 1, N_own);
+}
+int linear_product(const float* x, const float* w, const float* bias, int act, float* y, long long M, int K_w, int N_w, int mode, int Kg,
+                   int Ng, void* wop_ws, void* stream, const int32_t* rows, const float* h) {
+    AURPPO_REQUIRE(act == (h ? 2 : 1) && (h != nullptr) == (mode == 1), AURPPO_EINVAL, "aurppo_linear_f32: act %d in mode %d", act, mode);
+    return linear_impl(x, w, bias, act, y, M, K_w, N_w, mode, wop_ws, stream, rows, h, Kg, Ng);
 }
 
 extern "C" int aurppo_linear_f32(const float* x, const float* w, float* y, long long M, int K_w, int N_w, int mode, void* wop_ws,
@@ -279,9 +290,10 @@ size_t aurppo_linear_wop_bytes(int K, int N) { return (size_t)((N + 31) / 32 + k
 
 // y (M, N) = act(x (M, K) . B + bias) for each of ops[0 .. nets), from the operand copies of (N, K) weights: the forward products without
 // their k_conv_prep launch, on the large tile or the small one (common.h)
-int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream) {
+int aurppo_linear_forward(const char* who, bool small, int nets, const LinOps* ops, int act, long long M, int K, int N, void* stream,
+                          int n_bias) {
     if (const int rc = linear_forward_check(who, "operand copy", true, small, nets, ops, act, M, K, N)) return rc;
-    return linear_launch(small, nets, ops, act, M, K, N, (hipStream_t)stream);
+    return linear_launch(small, nets, ops, act, M, K, N, (hipStream_t)stream, nullptr, nullptr, false, n_bias);
 }
 
 // aurppo_linear_bias_act_f32 on the small tile, whatever M: same argument list, same checks, same bits
@@ -326,10 +338,14 @@ extern "C" size_t aurppo_linear_wgrad_ws_bytes(long long M, int N, int K) {
 // bytes of the (S, N, K) partial products, rounded to where the BIAS builds' (S, N) fp64 partial column sums begin
 static size_t linear_wgrad_part_bytes(int S, int N, int K) { return ((size_t)S * (size_t)N * (size_t)K * sizeof(float) + 15) & ~(size_t)15; }
 // The weight-gradient launches; db != nullptr: the BIAS builds and their fold (rows or K a multiple of 4: no plain BIAS tail build)
+// Nr, Kr (0: N, K): dw is the (Nr, Kr) corner of the product, which ran on padded planes (common.h) -- the fold writes that corner alone
 static int linear_wgrad_impl(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N, int K,
-                             void* ws, void* stream) {
+                             void* ws, void* stream, int Nr = 0, int Kr = 0) {
     AURPPO_REQUIRE(dy && x && dw && ws, AURPPO_EINVAL, "aurppo_linear_wgrad_f32: null pointer");
     AURPPO_REQUIRE(M > 0 && N > 0 && K > 0 && N % 4 == 0, AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: M=%lld N=%d (a multiple of 4) K=%d", M, N, K);
+    if (!Nr) Nr = N;
+    if (!Kr) Kr = K;
+    AURPPO_REQUIRE(Nr > 0 && Nr <= N && Kr > 0 && Kr <= K, AURPPO_ESHAPE, "aurppo_linear_wgrad_f32: a %d x %d gradient out of %d x %d", Nr, Kr, N, K);
     AURPPO_REQUIRE(aligned_to(dy, 16) && aligned_to(x, 16) && aligned_to(ws, 16), AURPPO_EINVAL,
                    "aurppo_linear_wgrad_f32: operands / workspace not 16-byte aligned");
     const int S0 = linear_wgrad_slices(M, N, K);
@@ -355,7 +371,13 @@ static int linear_wgrad_impl(const float* dy, const float* x, const int32_t* row
     else if (rows) hipLaunchKernelGGL(k_linear_wgrad<true>, g, blk, 0, st, a);
     else hipLaunchKernelGGL(k_linear_wgrad<false>, g, blk, 0, st, a);
     AURPPO_LAUNCH_CHECK("k_linear_wgrad");
+    if (Nr != N || Kr != K) return fold_slices_pad_launch(a.part, (int)S, N, K, Nr, Kr, dw, a.bpart, db, st);
     return fold_slices_launch(a.part, (int)S, (long long)N * K, dw, a.bpart, N, db, st);
+}
+int linear_wgrad_product(const float* dy, const float* x, const int32_t* rows, float* dw, float* db, long long M, int N, int K, int Nr, int Kr,
+                         void* ws, void* stream) {
+    AURPPO_REQUIRE(!db || (aligned_to(db, 4) && (rows || K % 4 == 0)), AURPPO_EINVAL, "aurppo_linear_wgrad_bias_f32: db not 4-byte aligned / K=%d", K);
+    return linear_wgrad_impl(dy, x, rows, dw, db, M, N, K, ws, stream, Nr, Kr);
 }
 // dw (N, K) = dy (M, N)^T . x (M, K): nn.Linear's weight gradient (row-major fp32; N a multiple of 4, any K >= 1 -- no multiple of 4:
 // the tail builds; 16-byte aligned operands)

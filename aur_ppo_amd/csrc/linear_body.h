@@ -130,7 +130,7 @@
         for (int nb = 0; nb < NB; ++nb) {
             const int col = (ng * NB + nb) * 32 + (lane & 31);
             if (col < a.N) {
-                const float bv = a.bias ? a.bias[col] : 0.0f;
+                const float bv = a.bias && col < a.n_bias ? a.bias[col] : 0.0f;      // (n_bias < N: the columns behind the layer's own add 0)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const long long r = m0[mb] + acc_row_c(e, lane);

@@ -341,21 +341,46 @@ def mlp_layout(policy, bucket):
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, wide=not fast)
 
 
-def mlp_layered_layout(policy, bucket, any_state=False):
+def mlp_layered_layout(policy, bucket, any_state=False, any_hidden=False):
     """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
     kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, at most 16 actions,
     and a state of a multiple of 16 floats -- or, with ``any_state=True``, of any width (Hopper's 11, HalfCheetah's 17, Humanoid's
     376: layer 0's three products then run on the tail builds of k_linear / k_linear_wgrad, csrc/linear.hip).  Offsets as K7w's:
-    {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no device."""
+    {w_l, b_l} for l = 0..L per net, then actor_logstd.  Needs no device.
+    ``any_hidden=True``: any ``hidden_dim`` in 1..1024 (200, 300, 400, 500; 100 over Humanoid's state).  A width that is no multiple
+    of 32 gives the same dict -- the unpadded policy's offsets and ``n_params`` -- plus ``ragged_hidden=True``: the native calls
+    (``mlp_layered_step_native``, ``mlp_layered_minibatch``, ``mlp_layered_prepare``, ``mlp_layered_act``) then run the policy at the
+    width rounded up to 32 through the library's ``anyh`` entries (csrc/layered.hip); the per-product route refuses it."""
     if mlp_layout(policy, bucket) is not None:
         return None
     st = _mlp_structure(policy, bucket)
     if st is None:
         return None
     seq, pos, D, A, cont, NL, Hd = st
-    if Hd % 32 != 0 or Hd > MLP_LAYERED_MAX_HIDDEN or (D % 16 != 0 and not any_state):
+    if (Hd % 32 != 0 and not any_hidden) or Hd > MLP_LAYERED_MAX_HIDDEN or (D % 16 != 0 and not any_state):
         return None
-    return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, layered=True)
+    lay = dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, layered=True)
+    if Hd % 32 != 0:
+        lay["ragged_hidden"] = True
+    return lay
+
+
+def _layered_entry(lib, layout, name):
+    """(function, its name) of the layered entry ``aurppo_mlp_layered_<name>`` for ``layout``: the ``anyh`` sibling where the hidden
+    width is no multiple of 32, with the same arguments in the same order."""
+    entry = ("aurppo_mlp_layered_anyh_" if layout.get("ragged_hidden") else "aurppo_mlp_layered_") + name
+    return getattr(lib, entry), entry
+
+
+def _layered_ws_kind(kind, layout):
+    """The workspace's cache key: a ragged hidden width keeps a buffer of its own per width (200 and 224 share none)."""
+    return f"{kind}_h{layout['hidden']}" if layout.get("ragged_hidden") else kind
+
+
+def _refuse_ragged_hidden(who, layout):
+    if layout.get("ragged_hidden"):
+        raise ValueError(f"{who}: a hidden width of {layout['hidden']} (no multiple of 32) runs through mlp_layered_step_native / "
+                         f"mlp_layered_minibatch / mlp_layered_act only")
 
 
 def k7_variant():
@@ -1276,6 +1301,7 @@ def head_ppo(hA, hC, actions, rec, idx, flat_param, layout, flat_grad, clip, ent
     ``hC`` (M, H).  Writes ``gzA`` / ``gzC`` (default: in place of the activations), the heads', actor_logstd's and the last
     hidden layers' bias gradients at their bucket offsets in ``flat_grad``, and returns the 9 scalars."""
     lib = _lib_or_raise()
+    _refuse_ragged_hidden("head_ppo", layout)
     M, Hd = hA.shape
     A, n = layout["A"], layout["n_params"]
     gzA, gzC = hA if gzA is None else gzA, hC if gzC is None else gzC
@@ -1320,6 +1346,7 @@ def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip
     gradient (k_linear_wgrad, layer 0's x through the index), the input gradient with tanh' (k_linear) and the bias
     gradient (a column sum)."""
     lib = _lib_or_raise()
+    _refuse_ragged_hidden("mlp_layered_step", layout)
     M, D, Hd, L, n = idx.numel(), layout["D"], layout["hidden"], layout["num_layers"], layout["n_params"]
     if not layout.get("layered") or not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_layered_step: buffer shapes do not match the policy")
@@ -1363,10 +1390,10 @@ def _layered_native(lib, who, obs, actions, rec, idx, flat_param, layout, *bucke
         raise ValueError(f"{who}: buffer shapes do not match the policy")
     _bucket_fits(layout["n_params"], flat_param, *buckets, who=who)
     lay, shape = _layout_shape(layout, idx.numel())
-    nb = lib.aurppo_mlp_layered_step_workspace_bytes(shape[0], layout["D"], layout["A"], layout["hidden"], layout["num_layers"])
+    nb = _layered_entry(lib, layout, "step_workspace_bytes")[0](shape[0], layout["D"], layout["A"], layout["hidden"], layout["num_layers"])
     if nb == 0:
         raise RuntimeError(f"aur_ppo_amd: {who} does not take this shape")
-    return lay, shape, _workspace("layered_step", nb, obs.device)
+    return lay, shape, _workspace(_layered_ws_kind("layered_step", layout), nb, obs.device)
 
 
 def mlp_layered_step_native(obs, actions, rec, idx, flat_param, layout, flat_grad, clip, ent_coef, vf_coef, norm_adv=True,
@@ -1378,9 +1405,9 @@ def mlp_layered_step_native(obs, actions, rec, idx, flat_param, layout, flat_gra
     lay, shape, ws = _layered_native(lib, "mlp_layered_step_native", obs, actions, rec, idx, flat_param, layout, flat_grad)
     if out_scalars is None:
         out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=obs.device)
-    _check(lib.aurppo_mlp_layered_step_f32(
-        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
-                      vloss_mode, out_scalars), *_ws_stream(ws)), "aurppo_mlp_layered_step_f32")
+    fn, entry = _layered_entry(lib, layout, "step_f32")
+    _check(fn(*_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
+                            vloss_mode, out_scalars), *_ws_stream(ws)), entry)
     return out_scalars
 
 
@@ -1391,11 +1418,10 @@ def mlp_layered_minibatch(obs, actions, rec, idx, flat_param, layout, flat_grad,
     lib = _lib_or_raise()
     lay, shape, ws = _layered_native(lib, "mlp_layered_minibatch", obs, actions, rec, idx, flat_param, layout, flat_grad, exp_avg,
                                      exp_avg_sq)
-    _check(lib.aurppo_mlp_layered_minibatch_f32(
-        *_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
-                      vloss_mode, out_scalars),
-        *_adam_tail(exp_avg, exp_avg_sq, max_norm, lr_dev, step_dev, betas, eps, out_norm), *_ws_stream(ws)),
-        "aurppo_mlp_layered_minibatch_f32")
+    fn, entry = _layered_entry(lib, layout, "minibatch_f32")
+    _check(fn(*_step_prefix((obs,), actions, rec, idx, shape, flat_param, lay, layout["n_params"], flat_grad, clip, ent_coef, vf_coef, norm_adv,
+                            vloss_mode, out_scalars),
+              *_adam_tail(exp_avg, exp_avg_sq, max_norm, lr_dev, step_dev, betas, eps, out_norm), *_ws_stream(ws)), entry)
     return out_scalars
 
 
@@ -1432,6 +1458,7 @@ def head_act(hA, hC, noise, flat_param, layout, actions=None, logp=None, value=N
     """K14: both heads, the sampled action, its log-prob and the value from the last hidden activations ``hA`` / ``hC`` (N, H).
     ``noise`` as ``mlp_act``'s; None -> the value only (``hA`` may then be None).  Returns (actions, logp, value)."""
     lib = _lib_or_raise()
+    _refuse_ragged_hidden("head_act", layout)
     N, Hd = hC.shape
     if Hd != layout["hidden"] or (noise is not None and (hA is None or hA.shape != (N, Hd))):
         raise ValueError("head_act: activation shapes do not match the policy")
@@ -1454,7 +1481,7 @@ def _layered_wop(lib, layout, device):
     key = (D, Hd, L, device.index if device.index is not None else torch.cuda.current_device())
     wop = _layered_wop_cache.get(key)
     if wop is None:
-        nb = lib.aurppo_mlp_layered_wop_bytes(D, Hd, L)
+        nb = _layered_entry(lib, layout, "wop_bytes")[0](D, Hd, L)
         if nb == 0:
             raise RuntimeError("aur_ppo_amd: aurppo_mlp_layered_prep_f32 does not take this shape")
         wop = _layered_wop_cache[key] = torch.empty(nb, dtype=torch.uint8, device=device)
@@ -1471,8 +1498,9 @@ def mlp_layered_prepare(flat_param, layout):
     _bucket_fits(layout["n_params"], flat_param, who="mlp_layered_prepare")
     wop = _layered_wop(lib, layout, flat_param.device)
     lay, _ = _layout_shape(layout, 0)
-    _check(lib.aurppo_mlp_layered_prep_f32(_ptr(flat_param), lay, layout["n_params"], layout["D"], layout["hidden"], layout["num_layers"],
-                                           C.c_void_p(wop.data_ptr()), _stream()), "aurppo_mlp_layered_prep_f32")
+    fn, entry = _layered_entry(lib, layout, "prep_f32")
+    _check(fn(_ptr(flat_param), lay, layout["n_params"], layout["D"], layout["hidden"], layout["num_layers"], C.c_void_p(wop.data_ptr()),
+              _stream()), entry)
     return wop
 
 
@@ -1491,11 +1519,11 @@ def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, val
     _bucket_fits(layout["n_params"], flat_param, who="mlp_layered_act")
     if wop is None:
         wop = mlp_layered_prepare(flat_param, layout)
-    elif wop.numel() * wop.element_size() < lib.aurppo_mlp_layered_wop_bytes(layout["D"], layout["hidden"], layout["num_layers"]):
+    elif wop.numel() * wop.element_size() < _layered_entry(lib, layout, "wop_bytes")[0](layout["D"], layout["hidden"], layout["num_layers"]):
         raise ValueError("mlp_layered_act: the prepared buffer is smaller than the policy's operand copies")
     lay, shape = _layout_shape(layout, N)
-    ws = _workspace("layered_act", lib.aurppo_mlp_layered_act_workspace_bytes(N, layout["hidden"]), dev)
-    entry = "aurppo_mlp_layered_act_paired_f32" if paired else "aurppo_mlp_layered_act_f32"
-    _check(getattr(lib, entry)(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"],
-                               *_act_outputs_ptrs(noise, actions, logp, value), C.c_void_p(wop.data_ptr()), *_ws_stream(ws)), entry)
+    ws = _workspace(_layered_ws_kind("layered_act", layout), _layered_entry(lib, layout, "act_workspace_bytes")[0](N, layout["hidden"]), dev)
+    fn, entry = _layered_entry(lib, layout, "act_paired_f32" if paired else "act_f32")
+    _check(fn(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"], *_act_outputs_ptrs(noise, actions, logp, value),
+              C.c_void_p(wop.data_ptr()), *_ws_stream(ws)), entry)
     return actions, logp, value

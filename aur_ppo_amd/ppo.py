@@ -62,6 +62,15 @@ LAYERED_STEP_DEFAULT = "0"      # AURPPO_LAYERED_STEP when the environment does 
 LAYERED_ACT_DEFAULT = "0"       # AURPPO_LAYERED_ACT when the environment does not set it
 LAYERED_NATIVE_DEFAULT = "0"    # AURPPO_LAYERED_NATIVE when the environment does not set it
 LAYERED_ACT_PAIRED_DEFAULT = "0"    # AURPPO_LAYERED_ACT_PAIRED when the environment does not set it
+LAYERED_ANY_HIDDEN_DEFAULT = "0"    # AURPPO_LAYERED_ANY_HIDDEN when the environment does not set it
+
+
+def _layered_layout(ops, policy, bucket):
+    """The layered layout of ``policy``, called only where AURPPO_LAYERED_STEP / AURPPO_LAYERED_ACT is on.  AURPPO_LAYERED_ANY_HIDDEN=1
+    (opt-in, read only here): hidden widths that are no multiple of 32 too (``ragged_hidden`` layouts: the native calls only)."""
+    if os.environ.get("AURPPO_LAYERED_ANY_HIDDEN", LAYERED_ANY_HIDDEN_DEFAULT) != "0":
+        return ops.mlp_layered_layout(policy, bucket, any_state=True, any_hidden=True)
+    return ops.mlp_layered_layout(policy, bucket, any_state=True)
 
 
 def _layered_act_paired(act_layout):
@@ -159,7 +168,7 @@ class ppo(FlatAdamMixin):
         self._mlp_layered = None
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_layout")
                 and os.environ.get("AURPPO_LAYERED_STEP", LAYERED_STEP_DEFAULT) != "0"):
-            self._mlp_layered = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
+            self._mlp_layered = _layered_layout(ops, self.policy, self.bucket)
         # AURPPO_LAYERED_NATIVE=1 (opt-in, read only where the layered update is on): the step as one native call
         # (ops.mlp_layered_step_native), and with a single process, fused Adam and a bucket that holds exactly the policy, clip + Adam
         # behind it in the same call (ops.mlp_layered_minibatch)
@@ -171,7 +180,7 @@ class ppo(FlatAdamMixin):
         self._mlp_layered_act = None
         if (self._mlp is None and params.get("fused_mlp", True) and self.device.type == "cuda" and hasattr(ops, "mlp_layered_act")
                 and os.environ.get("AURPPO_LAYERED_ACT", LAYERED_ACT_DEFAULT) != "0"):
-            self._mlp_layered_act = ops.mlp_layered_layout(self.policy, self.bucket, any_state=True)
+            self._mlp_layered_act = _layered_layout(ops, self.policy, self.bucket)
         # ... on the small-M products, both nets' layer in one launch (ops.mlp_layered_act(paired=True): the same bits in L + 1
         # launches).  Opt-in (AURPPO_LAYERED_ACT_PAIRED=1), and read only where the layered rollout step is on.
         self._act_paired = _layered_act_paired(self._mlp_layered_act)
@@ -489,12 +498,13 @@ class ppo(FlatAdamMixin):
             return "halves_p2p" if self._p2p is not None else "halves_allreduce"
         if packed and self._mlp is not None:
             return "fused_step"         # one fused launch: rows are read through the permutation, gradients land in the bucket
-        if packed and self._mlp_layered is not None and self._layered_native:
-            # the native layered step; clip + Adam ride in the same call where nothing has to happen between the two
+        if packed and self._mlp_layered is not None and (self._layered_native or self._mlp_layered.get("ragged_hidden")):
+            # the native layered step (a ragged hidden width has no other, whatever AURPPO_LAYERED_NATIVE says); clip + Adam ride in
+            # the same call where nothing has to happen between the two
             if (not self._dp and self._fused_adam and self.bucket.numel == self._mlp_layered["n_params"]
                     and hasattr(ops, "mlp_layered_minibatch")):
                 return "layered_minibatch"
-            if hasattr(ops, "mlp_layered_step_native"):
+            if hasattr(ops, "mlp_layered_step_native") or self._mlp_layered.get("ragged_hidden"):
                 return "layered_native_step"
         if packed and self._mlp_layered is not None:
             return "layered_step"       # rows through the permutation in the first product, the loss behind the last one

@@ -453,6 +453,40 @@ int aurppo_mlp_layered_minibatch_f32(const float* obs, const float* actions, con
                                      const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
                                      void* workspace, void* stream);
 
+/* ---- the layered steps at any hidden width ----------------------------------------------------------------------------------
+ * The entries above refuse a hidden width that is no multiple of 32 (-d 200, 300, 400, 500; 100 over Humanoid's 376 state floats).
+ * Each entry below takes the argument list of its sibling, unchanged, the same checks and the same limits, but any hidden width in
+ * 1..1024: `hidden` is the bucket's width -- offsets and n_params are the unpadded policy's -- and the step runs as the policy of
+ * width Hp = 32 * ceil(hidden / 32) whose extra weights and biases are zero.  That is exact (a pad unit's pre-activation is 0,
+ * tanh(0) is exactly 0 as the kernels form it, its outgoing weights are zero planes), the pad entries exist in neither bucket, and
+ * nothing is written for them: grads gets its [0, n_params) and nothing else.  Results are bit for bit those of the Hp-wide
+ * zero-padded policy through the sibling entry, and at hidden % 32 == 0 each entry IS its sibling.
+ *   wop: aurppo_mlp_layered_anyh_wop_bytes(D, hidden, num_layers) = the sibling's figure at Hp (the padded operand copies);
+ *     workspaces likewise: the activation planes are (rows, Hp).  All three size functions return 0 outside 1..1024.
+ *   Launch counts are the siblings': prep 2 L, act 2 L + 1 (paired: L + 1), step 12 L - 1, minibatch two more.
+ *   A buffer prepared by aurppo_mlp_layered_anyh_prep_f32 goes to the anyh act entries only. */
+size_t aurppo_mlp_layered_anyh_wop_bytes(int D, int hidden, int num_layers);
+int aurppo_mlp_layered_anyh_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers, void* wop,
+                                     void* stream);
+size_t aurppo_mlp_layered_anyh_act_workspace_bytes(int N, int hidden);
+int aurppo_mlp_layered_anyh_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                    int num_layers, const float* params, const int* offsets, int n_params, float* actions, float* logp,
+                                    float* value, const void* wop, void* workspace, void* stream);
+int aurppo_mlp_layered_anyh_act_paired_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                           int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                           float* logp, float* value, const void* wop, void* workspace, void* stream);
+size_t aurppo_mlp_layered_anyh_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers);
+int aurppo_mlp_layered_anyh_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
+                                     int continuous, int hidden, int num_layers, const float* params, const int* offsets, int n_params,
+                                     float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
+                                     float* out_scalars, void* workspace, void* stream);
+int aurppo_mlp_layered_anyh_minibatch_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
+                                          int A, int continuous, int hidden, int num_layers, float* params, const int* offsets,
+                                          int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                          int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
+                                          const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
+                                          void* workspace, void* stream);
+
 /* K12 -- the weight gradient of the 3x3 convolution of aurppo_conv3x3_f32 (src/nets/base_cnns.py:32-45, src/nets/equiv.py:12-62;
  * what loss.backward() leaves in <conv>.weight.grad, src/robot_ppo.py:389): dw (Co, Ci, 3, 3) from x (B, Ci, H, W) and the
  * output gradient dy (B, Co, H + 2 pad - 2, W + 2 pad - 2), NCHW fp32, as a product over the batch's output pixels on bf16 MFMAs
