@@ -36,6 +36,9 @@ SYMBOLS = (
     "aurppo_mlp_layered_anyh_step_workspace_bytes", "aurppo_mlp_layered_anyh_step_f32", "aurppo_mlp_layered_anyh_minibatch_f32",
     "aurppo_mlp_layered_anyh_wop_bytes", "aurppo_mlp_layered_anyh_prep_f32", "aurppo_mlp_layered_anyh_act_workspace_bytes",
     "aurppo_mlp_layered_anyh_act_f32", "aurppo_mlp_layered_anyh_act_paired_f32",
+    "aurppo_head_ppo_wa_workspace_bytes", "aurppo_head_ppo_wa_f32", "aurppo_head_act_wa_f32",
+    "aurppo_mlp_layered_wa_step_workspace_bytes", "aurppo_mlp_layered_wa_step_f32", "aurppo_mlp_layered_wa_minibatch_f32",
+    "aurppo_mlp_layered_wa_act_f32", "aurppo_mlp_layered_wa_act_paired_f32",
 )
 
 _lib = None
@@ -143,6 +146,12 @@ def _declare(lib):
     for name in ("wop_bytes", "prep_f32", "act_workspace_bytes", "act_f32", "act_paired_f32", "step_workspace_bytes", "step_f32",
                  "minibatch_f32"):
         getattr(lib, "aurppo_mlp_layered_anyh_" + name).argtypes = getattr(lib, "aurppo_mlp_layered_" + name).argtypes
+    # K13, K14 and the layered steps with up to 32 actions: each entry has its sibling's argument list
+    lib.aurppo_head_ppo_wa_workspace_bytes.argtypes = lib.aurppo_head_ppo_workspace_bytes.argtypes
+    lib.aurppo_head_ppo_wa_f32.argtypes = lib.aurppo_head_ppo_f32.argtypes
+    lib.aurppo_head_act_wa_f32.argtypes = lib.aurppo_head_act_f32.argtypes
+    for name in ("act_f32", "act_paired_f32", "step_workspace_bytes", "step_f32", "minibatch_f32"):
+        getattr(lib, "aurppo_mlp_layered_wa_" + name).argtypes = getattr(lib, "aurppo_mlp_layered_anyh_" + name).argtypes
     lib.aurppo_conv3x3_wgrad_ws_bytes.argtypes = [i32] * 6
     lib.aurppo_conv3x3_wgrad_f32.argtypes = [vp, vp, vp] + [i32] * 6 + ws_stream
     # the narrow builds of the 16 -> 32 block's gradients
@@ -187,6 +196,7 @@ def _declare(lib):
              "aurppo_linear_wgrad_bias_ws_bytes", "aurppo_mlp_layered_step_workspace_bytes",
              "aurppo_conv3x3_dgrad_narrow_wop_bytes", "aurppo_conv3x3_wgrad_narrow_ws_bytes", "aurppo_planes_bytes",
              "aurppo_linear_pair_wop_bytes", "aurppo_mlp_layered_anyh_wop_bytes", "aurppo_mlp_layered_anyh_act_workspace_bytes",
-             "aurppo_mlp_layered_anyh_step_workspace_bytes")
+             "aurppo_mlp_layered_anyh_step_workspace_bytes", "aurppo_head_ppo_wa_workspace_bytes",
+             "aurppo_mlp_layered_wa_step_workspace_bytes")
     for name in SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "aurppo_last_error" else C.c_size_t if name in sized else i32

@@ -102,10 +102,12 @@ int linear_wgrad_product(const float* dy, const float* x, const int32_t* rows, f
 int fold_slices_pad_launch(const float* part, int S, int Np, int Kp, int Nr, int Kr, float* out, const double* bpart, float* db, hipStream_t s);
 // K13 / K14's shape rule (H a multiple of 32) and the two kernels on checked operands (head.hip), for the layered steps
 bool head_shape_ok(int H, int A, int continuous);
+// ... with at most max_a actions: 16 (head_shape_ok), or 32 for the wide-action (`wa`) entries, whose A in 17 .. 32 runs the kernels' NA = 32 builds
+bool head_shape_ok_upto(int H, int A, int continuous, int max_a);
 int head_ppo_run(const char* who, const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
                  const int32_t* idx, int M, int H, int Hr, int A, int continuous, const float* params, const int* layout_h, int n_params,
                  float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace,
-                 void* stream);
+                 void* stream, int max_a);
 int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int Hr, int A, int continuous, const float* params,
                     const int* lay, float* actions, float* logp, float* value, hipStream_t s);
 // The kernels conv.hip and linear.hip both run live in conv.hip: linear_prep above (k_conv_prep / k_linear_prep_tail), the fold of a

@@ -28,7 +28,17 @@ namespace {
 constexpr int kHT = 256;             // threads per workgroup
 constexpr int kHeadMaxGrid = 512;
 constexpr int kHeadStat = 64;        // statistics workgroups (at most)
-constexpr int kSmall = 48;           // slab tail: d b_actor [16], d logstd [16], d b_critic [1] + padding
+// NA: the length of a head kernel's per-action register arrays, 16 for A <= 16 and 32 for A in 17 .. 32.  The critic's product sits in
+// slot p[NA]; s_small and the slab tail are 3 NA floats: d b_actor [NA], d logstd [NA], d b_critic [1] + padding.
+constexpr int kHeadMaxA = 32;
+__host__ __device__ constexpr int head_na(int A) { return A > 16 ? 32 : 16; }
+__host__ __device__ constexpr int head_small(int NA) { return 3 * NA; }
+// The accumulator of a Gaussian head's log-prob, a sum of A fp32 terms of one sign: fp32, added in order, up to 16 actions.  At 17 .. 32
+// that order's rounding is twice that of a tree sum at the same width and lifts the actor's gradients to 2.05 - 2.08 x the fp32 yardstick
+// (tests/test_layered_actions_fp64_gpu.py: the per-sample ratio exp(logp - old_logp) carries it into every one of them), so NA = 32 adds
+// the same fp32 terms in fp64 and rounds once.  K13 and K14 share the type: the log-prob K14 stores stays the one K13 forms.
+template <int NA>
+using HeadLogpAcc = std::conditional_t<(NA > 16), double, float>;
 
 struct HeadArgs {
     const float* hA;                 // (M, H) last hidden activations, minibatch order
@@ -53,7 +63,7 @@ struct HeadArgs {
     PpoHyper h;
 };
 
-__host__ __device__ constexpr int head_slab_floats(int H, int A) { return (A + 3) * H + kSmall; }
+__host__ __device__ constexpr int head_slab_floats(int H, int A) { return (A + 3) * H + head_small(head_na(A)); }
 
 __global__ __launch_bounds__(kHT) void k_head_stats(const float4* __restrict__ rec, int rec_stride, const int32_t* __restrict__ idx, int M,
                                                     double (*__restrict__ stats)[2]) {
@@ -97,15 +107,22 @@ __device__ __forceinline__ void fma4(float4& acc, float s, const float4 v) {
 // H = 1024 (M = 131072), above the two-copy build in every one of four alternating rounds, and no single piece carried it
 // (profiles/refactor_head_rollout.txt, section 5).  tests/test_layered_act_fp64_gpu.py and tools/build_bitdiff.py hold the two copies
 // to the same bits.
-template <int TPR>      // threads per row: the power of two >= H / 4, 8 ... 256
+//
+// NA = 32 (A in 17 .. 32) is the same text with longer arrays, and two savings of registers that NA = 16 does not take (kLean): the
+// logstd gradient of a row goes into dls[k] where it is formed (no dlr[]), and an action is read from its row where it is used, in both
+// loops, instead of a copy of the row held across the reductions (no actv[]).  Both leave every sum's terms and order as they are.  The
+// Gaussian log-prob alone is summed differently at NA = 32 (HeadLogpAcc).
+template <int TPR, int NA>      // threads per row: the power of two >= H / 4, 8 ... 256; per-action array length: 16 | 32
 __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
     constexpr int GPW = kHT / TPR;                     // rows a workgroup works on at a time
     constexpr int NWG = TPR > kWave ? TPR / kWave : 1;   // waves per row
     constexpr int LW = TPR > kWave ? kWave : TPR;      // lanes of a wave on one row
+    constexpr int kSmall = head_small(NA);
+    constexpr bool kLean = NA > 16;
     extern __shared__ __attribute__((aligned(16))) float sW[];       // (A + 1, H): actor head rows, then the critic's
     __shared__ __attribute__((aligned(16))) float s_red[kHT * 4];
-    __shared__ float s_small[kSmall];                  // b_actor [16], logstd [16], std * std [16]
-    __shared__ float s_part[2][kHT / kWave][20];
+    __shared__ float s_small[kSmall];                  // b_actor [NA], logstd [NA], std * std [NA]
+    __shared__ float s_part[2][kHT / kWave][NA + 4];
     __shared__ float s_sm[32][kSmall];
     __shared__ double s_loss[32][6];
     __shared__ double s_dred[2][kHT / kWave];
@@ -121,12 +138,12 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
             for (int c = tid; c < H; c += kHT) sW[k * H + c] = c < a.Hr ? src[c] : 0.0f;
         }
     }
-    if (tid < 16) {
+    if (tid < NA) {
         s_small[tid] = tid < A ? a.params[a.off_ba + tid] : 0.0f;
         const float ls = (a.continuous && tid < A) ? a.params[a.off_ls + tid] : 0.0f;
         const float sd = expf(ls);
-        s_small[16 + tid] = ls;
-        s_small[32 + tid] = sd * sd;
+        s_small[NA + tid] = ls;
+        s_small[2 * NA + tid] = sd * sd;
     }
     __syncthreads();
     const float mean = s_ms[0], denom = s_ms[1] + 1e-8f;
@@ -142,10 +159,10 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
     const float4 wc = *reinterpret_cast<const float4*>(sW + A * H + cw);
     const float4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
-    float4 dWa[16], dWc = zero4, dblA = zero4, dblC = zero4;
-    float dba[16], dls[16], dbc = 0.0f;
+    float4 dWa[NA], dWc = zero4, dblA = zero4, dblC = zero4;
+    float dba[NA], dls[NA], dbc = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
+    for (int k = 0; k < NA; ++k) {
         dWa[k] = zero4;
         dba[k] = dls[k] = 0.0f;
     }
@@ -172,28 +189,33 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
         const int src = nsrc;
         // this row's record and action row: asked for here, used behind the dot products
         float4 rc = zero4;
-        float actv[16];
+        float actv[NA];
+        const float* ap = nullptr;
+        if constexpr (!kLean) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) actv[k] = 0.0f;
+            for (int k = 0; k < NA; ++k) actv[k] = 0.0f;
+        }
         if (valid) {
             rc = a.rec[(size_t)src * a.rec_stride];
-            const float* ap = a.actions ? a.actions + (size_t)src * a.aw : reinterpret_cast<const float*>(a.rec) + (size_t)src * 16 + 4;
+            ap = a.actions ? a.actions + (size_t)src * a.aw : reinterpret_cast<const float*>(a.rec) + (size_t)src * 16 + 4;
+            if constexpr (!kLean) {
 #pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < a.aw) actv[k] = ap[k];
+                for (int k = 0; k < NA; ++k)
+                    if (k < a.aw) actv[k] = ap[k];
+            }
         }
         fetch(row + G);
 
-        float p[17];
+        float p[NA + 1];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NA; ++k) {
             p[k] = 0.0f;
             if (k < A) p[k] = dot4(ha, *reinterpret_cast<const float4*>(sW + k * H + cw));
         }
-        p[16] = dot4(hc, wc);
+        p[NA] = dot4(hc, wc);
 #pragma unroll
-        for (int k = 0; k < 17; ++k) {
-            if (k < A || k == 16) {
+        for (int k = 0; k < NA + 1; ++k) {
+            if (k < A || k == NA) {
 #pragma unroll
                 for (int off = LW / 2; off > 0; off >>= 1) p[k] += __shfl_xor(p[k], off, kWave);
             }
@@ -202,13 +224,13 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
             float* const mine = s_part[it & 1][wave];
             if (lane == 0) {
 #pragma unroll
-                for (int k = 0; k < 17; ++k)
-                    if (k < A || k == 16) mine[k] = p[k];
+                for (int k = 0; k < NA + 1; ++k)
+                    if (k < A || k == NA) mine[k] = p[k];
             }
             __syncthreads();
 #pragma unroll
-            for (int k = 0; k < 17; ++k) {
-                if (k < A || k == 16) {
+            for (int k = 0; k < NA + 1; ++k) {
+                if (k < A || k == NA) {
                     float s = 0.0f;
 #pragma unroll
                     for (int w = 0; w < NWG; ++w) s += s_part[it & 1][g * NWG + w][k];
@@ -218,38 +240,42 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
         }
         // ---- the row's loss terms (every lane of the row forms the same bits); p[k] becomes d loss / d head output k
         float dv = 0.0f;
-        float dlr[16];
+        float dlr[NA];
+        if constexpr (!kLean) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) dlr[k] = 0.0f;
+            for (int k = 0; k < NA; ++k) dlr[k] = 0.0f;
+        }
         if (valid) {
-            const float v_new = p[16] + bc;
+            const float v_new = p[NA] + bc;
             PpoSample ts;
             if (a.continuous) {
-                float logp = 0.0f, ent = 0.0f;
+                HeadLogpAcc<NA> logp = 0.0f;
+                float ent = 0.0f;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NA; ++k) {
                     if (k < A) {
-                        const float ls = s_small[16 + k], var = s_small[32 + k];
-                        const float z = actv[k] - (p[k] + s_small[k]);
+                        const float ls = s_small[NA + k], var = s_small[2 * NA + k];
+                        const float z = (kLean ? ap[k] : actv[k]) - (p[k] + s_small[k]);
                         logp += gauss_logp_var(z, var, ls);
                         ent += gauss_ent(ls);
                     }
                 }
-                ts = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
+                ts = ppo_sample((float)logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NA; ++k) {
                     if (k < A) {
-                        const float var = s_small[32 + k];
-                        const float z = actv[k] - (p[k] + s_small[k]);
+                        const float var = s_small[2 * NA + k];
+                        const float z = (kLean ? ap[k] : actv[k]) - (p[k] + s_small[k]);
                         p[k] = gauss_dmu_var(ts.g_logp, z, var);
-                        dlr[k] = gauss_dls_var(ts.g_logp, z, var, g_ent);
+                        if constexpr (kLean) dls[k] += gauss_dls_var(ts.g_logp, z, var, g_ent);
+                        else dlr[k] = gauss_dls_var(ts.g_logp, z, var, g_ent);
                     }
                 }
                 l_ent += (double)ent;
             } else {
                 float mx = -INFINITY;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NA; ++k) {
                     if (k < A) {
                         p[k] += s_small[k];
                         mx = fmaxf(mx, p[k]);
@@ -257,13 +283,13 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
                 }
                 float se = 0.0f;
 #pragma unroll
-                for (int k = 0; k < 16; ++k)
+                for (int k = 0; k < NA; ++k)
                     if (k < A) se += expf(p[k] - mx);
                 const float lse = mx + logf(se);
-                const int ai = (int)actv[0];
+                const int ai = (int)(kLean ? ap[0] : actv[0]);
                 float logp = 0.0f, ent = 0.0f;
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NA; ++k) {
                     if (k < A) {
                         const float lpk = p[k] - lse;
                         ent -= expf(lpk) * lpk;
@@ -272,7 +298,7 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
                 }
                 ts = ppo_sample(logp, rc.x, rc.y, v_new, rc.w, rc.z, mean, denom, invM, a.h);
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
+                for (int k = 0; k < NA; ++k) {
                     if (k < A) {
                         const float lpk = p[k] - lse;
                         const float pk = expf(lpk);
@@ -289,17 +315,17 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
             l_cf += (double)ts.cf;
         } else {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) p[k] = 0.0f;
+            for (int k = 0; k < NA; ++k) p[k] = 0.0f;
         }
         // ---- backward: gz of both nets for this thread's four columns, the register accumulators
         float4 ga = zero4;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NA; ++k) {
             if (k < A) {
                 fma4(ga, p[k], *reinterpret_cast<const float4*>(sW + k * H + cw));
                 fma4(dWa[k], p[k], ha);
                 dba[k] += p[k];
-                dls[k] += dlr[k];
+                if constexpr (!kLean) dls[k] += dlr[k];
             }
         }
         const float4 gza = {ga.x * (1.0f - ha.x * ha.x), ga.y * (1.0f - ha.y * ha.y), ga.z * (1.0f - ha.z * ha.z), ga.w * (1.0f - ha.w * ha.w)};
@@ -332,17 +358,17 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
         }
     };
 #pragma unroll
-    for (int k = 0; k < 16; ++k)
+    for (int k = 0; k < NA; ++k)
         if (k < A) emit(dWa[k], k * H);
     emit(dWc, A * H);
     emit(dblA, (A + 1) * H);
     emit(dblC, (A + 2) * H);
     if (t == 0) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NA; ++k) {
             s_sm[g][k] = dba[k];
-            s_sm[g][16 + k] = dls[k];
-            s_sm[g][32 + k] = k == 0 ? dbc : 0.0f;
+            s_sm[g][NA + k] = dls[k];
+            s_sm[g][2 * NA + k] = k == 0 ? dbc : 0.0f;
         }
         s_loss[g][0] = l_pg; s_loss[g][1] = l_vl; s_loss[g][2] = l_ent; s_loss[g][3] = l_okl; s_loss[g][4] = l_kl; s_loss[g][5] = l_cf;
     }
@@ -361,7 +387,8 @@ __global__ __launch_bounds__(kHT) void k_head_ppo(const HeadArgs a) {
 
 // grads[...] = the slabs summed in workgroup order (eight runs of consecutive slabs, each summed in order in fp64, then the eight
 // in order; rounded once); the workgroup past the last folds the loss sums into the nine scalars (k_loss_final's arithmetic).
-__global__ __launch_bounds__(kHT) void k_head_fold(const HeadArgs a, int n_slabs, float* __restrict__ grads, float* __restrict__ out) {
+// NA: the slab tail's layout, the one the k_head_ppo build that wrote the slabs used.
+__global__ __launch_bounds__(kHT) void k_head_fold(const HeadArgs a, int n_slabs, int NA, float* __restrict__ grads, float* __restrict__ out) {
     __shared__ double s_run[8][32];
     __shared__ double sc[6][kHT / kWave];
     __shared__ float s_ms[2];
@@ -427,9 +454,9 @@ __global__ __launch_bounds__(kHT) void k_head_fold(const HeadArgs a, int n_slabs
     else if (e < (A + 3) * H) dst = a.off_blc + (e - (A + 2) * H);
     else {
         const int j = e - (A + 3) * H;
-        if (j < 16) dst = j < A ? a.off_ba + j : -1;
-        else if (j < 32) dst = (a.continuous && j - 16 < A) ? a.off_ls + (j - 16) : -1;
-        else if (j == 32) dst = a.off_bc;
+        if (j < NA) dst = j < A ? a.off_ba + j : -1;
+        else if (j < 2 * NA) dst = (a.continuous && j - NA < A) ? a.off_ls + (j - NA) : -1;
+        else if (j == 2 * NA) dst = a.off_bc;
     }
     if (dst >= 0) grads[dst] = (float)total;
 }
@@ -486,14 +513,14 @@ struct HeadActArgs {
     int Hr;                          // floats of a head row in the bucket (HeadArgs::Hr)
 };
 
-template <int TPR>
+template <int TPR, int NA>
 __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
     constexpr int GPW = kHT / TPR;
     constexpr int NWG = TPR > kWave ? TPR / kWave : 1;
     constexpr int LW = TPR > kWave ? kWave : TPR;
     extern __shared__ __attribute__((aligned(16))) float sW[];       // (A + 1, H): actor head rows, then the critic's
-    __shared__ float s_small[kSmall];                  // b_actor [16], logstd [16], std [16]
-    __shared__ float s_part[2][kHT / kWave][20];
+    __shared__ float s_small[head_small(NA)];          // b_actor [NA], logstd [NA], std [NA]
+    __shared__ float s_part[2][kHT / kWave][NA + 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int H = a.H, A = a.A;
     const int nA = a.noise ? A : 0;                    // actor outputs to form: none for the value alone
@@ -508,11 +535,11 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             for (int c = tid; c < H; c += kHT) sW[k * H + c] = c < a.Hr ? src[c] : 0.0f;
         }
     }
-    if (tid < 16) {
+    if (tid < NA) {
         s_small[tid] = tid < nA ? a.params[a.off_ba + tid] : 0.0f;
         const float ls = (a.continuous && tid < nA) ? a.params[a.off_ls + tid] : 0.0f;
-        s_small[16 + tid] = ls;
-        s_small[32 + tid] = expf(ls);
+        s_small[NA + tid] = ls;
+        s_small[2 * NA + tid] = expf(ls);
     }
     __syncthreads();
     const float bc = a.params[a.off_bc];
@@ -540,16 +567,16 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
         const float4 ha = na, hc = nc;
         fetch(row + G);
 
-        float p[17];
+        float p[NA + 1];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < NA; ++k) {
             p[k] = 0.0f;
             if (k < nA) p[k] = dot4(ha, *reinterpret_cast<const float4*>(sW + k * H + cw));
         }
-        p[16] = dot4(hc, wc);
+        p[NA] = dot4(hc, wc);
 #pragma unroll
-        for (int k = 0; k < 17; ++k) {
-            if (k < nA || k == 16) {
+        for (int k = 0; k < NA + 1; ++k) {
+            if (k < nA || k == NA) {
 #pragma unroll
                 for (int off = LW / 2; off > 0; off >>= 1) p[k] += __shfl_xor(p[k], off, kWave);
             }
@@ -558,13 +585,13 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             float* const mine = s_part[it & 1][wave];
             if (lane == 0) {
 #pragma unroll
-                for (int k = 0; k < 17; ++k)
-                    if (k < nA || k == 16) mine[k] = p[k];
+                for (int k = 0; k < NA + 1; ++k)
+                    if (k < nA || k == NA) mine[k] = p[k];
             }
             __syncthreads();
 #pragma unroll
-            for (int k = 0; k < 17; ++k) {
-                if (k < nA || k == 16) {
+            for (int k = 0; k < NA + 1; ++k) {
+                if (k < nA || k == NA) {
                     float s = 0.0f;
 #pragma unroll
                     for (int w = 0; w < NWG; ++w) s += s_part[it & 1][g * NWG + w][k];
@@ -573,20 +600,20 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             }
         }
         if (!valid || t != 0) continue;
-        a.value[row] = p[16] + bc;
+        a.value[row] = p[NA] + bc;
         if (!nA) continue;
         if (a.continuous) {
             const float* const eps = a.noise + (size_t)row * A;
             float* const out = a.actions + (size_t)row * A;
-            float logp = 0.0f;
+            HeadLogpAcc<NA> logp = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k)
-                if (k < A) logp += gauss_sample(p[k] + s_small[k], s_small[32 + k], s_small[16 + k], eps[k], out[k]);
-            a.logp[row] = logp;
+            for (int k = 0; k < NA; ++k)
+                if (k < A) logp += gauss_sample(p[k] + s_small[k], s_small[2 * NA + k], s_small[NA + k], eps[k], out[k]);
+            a.logp[row] = (float)logp;
         } else {
             float mx = -INFINITY;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
+            for (int k = 0; k < NA; ++k) {
                 if (k < A) {
                     p[k] += s_small[k];
                     mx = fmaxf(mx, p[k]);
@@ -594,7 +621,7 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             }
             float se = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k)
+            for (int k = 0; k < NA; ++k)
                 if (k < A) se += expf(p[k] - mx);
             const float lse = mx + logf(se);
             const float u = a.noise[row];
@@ -602,7 +629,7 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             int pick = A - 1;
             bool open = true;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) {
+            for (int k = 0; k < NA; ++k) {
                 if (k < A && open) {
                     cdf += expf(p[k] - lse);
                     if (u < cdf) {
@@ -613,7 +640,7 @@ __global__ __launch_bounds__(kHT) void k_head_act(const HeadActArgs a) {
             }
             float logp = 0.0f;
 #pragma unroll
-            for (int k = 0; k < 16; ++k)
+            for (int k = 0; k < NA; ++k)
                 if (k == pick) logp = p[k] - lse;
             a.actions[row] = (float)pick;
             a.logp[row] = logp;
@@ -631,22 +658,37 @@ int head_act_grid(int N, int H) {
 }
 
 // The TPR build of a head kernel for a.H, on `grid` workgroups with its (A + 1) x H weights as dynamic LDS: launch_k_head_ppo,
-// launch_k_head_act.  The limit is raised to the largest shape's, once per build and device.
+// launch_k_head_act.  The limit is raised to the largest shape's, once per build and device.  NA follows from A alone (head_na): A <= 16
+// runs the NA = 16 builds whichever entry asked.
 #define AURPPO_HEAD_DISPATCH(K, ARGS)                                                                                  \
-    int launch_##K(const ARGS& a, int grid, hipStream_t s) {                                                           \
-        const size_t lds = (size_t)(a.A + 1) * a.H * sizeof(float), cap = (size_t)17 * 1024 * sizeof(float);           \
+    template <int NA>                                                                                                  \
+    int launch_na_##K(const ARGS& a, int grid, hipStream_t s) {                                                        \
+        const size_t lds = (size_t)(a.A + 1) * a.H * sizeof(float), cap = (size_t)(NA + 1) * 1024 * sizeof(float);     \
         switch (head_tpr(a.H)) {                                                                                       \
-            case 8: return launch_dyn_lds<K<8>>(#K, grid, kHT, lds, cap, s, a);                                        \
-            case 16: return launch_dyn_lds<K<16>>(#K, grid, kHT, lds, cap, s, a);                                      \
-            case 32: return launch_dyn_lds<K<32>>(#K, grid, kHT, lds, cap, s, a);                                      \
-            case 64: return launch_dyn_lds<K<64>>(#K, grid, kHT, lds, cap, s, a);                                      \
-            case 128: return launch_dyn_lds<K<128>>(#K, grid, kHT, lds, cap, s, a);                                    \
-            default: return launch_dyn_lds<K<256>>(#K, grid, kHT, lds, cap, s, a);                                     \
+            case 8: return launch_dyn_lds<K<8, NA>>(#K, grid, kHT, lds, cap, s, a);                                    \
+            case 16: return launch_dyn_lds<K<16, NA>>(#K, grid, kHT, lds, cap, s, a);                                  \
+            case 32: return launch_dyn_lds<K<32, NA>>(#K, grid, kHT, lds, cap, s, a);                                  \
+            case 64: return launch_dyn_lds<K<64, NA>>(#K, grid, kHT, lds, cap, s, a);                                  \
+            case 128: return launch_dyn_lds<K<128, NA>>(#K, grid, kHT, lds, cap, s, a);                                \
+            default: return launch_dyn_lds<K<256, NA>>(#K, grid, kHT, lds, cap, s, a);                                 \
         }                                                                                                              \
+    }                                                                                                                  \
+    int launch_##K(const ARGS& a, int grid, hipStream_t s) {                                                           \
+        return head_na(a.A) == 32 ? launch_na_##K<32>(a, grid, s) : launch_na_##K<16>(a, grid, s);                     \
     }
 AURPPO_HEAD_DISPATCH(k_head_act, HeadActArgs)
 AURPPO_HEAD_DISPATCH(k_head_ppo, HeadArgs)
 #undef AURPPO_HEAD_DISPATCH
+
+// The largest build's LDS: k_head_ppo<*, 32>'s static arrays (s_red, s_small, s_part, s_sm, s_loss, s_dred, s_ms, each rounded up to 16
+// bytes) beside (32 + 1) x 1024 dynamic floats, within the CU's 160 KiB.
+constexpr size_t head_ppo_static_lds(int NA) {
+    auto up = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
+    return up((size_t)kHT * 16) + up((size_t)head_small(NA) * 4) + up((size_t)2 * (kHT / kWave) * (NA + 4) * 4) +
+           up((size_t)32 * head_small(NA) * 4) + up((size_t)32 * 6 * 8) + up((size_t)2 * (kHT / kWave) * 8) + 16;
+}
+static_assert(head_ppo_static_lds(kHeadMaxA) + (size_t)(kHeadMaxA + 1) * 1024 * sizeof(float) <= (size_t)160 * 1024,
+              "k_head_ppo<*, 32>: dynamic + static LDS above the CU's 160 KiB");
 
 // rows each of the grid's row groups takes: ceil(rows / (grid * rows per workgroup))
 int head_n_iter(int rows, int H, int grid) {
@@ -664,7 +706,11 @@ int head_layout_check(const int* layout, const long long* need, int count, int n
 
 }  // namespace
 
-bool head_shape_ok(int H, int A, int continuous) { return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= 16 && (continuous || A >= 2); }
+// max_a: 16 for the entries that came first, 32 for the `wa` (wide action head) entries
+bool head_shape_ok_upto(int H, int A, int continuous, int max_a) {
+    return H % 32 == 0 && H >= 32 && H <= 1024 && A >= 1 && A <= max_a && (continuous || A >= 2);
+}
+bool head_shape_ok(int H, int A, int continuous) { return head_shape_ok_upto(H, A, continuous, 16); }
 
 // K14 on checked operands; lay = {actor head w, b; critic head w, b; actor_logstd}  (this and head_shape_ok: also layered.hip's)
 int head_act_launch(const float* hA, const float* hC, const float* noise, int N, int H, int Hr, int A, int continuous, const float* params,
@@ -683,17 +729,23 @@ extern "C" size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A) {
     if (M <= 0 || !head_shape_ok(H, A, 1)) return 0;
     return head_carve(nullptr, M, H, A).bytes;
 }
+// ... with A up to 32: the same figure at A <= 16
+extern "C" size_t aurppo_head_ppo_wa_workspace_bytes(int M, int H, int A) {
+    if (M <= 0 || !head_shape_ok_upto(H, A, 1, kHeadMaxA)) return 0;
+    return head_carve(nullptr, M, H, A).bytes;
+}
 
-// K13's three launches under the entry's name `who`: (M, H) planes, head rows and last-layer biases of Hr <= H floats in the bucket
+// K13's three launches under the entry's name `who`: (M, H) planes, head rows and last-layer biases of Hr <= H floats in the bucket,
+// at most max_a (16 | 32) actions
 int head_ppo_run(const char* who, const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
                  const int32_t* idx, int M, int H, int Hr, int A, int continuous, const float* params, const int* layout_h, int n_params,
                  float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace,
-                 void* stream) {
+                 void* stream, int max_a) {
     AURPPO_REQUIRE(hA && hC && gzA && gzC && rec && idx && params && layout_h && grads && out_scalars && workspace, AURPPO_EINVAL,
                    "%s: null pointer", who);
     AURPPO_REQUIRE(M > 0, AURPPO_ESHAPE, "%s: M=%d", who, M);
-    AURPPO_REQUIRE(head_shape_ok(H, A, continuous) && Hr >= 1 && Hr <= H, AURPPO_ESHAPE,
-                   "%s: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", who, H, A);
+    AURPPO_REQUIRE(head_shape_ok_upto(H, A, continuous, max_a) && Hr >= 1 && Hr <= H, AURPPO_ESHAPE,
+                   "%s: H=%d (a multiple of 32, 32..1024), A=%d (1..%d, Categorical: 2..%d)", who, H, A, max_a, max_a);
     AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: vloss_mode %d", who, vloss_mode);
     const int aw = continuous ? A : 1;
     AURPPO_REQUIRE(actions || aw <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (A=%d)", who, A);
@@ -723,32 +775,47 @@ int head_ppo_run(const char* who, const float* hA, const float* hC, float* gzA, 
     AURPPO_LAUNCH_CHECK("k_head_stats");
     if (const int rc = launch_k_head_ppo(a, grid, s)) return rc;
     const int n = head_slab_floats(H, A);
-    hipLaunchKernelGGL(k_head_fold, dim3((n + 31) / 32 + 1), dim3(kHT), 0, s, a, grid, grads, out_scalars);
+    hipLaunchKernelGGL(k_head_fold, dim3((n + 31) / 32 + 1), dim3(kHT), 0, s, a, grid, head_na(A), grads, out_scalars);
     AURPPO_LAUNCH_CHECK("k_head_fold");
     return AURPPO_OK;
 }
 
-extern "C" int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
-                                   const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
-                                   int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
-                                   int vloss_mode, float* out_scalars, void* workspace, void* stream) {
-    return head_ppo_run("aurppo_head_ppo_f32", hA, hC, gzA, gzC, actions, rec, idx, M, H, H, A, continuous, params, layout_h, n_params, grads,
-                        clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream);
-}
+#define AURPPO_HEAD_PPO_ENTRY(NAME, MAX_A)                                                                                                \
+    extern "C" int NAME(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,                 \
+                        const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h, int n_params,  \
+                        float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars,      \
+                        void* workspace, void* stream) {                                                                                  \
+        return head_ppo_run(#NAME, hA, hC, gzA, gzC, actions, rec, idx, M, H, H, A, continuous, params, layout_h, n_params, grads, clip,  \
+                            ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, MAX_A);                              \
+    }
+AURPPO_HEAD_PPO_ENTRY(aurppo_head_ppo_f32, 16)
+AURPPO_HEAD_PPO_ENTRY(aurppo_head_ppo_wa_f32, kHeadMaxA)
+#undef AURPPO_HEAD_PPO_ENTRY
 
-// K14 alone: layout_h = {actor head w, b; critic head w, b; actor_logstd}.
-extern "C" int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
-                                   const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
-                                   void* stream) {
-    AURPPO_REQUIRE(hC && params && layout_h && value && (!noise || (hA && actions && logp)), AURPPO_EINVAL,
-                   "aurppo_head_act_f32: null pointer");
-    AURPPO_REQUIRE(N > 0, AURPPO_ESHAPE, "aurppo_head_act_f32: N=%d", N);
-    AURPPO_REQUIRE(head_shape_ok(H, A, continuous), AURPPO_ESHAPE,
-                   "aurppo_head_act_f32: H=%d (a multiple of 32, 32..1024), A=%d (1..16, Categorical: 2..16)", H, A);
-    AURPPO_REQUIRE((!noise || aligned_to(hA, 16)) && aligned_to(hC, 16), AURPPO_EINVAL, "aurppo_head_act_f32: activations not 16-byte aligned");
+namespace {
+
+// K14 alone behind both entries: layout_h = {actor head w, b; critic head w, b; actor_logstd}.
+int head_act_entry(const char* who, const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
+                   const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value, void* stream, int max_a) {
+    AURPPO_REQUIRE(hC && params && layout_h && value && (!noise || (hA && actions && logp)), AURPPO_EINVAL, "%s: null pointer", who);
+    AURPPO_REQUIRE(N > 0, AURPPO_ESHAPE, "%s: N=%d", who, N);
+    AURPPO_REQUIRE(head_shape_ok_upto(H, A, continuous, max_a), AURPPO_ESHAPE,
+                   "%s: H=%d (a multiple of 32, 32..1024), A=%d (1..%d, Categorical: 2..%d)", who, H, A, max_a, max_a);
+    AURPPO_REQUIRE((!noise || aligned_to(hA, 16)) && aligned_to(hC, 16), AURPPO_EINVAL, "%s: activations not 16-byte aligned", who);
     AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
-                   AURPPO_EINVAL, "aurppo_head_act_f32: noise / outputs not 4-byte aligned");
+                   AURPPO_EINVAL, "%s: noise / outputs not 4-byte aligned", who);
     const long long need[5] = {(long long)A * H, A, H, 1, continuous ? A : 0};
-    if (const int rc = head_layout_check(layout_h, need, 5, n_params, "aurppo_head_act_f32")) return rc;
+    if (const int rc = head_layout_check(layout_h, need, 5, n_params, who)) return rc;
     return head_act_launch(hA, hC, noise, N, H, H, A, continuous, params, layout_h, actions, logp, value, (hipStream_t)stream);
 }
+
+}  // namespace
+
+#define AURPPO_HEAD_ACT_ENTRY(NAME, MAX_A)                                                                                                \
+    extern "C" int NAME(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous, const float* params,   \
+                        const int* layout_h, int n_params, float* actions, float* logp, float* value, void* stream) {                     \
+        return head_act_entry(#NAME, hA, hC, noise, N, H, A, continuous, params, layout_h, n_params, actions, logp, value, stream, MAX_A); \
+    }
+AURPPO_HEAD_ACT_ENTRY(aurppo_head_act_f32, 16)
+AURPPO_HEAD_ACT_ENTRY(aurppo_head_act_wa_f32, kHeadMaxA)
+#undef AURPPO_HEAD_ACT_ENTRY

@@ -10,6 +10,10 @@
 // operand copies (k_linear_prep_pad), the bias read (LinArgs::n_bias), the weight gradients' fold (k_fold_slices_pad) and K13 / K14's
 // head rows (HeadArgs::Hr).  Every function below takes `hidden` and forms Hp itself; at a multiple of 32 the two are equal and each
 // call is the one it always was.  The old entries refuse the other widths before they come here (`anyh` false).
+//
+// Up to 32 actions (the aurppo_mlp_layered_wa_* entries, which take any hidden width too): nothing below the heads sees A, so the action
+// limit `max_a` (16 | 32) travels next to `anyh` into the shape check and K13's run, and head.hip picks the kernels' NA = 32 builds for
+// A in 17 .. 32.  The operand copies and the rollout workspace do not depend on A: the wa act entries take the anyh prep's buffer.
 #include "mlp_common.h"
 
 namespace {
@@ -56,7 +60,7 @@ LayeredStepWs layered_step_carve(void* workspace, int M, int D, int A, int width
     w.wop = c.take<char>(aurppo_conv3x3_wop_bytes(D > hidden ? D : hidden, hidden), 64);
     const size_t wg0 = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, D), wg = aurppo_linear_wgrad_bias_ws_bytes(M, hidden, hidden);
     w.wgrad = c.take<char>(wg0 > wg ? wg0 : wg, 64);
-    w.head = c.take<char>(aurppo_head_ppo_workspace_bytes(M, hidden, A), 64);
+    w.head = c.take<char>(aurppo_head_ppo_wa_workspace_bytes(M, hidden, A), 64);     // the old entry's figure at A <= 16
     w.clip = c.take<char>(aurppo_clip_workspace_bytes(0), 64);
     w.bytes = c.bytes;
     return w;
@@ -70,13 +74,13 @@ LayeredStepWs layered_step_carve(void* workspace, int M, int D, int A, int width
 int layered_step_impl(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A, int continuous,
                       int hidden, int num_layers, const float* params, const int* offsets, int n_params, float* grads, double clip,
                       double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace, void* stream,
-                      bool anyh, const char* who) {
+                      bool anyh, int max_a, const char* who) {
     AURPPO_REQUIRE(obs && rec && idx && params && offsets && grads && out_scalars && workspace, AURPPO_EINVAL, "%s: null pointer", who);
     AURPPO_REQUIRE(M > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE, "%s: M=%d, D=%d, %d layers (1..%d)",
                    who, M, D, num_layers, kLayeredMaxLayers);
     const int Hp = layered_padded(hidden);             // the planes' and products' width; `hidden` stays the bucket's
-    AURPPO_REQUIRE(layered_width_ok(hidden, anyh) && head_shape_ok(Hp, A, continuous), AURPPO_ESHAPE,
-                   "%s: hidden=%d (%s), A=%d (1..16, Categorical: 2..16)", who, hidden, layered_width_rule(anyh), A);
+    AURPPO_REQUIRE(layered_width_ok(hidden, anyh) && head_shape_ok_upto(Hp, A, continuous, max_a), AURPPO_ESHAPE,
+                   "%s: hidden=%d (%s), A=%d (1..%d, Categorical: 2..%d)", who, hidden, layered_width_rule(anyh), A, max_a, max_a);
     AURPPO_REQUIRE(actions || (continuous ? A : 1) <= 12, AURPPO_ESHAPE, "%s: packed records hold at most 12 action floats (A=%d)", who, A);
     AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: vloss_mode %d", who, vloss_mode);
     AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(rec, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
@@ -98,7 +102,7 @@ int layered_step_impl(const float* obs, const float* actions, const float* rec, 
                         offsets[2 * L - 1], offsets[per + 2 * L - 1]};
     if (const int rc = head_ppo_run("aurppo_head_ppo_f32", h(0, L - 1), h(1, L - 1), h(0, L - 1), h(1, L - 1), actions, rec, idx, M, Hp, hidden,
                                     A, continuous, params, lay, n_params, grads, clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars,
-                                    w.head, stream))
+                                    w.head, stream, max_a))
         return rc;
     for (int net = 0; net < 2; ++net) {
         const int* o = offsets + net * per;          // h(net, L - 1) now holds gz of the last layer; the lower layers follow in place
@@ -184,14 +188,14 @@ namespace {
 // bits are the unpaired route's: a row's result does not depend on the tile (linear_body.h).
 int layered_act_impl(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden, int num_layers,
                      const float* params, const int* offsets, int n_params, float* actions, float* logp, float* value, const void* wop,
-                     void* workspace, void* stream, bool paired, bool anyh, const char* who) {
+                     void* workspace, void* stream, bool paired, bool anyh, int max_a, const char* who) {
     AURPPO_REQUIRE(obs && params && offsets && value && wop && workspace && (!noise || (actions && logp)), AURPPO_EINVAL, "%s: null pointer",
                    who);
     AURPPO_REQUIRE(N > 0 && D > 0 && num_layers >= 1 && num_layers <= kLayeredMaxLayers, AURPPO_ESHAPE, "%s: N=%d, D=%d, %d layers (1..%d)",
                    who, N, D, num_layers, kLayeredMaxLayers);
     const int Hp = layered_padded(hidden);             // the planes' and products' width; `hidden` stays the bucket's
-    AURPPO_REQUIRE(layered_width_ok(hidden, anyh) && head_shape_ok(Hp, A, continuous), AURPPO_ESHAPE,
-                   "%s: hidden=%d (%s), A=%d (1..16, Categorical: 2..16)", who, hidden, layered_width_rule(anyh), A);
+    AURPPO_REQUIRE(layered_width_ok(hidden, anyh) && head_shape_ok_upto(Hp, A, continuous, max_a), AURPPO_ESHAPE,
+                   "%s: hidden=%d (%s), A=%d (1..%d, Categorical: 2..%d)", who, hidden, layered_width_rule(anyh), A, max_a, max_a);
     AURPPO_REQUIRE(aligned_to(obs, 16) && aligned_to(wop, 16) && aligned_to(workspace, 64), AURPPO_EINVAL,
                    "%s: obs / operand copies not 16-byte / workspace not 64-byte aligned", who);
     AURPPO_REQUIRE((!noise || (aligned_to(noise, 4) && aligned_to(actions, 4) && aligned_to(logp, 4))) && aligned_to(value, 4),
@@ -221,26 +225,29 @@ int layered_act_impl(const float* obs, const float* noise, int N, int D, int A, 
 }  // namespace
 
 // The entries.  The aurppo_mlp_layered_anyh_* ones take their siblings' argument lists and any hidden width 1 .. 1024; at a multiple of 32
-// both run the same calls.
-#define AURPPO_LAYERED_ACT_ENTRY(NAME, PAIRED, ANYH)                                                                                       \
+// both run the same calls.  The aurppo_mlp_layered_wa_* ones take the anyh entries' argument lists and widths and up to 32 actions; at
+// A <= 16 they run the anyh entries' calls.
+#define AURPPO_LAYERED_ACT_ENTRY(NAME, PAIRED, ANYH, MAX_A)                                                                                \
     extern "C" int NAME(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden, int num_layers,             \
                         const float* params, const int* offsets, int n_params, float* actions, float* logp, float* value, const void* wop, \
                         void* workspace, void* stream) {                                                                                   \
         return layered_act_impl(obs, noise, N, D, A, continuous, hidden, num_layers, params, offsets, n_params, actions, logp, value, wop, \
-                                workspace, stream, PAIRED, ANYH, #NAME);                                                                   \
+                                workspace, stream, PAIRED, ANYH, MAX_A, #NAME);                                                            \
     }
-AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_act_f32, false, false)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_act_f32, false, false, 16)
 // The same step on the small-M products, both nets' layer l in one launch: same arguments, same buffers, same bits, L + 1 launches.
-AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_act_paired_f32, true, false)
-AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_anyh_act_f32, false, true)
-AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_anyh_act_paired_f32, true, true)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_act_paired_f32, true, false, 16)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_anyh_act_f32, false, true, 16)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_anyh_act_paired_f32, true, true, 16)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_wa_act_f32, false, true, 32)
+AURPPO_LAYERED_ACT_ENTRY(aurppo_mlp_layered_wa_act_paired_f32, true, true, 32)
 #undef AURPPO_LAYERED_ACT_ENTRY
 
 namespace {
 
-size_t layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers, bool anyh) {
+size_t layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers, bool anyh, int max_a) {
     if (M <= 0 || D <= 0 || num_layers < 1 || num_layers > kLayeredMaxLayers || !layered_width_ok(hidden, anyh) ||
-        !head_shape_ok(layered_padded(hidden), A, 1))
+        !head_shape_ok_upto(layered_padded(hidden), A, 1, max_a))
         return 0;
     return layered_step_carve(nullptr, M, D, A, hidden, num_layers).bytes;
 }
@@ -250,10 +257,10 @@ int layered_minibatch_impl(const float* obs, const float* actions, const float* 
                            int hidden, int num_layers, float* params, const int* offsets, int n_params, float* grads, double clip,
                            double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq,
                            double max_norm, const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
-                           void* workspace, void* stream, bool anyh, const char* who) {
+                           void* workspace, void* stream, bool anyh, int max_a, const char* who) {
     AURPPO_REQUIRE(exp_avg && exp_avg_sq && lr_dev && step_dev && out_norm, AURPPO_EINVAL, "%s: null optimizer pointer", who);
     if (const int rc = layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads,
-                                         clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, anyh, who))
+                                         clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, anyh, max_a, who))
         return rc;
     const LayeredStepWs w = layered_step_carve(workspace, M, D, A, hidden, num_layers);
     return aurppo_clip_adam_f32(params, grads, exp_avg, exp_avg_sq, n_params, n_params, max_norm, lr_dev, step_dev, beta1, beta2, eps, out_norm,
@@ -263,24 +270,28 @@ int layered_minibatch_impl(const float* obs, const float* actions, const float* 
 }  // namespace
 
 extern "C" size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {
-    return layered_step_workspace_bytes(M, D, A, hidden, num_layers, false);
+    return layered_step_workspace_bytes(M, D, A, hidden, num_layers, false, 16);
 }
 extern "C" size_t aurppo_mlp_layered_anyh_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {
-    return layered_step_workspace_bytes(M, D, A, hidden, num_layers, true);
+    return layered_step_workspace_bytes(M, D, A, hidden, num_layers, true, 16);
+}
+extern "C" size_t aurppo_mlp_layered_wa_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers) {
+    return layered_step_workspace_bytes(M, D, A, hidden, num_layers, true, 32);
 }
 
-#define AURPPO_LAYERED_STEP_ENTRY(NAME, ANYH)                                                                                              \
+#define AURPPO_LAYERED_STEP_ENTRY(NAME, ANYH, MAX_A)                                                                                       \
     extern "C" int NAME(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A, int continuous, \
                         int hidden, int num_layers, const float* params, const int* offsets, int n_params, float* grads, double clip,      \
                         double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, void* workspace, void* stream) { \
         return layered_step_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads, clip,  \
-                                 ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, ANYH, #NAME);                    \
+                                 ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, workspace, stream, ANYH, MAX_A, #NAME);             \
     }
-AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_step_f32, false)
-AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_anyh_step_f32, true)
+AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_step_f32, false, 16)
+AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_anyh_step_f32, true, 16)
+AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_wa_step_f32, true, 32)
 #undef AURPPO_LAYERED_STEP_ENTRY
 
-#define AURPPO_LAYERED_MINIBATCH_ENTRY(NAME, ANYH)                                                                                         \
+#define AURPPO_LAYERED_MINIBATCH_ENTRY(NAME, ANYH, MAX_A)                                                                                  \
     extern "C" int NAME(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A, int continuous, \
                         int hidden, int num_layers, float* params, const int* offsets, int n_params, float* grads, double clip,            \
                         double ent_coef, double vf_coef, int norm_adv, int vloss_mode, float* out_scalars, float* exp_avg,                 \
@@ -288,8 +299,9 @@ AURPPO_LAYERED_STEP_ENTRY(aurppo_mlp_layered_anyh_step_f32, true)
                         float* out_norm, void* workspace, void* stream) {                                                                  \
         return layered_minibatch_impl(obs, actions, rec, idx, M, D, A, continuous, hidden, num_layers, params, offsets, n_params, grads,   \
                                       clip, ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars, exp_avg, exp_avg_sq, max_norm, lr_dev,   \
-                                      step_dev, beta1, beta2, eps, out_norm, workspace, stream, ANYH, #NAME);                              \
+                                      step_dev, beta1, beta2, eps, out_norm, workspace, stream, ANYH, MAX_A, #NAME);                       \
     }
-AURPPO_LAYERED_MINIBATCH_ENTRY(aurppo_mlp_layered_minibatch_f32, false)
-AURPPO_LAYERED_MINIBATCH_ENTRY(aurppo_mlp_layered_anyh_minibatch_f32, true)
+AURPPO_LAYERED_MINIBATCH_ENTRY(aurppo_mlp_layered_minibatch_f32, false, 16)
+AURPPO_LAYERED_MINIBATCH_ENTRY(aurppo_mlp_layered_anyh_minibatch_f32, true, 16)
+AURPPO_LAYERED_MINIBATCH_ENTRY(aurppo_mlp_layered_wa_minibatch_f32, true, 32)
 #undef AURPPO_LAYERED_MINIBATCH_ENTRY

@@ -285,12 +285,13 @@ def ppo_loss(newlogp, newv, entropy, oldlogp, adv, oldv, ret, clip, ent_coef, vf
 MLP_HIDDEN, MLP_MAX_D, MLP_MAX_A = 64, 64, 16
 MLP_WIDE_MAX_HIDDEN, MLP_WIDE_MAX_D, MLP_WIDE_MAX_LAYERS = 128, 128, 3
 MLP_LAYERED_MAX_HIDDEN = 1024
+MLP_LAYERED_MAX_A = 32          # the layered routes' action cap with ``wide_actions``; without it, and for K7 / K7w, MLP_MAX_A
 
 
-def _mlp_structure(policy, bucket):
+def _mlp_structure(policy, bucket, max_a=MLP_MAX_A):
     """(offsets, n_params, D, A, continuous, num_layers, hidden) of the reference's tanh actor-critic inside ``bucket``'s flat
     buffers -- for the actor, then the critic: {w_l, b_l} for l = 0..L (layer L is the head), then actor_logstd -- or None if
-    ``policy`` is not that structure."""
+    ``policy`` is not that structure or has more than ``max_a`` actions."""
     NL, Hd = getattr(policy, "num_layers", None), getattr(policy, "hidden_dim", None)
     if not hasattr(policy, "continuous") or not isinstance(NL, int) or not isinstance(Hd, int) or NL < 1 or Hd < 1:
         return None
@@ -316,19 +317,20 @@ def _mlp_structure(policy, bucket):
                     return None
     except (KeyError, AttributeError, IndexError, TypeError):
         return None
-    if A > MLP_MAX_A or (not cont and A < 2):
+    if A > max_a or (not cont and A < 2):
         return None
     return seq, pos, D, A, cont, NL, Hd
 
 
-def mlp_layout(policy, bucket):
+def mlp_layout(policy, bucket, max_a=MLP_MAX_A):
     """Float offsets of ``policy`` (an ``actor_critic``: ``num_layers`` Tanh layers of ``hidden_dim``, src/nets/nets.py:19-53)
     inside ``bucket``'s flat buffers, or None if no fused kernel is built for its shape.
 
     The default shape (two layers of 64, D <= 64) gets K7/K8's layout {w1,b1,w2,b2,w3,b3} x {actor, critic} + actor_logstd;
     every other shape up to three layers of 128 over D <= 128 gets K7w/K8w's (``wide=True``: {w_l, b_l} for l = 0..L per
-    net, then actor_logstd)."""
-    st = _mlp_structure(policy, bucket)
+    net, then actor_logstd).  ``max_a``: the action count up to which the question is asked (the kernels take ``MLP_MAX_A``;
+    ``mlp_layered_layout`` asks whether a shape would be a fused one but for its actions)."""
+    st = _mlp_structure(policy, bucket, max_a)
     if st is None:
         return None
     seq, pos, D, A, cont, NL, Hd = st
@@ -341,7 +343,7 @@ def mlp_layout(policy, bucket):
     return dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, wide=not fast)
 
 
-def mlp_layered_layout(policy, bucket, any_state=False, any_hidden=False):
+def mlp_layered_layout(policy, bucket, any_state=False, any_hidden=False, wide_actions=False):
     """The layout of ``policy`` for ``mlp_layered_step``, or None.  Eligible: the reference's tanh actor-critic that no fused
     kernel covers (``mlp_layout`` is None), one or more layers of ``hidden_dim`` a multiple of 32 up to 1024, at most 16 actions,
     and a state of a multiple of 16 floats -- or, with ``any_state=True``, of any width (Hopper's 11, HalfCheetah's 17, Humanoid's
@@ -350,11 +352,15 @@ def mlp_layered_layout(policy, bucket, any_state=False, any_hidden=False):
     ``any_hidden=True``: any ``hidden_dim`` in 1..1024 (200, 300, 400, 500; 100 over Humanoid's state).  A width that is no multiple
     of 32 gives the same dict -- the unpadded policy's offsets and ``n_params`` -- plus ``ragged_hidden=True``: the native calls
     (``mlp_layered_step_native``, ``mlp_layered_minibatch``, ``mlp_layered_prepare``, ``mlp_layered_act``) then run the policy at the
-    width rounded up to 32 through the library's ``anyh`` entries (csrc/layered.hip); the per-product route refuses it."""
+    width rounded up to 32 through the library's ``anyh`` entries (csrc/layered.hip); the per-product route refuses it.
+    ``wide_actions=True``: up to 32 actions (Humanoid's 17, the dexterous hands' 20 - 30, a Categorical head of 17 - 32 choices).  A
+    policy with 17 .. 32 actions gives the same dict plus ``wide_actions=True``: the native calls, ``head_ppo`` and ``head_act`` then go
+    through the library's ``wa`` entries (K13 / K14 with 32-long per-action arrays, csrc/head.hip); the per-product route refuses it.  A
+    policy with at most 16 actions gets the dict it gets without the keyword.  The state and hidden rules follow their own keywords."""
     if mlp_layout(policy, bucket) is not None:
         return None
-    st = _mlp_structure(policy, bucket)
-    if st is None:
+    st = _mlp_structure(policy, bucket, MLP_LAYERED_MAX_A if wide_actions else MLP_MAX_A)
+    if st is None or mlp_layout(policy, bucket, MLP_LAYERED_MAX_A) is not None:      # a fused shape stays the fused kernels', at any A
         return None
     seq, pos, D, A, cont, NL, Hd = st
     if (Hd % 32 != 0 and not any_hidden) or Hd > MLP_LAYERED_MAX_HIDDEN or (D % 16 != 0 and not any_state):
@@ -362,24 +368,51 @@ def mlp_layered_layout(policy, bucket, any_state=False, any_hidden=False):
     lay = dict(offsets=seq, n_params=pos, D=D, A=A, continuous=cont, hidden=Hd, num_layers=NL, layered=True)
     if Hd % 32 != 0:
         lay["ragged_hidden"] = True
+    if A > MLP_MAX_A:
+        lay["wide_actions"] = True
     return lay
+
+
+# what does not depend on the action count has no ``wa`` entry: a wide-action layout takes the ``anyh`` one (any hidden width)
+_LAYERED_NO_WA = ("wop_bytes", "prep_f32", "act_workspace_bytes")
 
 
 def _layered_entry(lib, layout, name):
     """(function, its name) of the layered entry ``aurppo_mlp_layered_<name>`` for ``layout``: the ``anyh`` sibling where the hidden
-    width is no multiple of 32, with the same arguments in the same order."""
-    entry = ("aurppo_mlp_layered_anyh_" if layout.get("ragged_hidden") else "aurppo_mlp_layered_") + name
+    width is no multiple of 32, the ``wa`` sibling (any hidden width too) where the policy has more than 16 actions, with the same
+    arguments in the same order."""
+    if layout.get("wide_actions"):
+        family = "anyh_" if name in _LAYERED_NO_WA else "wa_"
+    else:
+        family = "anyh_" if layout.get("ragged_hidden") else ""
+    entry = "aurppo_mlp_layered_" + family + name
+    return getattr(lib, entry), entry
+
+
+def _head_entry(lib, layout, name):
+    """(function, its name) of K13 / K14's entry ``aurppo_head_<kernel>_<rest>`` (``name``: ``ppo_f32``, ``ppo_workspace_bytes``,
+    ``act_f32``): the ``wa`` sibling ``aurppo_head_<kernel>_wa_<rest>`` for a wide-action layout."""
+    kernel, rest = name.split("_", 1)
+    entry = f"aurppo_head_{kernel}_{'wa_' if layout.get('wide_actions') else ''}{rest}"
     return getattr(lib, entry), entry
 
 
 def _layered_ws_kind(kind, layout):
-    """The workspace's cache key: a ragged hidden width keeps a buffer of its own per width (200 and 224 share none)."""
-    return f"{kind}_h{layout['hidden']}" if layout.get("ragged_hidden") else kind
+    """The workspace's cache key: a ragged hidden width keeps a buffer of its own per width (200 and 224 share none), and so does a
+    wide-action layout, whose entries are another family's."""
+    key = f"{kind}_h{layout['hidden']}" if layout.get("ragged_hidden") else kind
+    return f"{key}_wa" if layout.get("wide_actions") else key
 
 
 def _refuse_ragged_hidden(who, layout):
     if layout.get("ragged_hidden"):
         raise ValueError(f"{who}: a hidden width of {layout['hidden']} (no multiple of 32) runs through mlp_layered_step_native / "
+                         f"mlp_layered_minibatch / mlp_layered_act only")
+
+
+def _refuse_wide_actions(who, layout):
+    if layout.get("wide_actions"):
+        raise ValueError(f"{who}: a policy with {layout['A']} actions (more than {MLP_MAX_A}) runs through mlp_layered_step_native / "
                          f"mlp_layered_minibatch / mlp_layered_act only")
 
 
@@ -1312,14 +1345,15 @@ def head_ppo(hA, hC, actions, rec, idx, flat_param, layout, flat_grad, clip, ent
     _bucket_fits(n, flat_param, flat_grad, who="head_ppo")
     if out_scalars is None:
         out_scalars = torch.empty(N_SCALARS, dtype=torch.float32, device=hA.device)
-    nb = lib.aurppo_head_ppo_workspace_bytes(M, Hd, A)
+    fn, entry = _head_entry(lib, layout, "ppo_f32")
+    nb = _head_entry(lib, layout, "ppo_workspace_bytes")[0](M, Hd, A)
     if nb == 0:
-        raise RuntimeError("aur_ppo_amd: aurppo_head_ppo_f32 does not take this shape")
+        raise RuntimeError(f"aur_ppo_amd: {entry} does not take this shape")
     ws = _workspace("head", nb, hA.device)
     lay = (C.c_int * 7)(*head_layout(layout))
-    _check(lib.aurppo_head_ppo_f32(
+    _check(fn(
         *_step_prefix((hA, hC, gzA, gzC), actions, rec, idx, (M, Hd, A, int(layout["continuous"])), flat_param, lay, n, flat_grad, clip,
-                      ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars), *_ws_stream(ws)), "aurppo_head_ppo_f32")
+                      ent_coef, vf_coef, norm_adv, vloss_mode, out_scalars), *_ws_stream(ws)), entry)
     return out_scalars
 
 
@@ -1347,6 +1381,7 @@ def mlp_layered_step(obs, actions, rec, idx, flat_param, layout, flat_grad, clip
     gradient (a column sum)."""
     lib = _lib_or_raise()
     _refuse_ragged_hidden("mlp_layered_step", layout)
+    _refuse_wide_actions("mlp_layered_step", layout)
     M, D, Hd, L, n = idx.numel(), layout["D"], layout["hidden"], layout["num_layers"], layout["n_params"]
     if not layout.get("layered") or not _mlp_buffers_ok(obs, actions, rec, layout):
         raise ValueError("mlp_layered_step: buffer shapes do not match the policy")
@@ -1465,9 +1500,9 @@ def head_act(hA, hC, noise, flat_param, layout, actions=None, logp=None, value=N
     actions, logp, value = _act_outputs("head_act", N, layout, noise, actions, logp, value, hC.device)
     _bucket_fits(layout["n_params"], flat_param, who="head_act")
     lay = (C.c_int * 5)(*head_act_layout(layout))
-    _check(lib.aurppo_head_act_f32(_optr(hA if noise is not None else None), _ptr(hC), _optr(noise), N, Hd, layout["A"],
-                                   int(layout["continuous"]), _ptr(flat_param), lay, layout["n_params"],
-                                   *_act_outputs_ptrs(noise, actions, logp, value), _stream()), "aurppo_head_act_f32")
+    fn, entry = _head_entry(lib, layout, "act_f32")
+    _check(fn(_optr(hA if noise is not None else None), _ptr(hC), _optr(noise), N, Hd, layout["A"], int(layout["continuous"]),
+              _ptr(flat_param), lay, layout["n_params"], *_act_outputs_ptrs(noise, actions, logp, value), _stream()), entry)
     return actions, logp, value
 
 

@@ -63,14 +63,24 @@ LAYERED_ACT_DEFAULT = "0"       # AURPPO_LAYERED_ACT when the environment does n
 LAYERED_NATIVE_DEFAULT = "0"    # AURPPO_LAYERED_NATIVE when the environment does not set it
 LAYERED_ACT_PAIRED_DEFAULT = "0"    # AURPPO_LAYERED_ACT_PAIRED when the environment does not set it
 LAYERED_ANY_HIDDEN_DEFAULT = "0"    # AURPPO_LAYERED_ANY_HIDDEN when the environment does not set it
+LAYERED_WIDE_ACTIONS_DEFAULT = "0"  # AURPPO_LAYERED_WIDE_ACTIONS when the environment does not set it
 
 
 def _layered_layout(ops, policy, bucket):
     """The layered layout of ``policy``, called only where AURPPO_LAYERED_STEP / AURPPO_LAYERED_ACT is on.  AURPPO_LAYERED_ANY_HIDDEN=1
-    (opt-in, read only here): hidden widths that are no multiple of 32 too (``ragged_hidden`` layouts: the native calls only)."""
+    (opt-in, read only here): hidden widths that are no multiple of 32 too (``ragged_hidden`` layouts: the native calls only).
+    AURPPO_LAYERED_WIDE_ACTIONS=1 (opt-in, read only here): 17 .. 32 actions too (``wide_actions`` layouts: the native calls only)."""
+    more = {}
     if os.environ.get("AURPPO_LAYERED_ANY_HIDDEN", LAYERED_ANY_HIDDEN_DEFAULT) != "0":
-        return ops.mlp_layered_layout(policy, bucket, any_state=True, any_hidden=True)
-    return ops.mlp_layered_layout(policy, bucket, any_state=True)
+        more["any_hidden"] = True
+    if os.environ.get("AURPPO_LAYERED_WIDE_ACTIONS", LAYERED_WIDE_ACTIONS_DEFAULT) != "0":
+        more["wide_actions"] = True
+    return ops.mlp_layered_layout(policy, bucket, any_state=True, **more)
+
+
+def _native_only(layout):
+    """A layered layout that only the native calls take: a ragged hidden width, or more than 16 actions."""
+    return bool(layout.get("ragged_hidden") or layout.get("wide_actions"))
 
 
 def _layered_act_paired(act_layout):
@@ -498,13 +508,13 @@ class ppo(FlatAdamMixin):
             return "halves_p2p" if self._p2p is not None else "halves_allreduce"
         if packed and self._mlp is not None:
             return "fused_step"         # one fused launch: rows are read through the permutation, gradients land in the bucket
-        if packed and self._mlp_layered is not None and (self._layered_native or self._mlp_layered.get("ragged_hidden")):
-            # the native layered step (a ragged hidden width has no other, whatever AURPPO_LAYERED_NATIVE says); clip + Adam ride in
+        if packed and self._mlp_layered is not None and (self._layered_native or _native_only(self._mlp_layered)):
+            # the native layered step (a ragged hidden width or 17+ actions have no other, whatever AURPPO_LAYERED_NATIVE says); clip + Adam ride in
             # the same call where nothing has to happen between the two
             if (not self._dp and self._fused_adam and self.bucket.numel == self._mlp_layered["n_params"]
                     and hasattr(ops, "mlp_layered_minibatch")):
                 return "layered_minibatch"
-            if hasattr(ops, "mlp_layered_step_native") or self._mlp_layered.get("ragged_hidden"):
+            if hasattr(ops, "mlp_layered_step_native") or _native_only(self._mlp_layered):
                 return "layered_native_step"
         if packed and self._mlp_layered is not None:
             return "layered_step"       # rows through the permutation in the first product, the loss behind the last one

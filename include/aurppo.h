@@ -375,7 +375,8 @@ int aurppo_linear_wgrad_bias_f32(const float* dy, const float* x, const int32_t*
  *     actor's last hidden layer, bias of the critic's}.  Written in grads: both heads' weight and bias gradients, the
  *     actor_logstd gradient, and the two last-hidden-layer bias gradients (the column sums of gz); nothing else.
  *   out_scalars: the 9 floats of AURPPO_S_*.   workspace: aurppo_head_ppo_workspace_bytes(M, H, A) bytes, 64-byte aligned.
- * Limits (AURPPO_ESHAPE otherwise): H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16; packed records A <= 12). */
+ * Limits (AURPPO_ESHAPE otherwise): H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16; packed records A <= 12; up to 32
+ * actions: aurppo_head_ppo_wa_f32 below). */
 size_t aurppo_head_ppo_workspace_bytes(int M, int H, int A);
 int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
                         const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
@@ -406,7 +407,7 @@ int aurppo_head_ppo_f32(const float* hA, const float* hC, float* gzA, float* gzC
  *     actor_logstd (ignored for the Categorical head)}.
  * Limits (AURPPO_ESHAPE otherwise): hidden / H a multiple of 32 in 32..1024, A in 1..16 (Categorical 2..16), any D >= 1 (no
  * multiple of 16: layer 0 on the tail builds of aurppo_linear_f32, its operand copy padded with zero planes to whole 16-column
- * steps; obs rows then need 4-byte alignment only, the base still 16), num_layers 1..16. */
+ * steps; obs rows then need 4-byte alignment only, the base still 16), num_layers 1..16.  Up to 32 actions: the wa entries below. */
 size_t aurppo_mlp_layered_wop_bytes(int D, int hidden, int num_layers);
 int aurppo_mlp_layered_prep_f32(const float* params, const int* offsets, int n_params, int D, int hidden, int num_layers, void* wop,
                                 void* stream);
@@ -440,7 +441,7 @@ int aurppo_head_act_f32(const float* hA, const float* hC, const float* noise, in
  *     the same stream -- src/ppo.py:219-269 -- with the same bits in params, moments, step count and norm as the two calls in turn.
  *     Single process only: nothing all-reduces the gradient in between.
  * Limits (AURPPO_ESHAPE before any launch otherwise): M >= 1, any D >= 1, hidden a multiple of 32 in 32..1024, A in 1..16
- * (Categorical 2..16; packed records A <= 12), num_layers 1..16. */
+ * (Categorical 2..16; packed records A <= 12), num_layers 1..16.  Up to 32 actions: the wa entries below. */
 size_t aurppo_mlp_layered_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers);
 int aurppo_mlp_layered_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
                                 int continuous, int hidden, int num_layers, const float* params, const int* offsets, int n_params,
@@ -486,6 +487,43 @@ int aurppo_mlp_layered_anyh_minibatch_f32(const float* obs, const float* actions
                                           int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
                                           const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
                                           void* workspace, void* stream);
+
+/* ---- K13, K14 and the layered steps with up to 32 actions ---------------------------------------------------------------------
+ * The entries above refuse more than 16 actions (Humanoid's 17, the dexterous hands' 20 - 30, a Categorical head of 17 - 32
+ * choices).  Each `wa` (wide action head) entry below takes the argument list of the sibling named, unchanged, and the same checks,
+ * with A in 1..32 (Categorical 2..32).  A in 17..32 runs K13 / K14's builds with 32-long per-action arrays (the head weights in
+ * LDS: up to 33 x 1024 floats); A <= 16 runs the very kernels the sibling runs: same bits, same workspace bytes.
+ *   aurppo_head_ppo_wa_workspace_bytes / aurppo_head_ppo_wa_f32 / aurppo_head_act_wa_f32: as aurppo_head_ppo_workspace_bytes /
+ *     aurppo_head_ppo_f32 / aurppo_head_act_f32 (H a multiple of 32 in 32..1024).
+ *   aurppo_mlp_layered_wa_*: as aurppo_mlp_layered_anyh_* -- any hidden width in 1..1024, so the two widenings compose.  The operand
+ *     copies and the rollout workspace do not depend on A: use aurppo_mlp_layered_anyh_wop_bytes / _prep_f32 / _act_workspace_bytes.
+ * Limits (AURPPO_ESHAPE before any launch otherwise, the message names A=<n>): A in 1..32 (Categorical 2..32); packed records hold
+ * at most 12 action floats, so a Gaussian head with A > 12 needs `actions`; everything else as the sibling's. */
+size_t aurppo_head_ppo_wa_workspace_bytes(int M, int H, int A);
+int aurppo_head_ppo_wa_f32(const float* hA, const float* hC, float* gzA, float* gzC, const float* actions, const float* rec,
+                           const int32_t* idx, int M, int H, int A, int continuous, const float* params, const int* layout_h,
+                           int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
+                           float* out_scalars, void* workspace, void* stream);
+int aurppo_head_act_wa_f32(const float* hA, const float* hC, const float* noise, int N, int H, int A, int continuous,
+                           const float* params, const int* layout_h, int n_params, float* actions, float* logp, float* value,
+                           void* stream);
+size_t aurppo_mlp_layered_wa_step_workspace_bytes(int M, int D, int A, int hidden, int num_layers);
+int aurppo_mlp_layered_wa_step_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D, int A,
+                                   int continuous, int hidden, int num_layers, const float* params, const int* offsets, int n_params,
+                                   float* grads, double clip, double ent_coef, double vf_coef, int norm_adv, int vloss_mode,
+                                   float* out_scalars, void* workspace, void* stream);
+int aurppo_mlp_layered_wa_minibatch_f32(const float* obs, const float* actions, const float* rec, const int32_t* idx, int M, int D,
+                                        int A, int continuous, int hidden, int num_layers, float* params, const int* offsets,
+                                        int n_params, float* grads, double clip, double ent_coef, double vf_coef, int norm_adv,
+                                        int vloss_mode, float* out_scalars, float* exp_avg, float* exp_avg_sq, double max_norm,
+                                        const float* lr_dev, float* step_dev, double beta1, double beta2, double eps, float* out_norm,
+                                        void* workspace, void* stream);
+int aurppo_mlp_layered_wa_act_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                  int num_layers, const float* params, const int* offsets, int n_params, float* actions, float* logp,
+                                  float* value, const void* wop, void* workspace, void* stream);
+int aurppo_mlp_layered_wa_act_paired_f32(const float* obs, const float* noise, int N, int D, int A, int continuous, int hidden,
+                                         int num_layers, const float* params, const int* offsets, int n_params, float* actions,
+                                         float* logp, float* value, const void* wop, void* workspace, void* stream);
 
 /* K12 -- the weight gradient of the 3x3 convolution of aurppo_conv3x3_f32 (src/nets/base_cnns.py:32-45, src/nets/equiv.py:12-62;
  * what loss.backward() leaves in <conv>.weight.grad, src/robot_ppo.py:389): dw (Co, Ci, 3, 3) from x (B, Ci, H, W) and the
