@@ -39,6 +39,7 @@ SYMBOLS = (
     "aurppo_head_ppo_wa_workspace_bytes", "aurppo_head_ppo_wa_f32", "aurppo_head_act_wa_f32",
     "aurppo_mlp_layered_wa_step_workspace_bytes", "aurppo_mlp_layered_wa_step_f32", "aurppo_mlp_layered_wa_minibatch_f32",
     "aurppo_mlp_layered_wa_act_f32", "aurppo_mlp_layered_wa_act_paired_f32",
+    "aurppo_cartpole_reset", "aurppo_cartpole_step", "aurppo_cartpole_rollout_f32",
 )
 
 _lib = None
@@ -179,6 +180,14 @@ def _declare(lib):
     lib.aurppo_mlp_wide_ppo_step_f32.argtypes = step_prefix(2) + ws_stream + [vp, vp]
     lib.aurppo_mlp_wide_ppo_minibatch_f32.argtypes = step_prefix(2) + adam_tail + next_pair + [i32] + ws_stream
     lib.aurppo_mlp_wide_act_f32.argtypes = [vp, vp] + [i32] * 6 + [vp, pi32, i32, vp, vp, vp] + ws_stream
+    # K15, K16: the device CartPole and the one-launch rollout on it
+    cart_env = [vp, vp, vp]                                 # state, steps, episode
+    cart_seed = [i32, u32, u32]                             # env0, seed_lo, seed_hi
+    cart_consts = [f64] * 8 + [i32]                         # gravity, masscart, masspole, length, force_mag, tau, theta_lim, x_lim, max_steps
+    lib.aurppo_cartpole_reset.argtypes = cart_env + [vp, i32] + cart_seed + [vp]
+    lib.aurppo_cartpole_step.argtypes = cart_env + [vp] * 5 + [i32] + cart_seed + cart_consts + [vp]
+    lib.aurppo_cartpole_rollout_f32.argtypes = (cart_env + [vp] * 3 + [i32] * 7 + [vp, pi32, i32] + [vp] * 7 + cart_seed + cart_consts
+                                                + [vp])
     # K6, K6b
     lib.aurppo_clip_workspace_bytes.argtypes = [i64]
     lib.aurppo_grad_norm_clip_f32.argtypes = [vp, i64, f64, vp] + ws_stream

@@ -1,6 +1,6 @@
 """Vector environments for the trainer.  The reference steps ``gym.vector.SyncVectorEnv`` on the
 host every rollout step (src/ppo.py:66-68,110); gym is not part of this image, and the BASELINE
-metric is defined on synthetic rollout tensors, so two built-ins are provided behind the same
+metric is defined on synthetic rollout tensors, so these built-ins are provided behind the same
 ``reset(seed=) -> (obs, info)`` / ``step(a) -> (obs, rew, done, trunc, info)`` interface:
 
 * ``SyntheticVecEnv`` -- device-resident N(0,1) observations / rewards, Bernoulli terminals
@@ -8,10 +8,14 @@ metric is defined on synthetic rollout tensors, so two built-ins are provided be
 * ``CartPoleVecEnv``  -- CartPole-v1 dynamics (Barto-Sutton-Anderson cart-pole as in gym's
   classic_control: Euler, tau 0.02, 12 deg / 2.4 m limits, 500-step truncation) with auto-reset
   and ``final_info`` episode statistics, for the plumbing config.
+* ``CartPoleDeviceVecEnv`` -- the same env as a HIP kernel on state kept on the device (csrc/cartpole.hip), opt-in
+  (``params["device_env"]`` / AURPPO_DEVICE_ENV=1): ``device_native`` and ``capturable``, and with the default
+  2 x 64 policy the trainer runs a whole rollout on it as one launch (``hip_ops.cartpole_rollout``).
 """
 from __future__ import annotations
 
 import math
+import os
 import types
 
 import numpy as np
@@ -113,15 +117,136 @@ class CartPoleVecEnv:
         pass
 
 
+class CartPoleDeviceVecEnv:
+    """``CartPoleVecEnv`` on the device (csrc/cartpole.hip): the same dynamics, limits, 500-step truncation and auto-reset in fp64,
+    one thread per env, behind the same ``reset`` / ``step`` interface.  What differs: resets draw from Philox4x32-10 on (seed, global
+    env index, episode number) instead of numpy's ``RandomState`` (so a reset does not depend on how a rollout is cut into launches),
+    and finished episodes are not reported through ``info`` but as rows of an int32 table -- ``begin_rollout(T)`` opens a (T, N)
+    table, every ``step()`` fills its next row with the lengths of the episodes that ended in it (0 elsewhere; CartPole's return is
+    its length), ``episode_triples`` reads it once per rollout.  There is no CPU fallback."""
+    device_native = True
+    capturable = True          # step() is one kernel launch into rows fixed at capture time
+    takes_float_actions = True  # step() reads K8's fp32 0.0 / 1.0 action row as it is
+
+    def __init__(self, num_envs, device, seed=0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("CartPoleDeviceVecEnv needs a gfx950 GPU: the env's HIP kernels have no CPU fallback")
+        self.num_envs = int(num_envs)
+        self.single_observation_space = _Space((4,))
+        self.single_action_space = _Space((), 2)
+        self.seed, self.env0 = int(seed), 0
+        self.state = torch.zeros((self.num_envs, 4), dtype=torch.float64, device=self.device)
+        self.steps = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.episode = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.ep_len = None         # (T, N) int32, see begin_rollout
+        self._row = 0
+        self._spare_row = None     # where a step() outside a rollout's table leaves its lengths
+        self.reset()
+
+    def native_state(self):
+        """What the ``hip_ops.cartpole_*`` calls take as ``env_state``."""
+        C = CartPoleVecEnv
+        return dict(state=self.state, steps=self.steps, episode=self.episode, seed=self.seed, env0=self.env0,
+                    consts=(C.gravity, C.masscart, C.masspole, C.length, C.force_mag, C.tau, C.theta_lim, C.x_lim, C.max_steps))
+
+    def generators(self):
+        return []
+
+    def reset(self, seed=None):
+        """``seed``: an int (the key of every draw from here on), or the trainer's list of consecutive per-env seeds, whose first
+        becomes the global index of env 0 (a rank's shard then draws what the same envs draw in a single process)."""
+        if isinstance(seed, (list, tuple)):
+            seeds = [int(s) for s in seed]
+            if len(seeds) != self.num_envs or any(b - a != 1 for a, b in zip(seeds, seeds[1:])) or seeds[0] < 0:
+                raise ValueError("CartPoleDeviceVecEnv.reset: a seed list must hold num_envs consecutive non-negative integers")
+            self.env0 = seeds[0]
+        elif seed is not None:
+            self.seed = int(seed)
+        from . import hip_ops
+        obs = torch.empty((self.num_envs, 4), dtype=torch.float32, device=self.device)
+        hip_ops.cartpole_reset(self.native_state(), obs)
+        return obs, {}
+
+    def begin_rollout(self, num_steps, clear=True):
+        """Open the (num_steps, N) episode-length table (allocated once per size) and point the next ``step()`` at its row 0."""
+        if self.ep_len is None or tuple(self.ep_len.shape) != (int(num_steps), self.num_envs):
+            self.ep_len = torch.zeros((int(num_steps), self.num_envs), dtype=torch.int32, device=self.device)
+        elif clear:
+            self.ep_len.zero_()
+        self._row = 0
+        return self.ep_len
+
+    def step(self, action):
+        from . import hip_ops
+        a = action.to(self.device).reshape(-1)
+        if a.dtype != torch.float32:
+            a = a.float()
+        if self.ep_len is not None and self._row < self.ep_len.shape[0]:
+            row = self.ep_len[self._row]
+            self._row += 1
+        else:
+            if self._spare_row is None:
+                self._spare_row = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            row = self._spare_row
+        obs = torch.empty((self.num_envs, 4), dtype=torch.float32, device=self.device)
+        reward = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
+        done = torch.empty(self.num_envs, dtype=torch.float32, device=self.device)
+        hip_ops.cartpole_step(self.native_state(), a.contiguous(), obs, reward, done, row)
+        return obs, reward, done, None, {}
+
+    def set_state(self, state64, steps):
+        """Overwrite every env's state (N, 4) and step count (N,), for tests and checkpoints; returns the observation."""
+        st = torch.as_tensor(np.asarray(state64.cpu() if isinstance(state64, torch.Tensor) else state64), dtype=torch.float64)
+        sp = torch.as_tensor(np.asarray(steps.cpu() if isinstance(steps, torch.Tensor) else steps)).to(torch.int32)
+        if tuple(st.shape) != (self.num_envs, 4) or tuple(sp.shape) != (self.num_envs,):
+            raise ValueError("CartPoleDeviceVecEnv.set_state: state must be (num_envs, 4) and steps (num_envs,)")
+        self.state.copy_(st)
+        self.steps.copy_(sp)
+        return self.state.float()
+
+    def get_state(self):
+        """(state (N, 4) float64, steps (N,), episode (N,)) as numpy arrays."""
+        return self.state.cpu().numpy(), self.steps.cpu().numpy(), self.episode.cpu().numpy()
+
+    def close(self):
+        pass
+
+
+def episode_rows(ep_len):
+    """Per row t of an episode-length table (T, N): the length recorded by the LOWEST env index with ``ep_len > 0``, or 0 -- the
+    reference logs the first finished env of a step and breaks (src/ppo.py:114-123).  Pure torch, any device; returns (T,) int64."""
+    T, N = ep_len.shape
+    cols = torch.arange(N, device=ep_len.device).expand(T, N)
+    first = torch.where(ep_len > 0, cols, torch.full_like(cols, N)).min(dim=1).values
+    picked = ep_len.gather(1, first.clamp(max=N - 1).view(T, 1)).view(T).to(torch.int64)
+    return torch.where(first < N, picked, torch.zeros_like(picked))
+
+
+def episode_triples(ep_len, global_step, step_stride):
+    """The ``(return, length, global_step)`` triples a rollout's table stands for, in step order: row t was filled at global step
+    ``global_step + (t + 1) * step_stride``.  One host read."""
+    rows = episode_rows(ep_len).cpu().tolist()
+    return [(float(l), int(l), int(global_step + (t + 1) * step_stride)) for t, l in enumerate(rows) if l > 0]
+
+
+def device_env_wanted(params):
+    """The opt-in switch of the device CartPole: ``params["device_env"]`` or AURPPO_DEVICE_ENV=1."""
+    return bool(params.get("device_env", False)) or os.environ.get("AURPPO_DEVICE_ENV", "0") not in ("", "0")
+
+
 def make_vec_env(gym_id, num_envs, continuous, device, params):
     """Synthetic-* ids -> SyntheticVecEnv (obs_dim/act_dim from params, defaults 64/6 continuous,
     4/2 discrete); otherwise gym's SyncVectorEnv when gym is importable (same wrappers as
-    src/ppo.py:85-99), else the built-in CartPole for 'CartPole-v1'."""
+    src/ppo.py:85-99), else the built-in CartPole for 'CartPole-v1'.  With the device-env switch on
+    (``device_env_wanted``) and a CUDA device, 'CartPole-v1' is ``CartPoleDeviceVecEnv``."""
     if str(gym_id).lower().startswith("synthetic"):
         obs_dim = params.get("obs_dim", 64 if continuous else 4)
         act_dim = params.get("act_dim", 6 if continuous else 2)
         return SyntheticVecEnv(num_envs, obs_dim, act_dim, continuous, device,
                                seed=int(params.get("env_seed", 1234)) + int(params.get("rank", 0)))
+    if gym_id == "CartPole-v1" and device_env_wanted(params) and torch.device(device).type == "cuda":
+        return CartPoleDeviceVecEnv(num_envs, device, seed=int(params.get("env_seed", 0)))
     try:
         import gym  # noqa: F401
     except ImportError:

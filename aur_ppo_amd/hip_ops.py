@@ -1562,3 +1562,105 @@ def mlp_layered_act(obs, noise, flat_param, layout, actions=None, logp=None, val
     _check(fn(_ptr(obs), _optr(noise), *shape, _ptr(flat_param), lay, layout["n_params"], *_act_outputs_ptrs(noise, actions, logp, value),
               C.c_void_p(wop.data_ptr()), *_ws_stream(ws)), entry)
     return actions, logp, value
+
+
+# ------------------------------------------------------------------ K15 / K16: the device CartPole and the one-launch rollout on it
+# ``env_state``: what ``envs.CartPoleDeviceVecEnv.native_state()`` returns -- ``state`` (N, 4) float64, ``steps`` / ``episode`` (N,) int32,
+# ``seed``, ``env0`` (the global index of env 0) and ``consts`` (gravity, masscart, masspole, length, force_mag, tau, theta_lim, x_lim,
+# max_steps).  Shapes and dtypes are checked (ValueError) before the library is reached.
+def _cart_tensor(who, name, t, shape, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
+def _cart_env(who, env_state):
+    """N after the env-state checks."""
+    steps = env_state["steps"]
+    N = steps.numel() if isinstance(steps, torch.Tensor) else 0
+    if N < 1:
+        raise ValueError(f"{who}: no envs")
+    _cart_tensor(who, "state", env_state["state"], (N, 4), torch.float64)
+    _cart_tensor(who, "steps", steps, (N,), torch.int32)
+    _cart_tensor(who, "episode", env_state["episode"], (N,), torch.int32)
+    if len(env_state["consts"]) != 9 or int(env_state["env0"]) < 0:
+        raise ValueError(f"{who}: consts must be the nine CartPole constants and env0 >= 0")
+    return N
+
+
+def _cart_env_ptrs(env_state):
+    """state, steps, episode."""
+    return (_ptr(env_state["state"], torch.float64), _ptr(env_state["steps"], torch.int32), _ptr(env_state["episode"], torch.int32))
+
+
+def _cart_seed(env_state):
+    """env0, seed_lo, seed_hi."""
+    seed = int(env_state["seed"]) & 0xFFFFFFFFFFFFFFFF
+    return (int(env_state["env0"]), seed & 0xFFFFFFFF, seed >> 32)
+
+
+def _cart_consts(env_state):
+    """gravity, masscart, masspole, length, force_mag, tau, theta_lim, x_lim, max_steps."""
+    c = env_state["consts"]
+    return (*[float(v) for v in c[:8]], int(c[8]))
+
+
+def cartpole_reset(env_state, obs):
+    """Episode 0 of every env: ``episode = steps = 0``, the state from the reset draw, ``obs`` (N, 4) = the state in fp32."""
+    N = _cart_env("cartpole_reset", env_state)
+    _cart_tensor("cartpole_reset", "obs", obs, (N, 4))
+    lib = _lib_or_raise()
+    _check(lib.aurppo_cartpole_reset(*_cart_env_ptrs(env_state), _ptr(obs), N, *_cart_seed(env_state), _stream()), "aurppo_cartpole_reset")
+    return obs
+
+
+def cartpole_step(env_state, action, obs, reward, done, ep_len):
+    """K15: one step of every env.  ``action`` (N,) fp32 0.0 / 1.0 (as K8 writes it); writes ``obs`` (N, 4) (the reset observation where
+    the episode ended), ``reward`` = 1, ``done`` 0.0 / 1.0 and ``ep_len`` (N,) int32: the finished episode's length, or 0."""
+    who = "cartpole_step"
+    N = _cart_env(who, env_state)
+    _cart_tensor(who, "action", action, (N,))
+    _cart_tensor(who, "obs", obs, (N, 4))
+    _cart_tensor(who, "reward", reward, (N,))
+    _cart_tensor(who, "done", done, (N,))
+    _cart_tensor(who, "ep_len", ep_len, (N,), torch.int32)
+    lib = _lib_or_raise()
+    _check(lib.aurppo_cartpole_step(*_cart_env_ptrs(env_state), _ptr(action), _ptr(obs), _ptr(reward), _ptr(done), _ptr(ep_len, torch.int32),
+                                    N, *_cart_seed(env_state), *_cart_consts(env_state), _stream()), "aurppo_cartpole_step")
+    return obs, reward, done, ep_len
+
+
+def cartpole_rollout_ok(layout):
+    """K16's shape rule: K8's default layout (two layers of 64) with a Categorical head of 2 over CartPole's 4 floats."""
+    return bool(layout is not None and not layout.get("wide") and not layout.get("layered") and not layout["continuous"]
+                and layout["D"] == 4 and layout["A"] == 2 and layout["hidden"] == MLP_HIDDEN and layout["num_layers"] == 2)
+
+
+def cartpole_rollout(env_state, flat_param, layout, noise, states, terminals, actions, log_probs, values, rewards, ep_len, next_obs,
+                     next_done):
+    """K16: T rollout steps in one launch -- per step t what ``mlp_act`` on ``noise[t]`` and ``cartpole_step`` leave, bit for bit, in
+    the buffer rows ``states[t]`` (N, 4), ``terminals[t]``, ``actions[t]``, ``log_probs[t]``, ``values[t]``, ``rewards[t]`` and
+    ``ep_len[t]`` (int32).  ``next_obs`` (N, 4) / ``next_done`` (N,) are read and written: on entry the current observation and done
+    flag, on exit those behind the last step.  The env state is updated in place.  A policy shape other than ``cartpole_rollout_ok``'s
+    is refused by the library (RuntimeError)."""
+    who = "cartpole_rollout"
+    N = _cart_env(who, env_state)
+    if not isinstance(noise, torch.Tensor) or noise.dim() != 2 or noise.shape[0] < 1:
+        raise ValueError(f"{who}: noise must be (T, N) uniform draws")
+    T = noise.shape[0]
+    _cart_tensor(who, "noise", noise, (T, N))
+    _cart_tensor(who, "states", states, (T, N, 4))
+    for name, t in (("terminals", terminals), ("actions", actions), ("log_probs", log_probs), ("values", values), ("rewards", rewards)):
+        _cart_tensor(who, name, t, (T, N))
+    _cart_tensor(who, "ep_len", ep_len, (T, N), torch.int32)
+    _cart_tensor(who, "next_obs", next_obs, (N, 4))
+    _cart_tensor(who, "next_done", next_done, (N,))
+    _bucket_fits(layout["n_params"], flat_param, who=who)
+    lib = _lib_or_raise()
+    lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
+    _check(lib.aurppo_cartpole_rollout_f32(*_cart_env_ptrs(env_state), _ptr(next_obs), _ptr(next_done), _ptr(noise), N, T, layout["D"],
+                                           layout["A"], int(layout["continuous"]), layout["hidden"], layout["num_layers"], _ptr(flat_param),
+                                           lay, layout["n_params"], _ptr(states), _ptr(terminals), _ptr(actions), _ptr(log_probs),
+                                           _ptr(values), _ptr(rewards), _ptr(ep_len, torch.int32), *_cart_seed(env_state),
+                                           *_cart_consts(env_state), _stream()), "aurppo_cartpole_rollout_f32")
+    return next_obs, next_done

@@ -25,7 +25,7 @@ from torch import nn
 
 from . import dist as D
 from .actor_critic import actor_critic
-from .envs import make_vec_env
+from .envs import CartPoleDeviceVecEnv, episode_triples, make_vec_env
 from .flat import FlatAdamMixin, FlatBucket
 from .scalars import make_writer
 
@@ -330,7 +330,7 @@ class ppo(FlatAdamMixin):
                          else torch.rand(self.num_envs, device=self.device))
             action, _, _ = self._act(lay, next_obs.to(self.device).contiguous(), noise,
                                      self.buffer.actions[step], self.buffer.log_probs[step], self.buffer.values[step])
-            if not cont:
+            if not cont and not getattr(self.envs, "takes_float_actions", False):
                 action = action.long()
         else:
             with torch.no_grad():
@@ -368,6 +368,8 @@ class ppo(FlatAdamMixin):
                 # the parameters stand still for the T steps: one set of operand-order copies per rollout (inside a captured
                 # rollout too, so a replay prepares from the updated parameters)
                 self._act_wop = self.ops.mlp_layered_prepare(self.bucket.flat_param, lay)
+        if hasattr(self.envs, "begin_rollout"):
+            self.envs.begin_rollout(self.num_steps)     # the device CartPole: step t fills row t of its episode table
         for step in range(0, self.num_steps):
             global_step += 1 * self.num_envs * self.world
             self.buffer.states[step] = next_obs
@@ -377,10 +379,44 @@ class ppo(FlatAdamMixin):
         self._act_wop = None            # ... and prepares for itself: nothing can go stale
         return next_obs, next_done, global_step
 
+    def _one_launch_rollout(self):
+        """Is the rollout one K16 launch?  The device CartPole, K8's shape (``ops.cartpole_rollout_ok``), and AURPPO_ROLLOUT_KERNEL
+        not 0 (0 keeps the device env on the per-step route, for A/B runs).  Every process runs its own shard's launch: nothing in it
+        crosses a rank."""
+        return (isinstance(self.envs, CartPoleDeviceVecEnv) and self.device.type == "cuda" and hasattr(self.ops, "cartpole_rollout")
+                and self.ops.cartpole_rollout_ok(self._mlp) and os.environ.get("AURPPO_ROLLOUT_KERNEL", "1") != "0")
+
     def _rollout(self, next_obs, next_done, global_step, writer):
-        """One rollout.  With a device-resident env whose step() is a fixed sequence of device ops (``capturable``), the MLP
-        policy (K8) and one process, the T steps -- ~10 launches each, host-bound -- are captured once as a hipGraph and
-        replayed: rollout 1 runs eagerly, rollout 2 is captured, later ones replay."""
+        """One rollout.  On the device CartPole the finished episodes are read from the env's table behind it (one host read), on
+        whichever route the steps ran."""
+        env = self.envs
+        if not isinstance(env, CartPoleDeviceVecEnv):
+            return self._rollout_captured(next_obs, next_done, global_step, writer)
+        first_step = global_step
+        if self._one_launch_rollout():
+            # K16: the noise of all T steps in one generator call (as _rollout_steps draws it), then one launch that writes the six
+            # buffer tensors and the episode table and updates next_obs / next_done in place
+            b, T = self.buffer, self.num_steps
+            noise = torch.rand((T, self.num_envs), device=self.device)
+            table = env.begin_rollout(T, clear=False)      # every row is written
+            self.ops.cartpole_rollout(env.native_state(), self.bucket.flat_param, self._mlp, noise, b.states, b.terminals, b.actions,
+                                      b.log_probs, b.values, b.rewards, table, next_obs, next_done)
+            global_step += T * self.num_envs * self.world
+        else:
+            next_obs, next_done, global_step = self._rollout_captured(next_obs, next_done, global_step, writer)
+        for ret, length, at in episode_triples(env.ep_len, first_step, self.num_envs * self.world):
+            if writer is not None:
+                writer.add_scalar("charts/episodic_return", ret, at)
+                writer.add_scalar("charts/episodic_length", length, at)
+            self.total_returns.append(ret)
+            self.total_episode_lengths.append(length)
+            self.x_indices.append(at)
+        return next_obs, next_done, global_step
+
+    def _rollout_captured(self, next_obs, next_done, global_step, writer):
+        """One rollout through ``_rollout_steps``.  With a device-resident env whose step() is a fixed sequence of device ops
+        (``capturable``), the MLP policy (K8) and one process, the T steps -- ~10 launches each, host-bound -- are captured once
+        as a hipGraph and replayed: rollout 1 runs eagerly, rollout 2 is captured, later ones replay."""
         env = self.envs
         ok = (self.use_graph and self.world == 1 and self._act_layout() is not None
               and getattr(env, "device_native", False) and getattr(env, "capturable", False) and self.device.type == "cuda")

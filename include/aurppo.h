@@ -585,7 +585,42 @@ int aurppo_mlp_act_f32(const float* obs, const float* noise, int N, int D, int A
                        const float* params, const int* layout_h, int n_params, float* actions, float* logp,
                        float* value, void* stream);
 
-/* ---- K7w / K8w: the same two operators for the other MLP shapes of the reference's CLI --------------------------------
+/* ---- K15 / K16: CartPole-v1 on the device, and a whole rollout on it in one launch ------------------------------------
+ * The env the reference CLI defaults to (src/run_ppo.py --gym_id CartPole-v1), stepped by gym's SyncVectorEnv on the host
+ * every rollout step (src/ppo.py:66-68,110).  Env state, caller-owned device memory for N envs: state (N,4) fp64 (gym keeps
+ * fp64 and hands out fp32 observations), steps (N,) and episode (N,) int32.  A reset draw is Philox4x32-10 on the counter
+ * (env0 + n, episode, 0, 0) under the key (seed_lo, seed_hi); component j = -0.05 + 0.1 * ((word_j >> 8) * 2^-24).  The
+ * dynamics' constants (gravity .. x_lim, max_steps) arrive as arguments: CartPoleVecEnv's class attributes (envs.py).
+ *
+ * aurppo_cartpole_reset replaces `envs.reset(seed=...)` (src/ppo.py:188): episode = 0, steps = 0, the state from the draw,
+ *   obs (N,4) = (float)state.
+ * aurppo_cartpole_step (K15) replaces `envs.step(action.cpu().numpy())` (src/ppo.py:110) with gym's auto-reset and
+ *   RecordEpisodeStatistics (src/ppo.py:88): action (N,) fp32 0.0 / 1.0 as K8 writes it; the Euler step in fp64; steps += 1;
+ *   done = |x| > x_lim or |theta| > theta_lim or steps >= max_steps.  Where done: ep_len[n] = steps (else 0; CartPole's
+ *   return equals its length), episode += 1, the state from the next draw, steps = 0.  Writes obs (the reset observation
+ *   where done), reward = 1, done as 0.0 / 1.0.
+ * aurppo_cartpole_rollout_f32 (K16) replaces the T steps of src/ppo.py:201-205 for K8's shape alone (hidden == 64,
+ *   num_layers == 2, D == 4, A == 2, continuous == 0; anything else: AURPPO_ESHAPE): per step t the rows states[t] /
+ *   terminals[t] from the current observation / done flag, aurppo_mlp_act_f32 on noise[t] into actions[t] / logp[t] /
+ *   values[t], K15 into rewards[t] / ep_len[t].  obs_io (N,4) / done_io (N,): in, the current observation and done flag (what
+ *   the last reset / step left); out, those after step T - 1.  The env state is updated in place.  noise (T,N) uniform
+ *   [0,1); states (T,N,4); every other row table (T,N).  Bit for bit what T x (aurppo_mlp_act_f32, aurppo_cartpole_step)
+ *   leave.  params / layout_h / n_params as aurppo_mlp_act_f32 (the twelve weight / bias offsets).                        */
+int aurppo_cartpole_reset(double* state, int32_t* steps, int32_t* episode, float* obs, int N, int env0, uint32_t seed_lo,
+                          uint32_t seed_hi, void* stream);
+int aurppo_cartpole_step(double* state, int32_t* steps, int32_t* episode, const float* action, float* obs, float* reward,
+                         float* done, int32_t* ep_len, int N, int env0, uint32_t seed_lo, uint32_t seed_hi, double gravity,
+                         double masscart, double masspole, double length, double force_mag, double tau, double theta_lim,
+                         double x_lim, int max_steps, void* stream);
+int aurppo_cartpole_rollout_f32(double* state, int32_t* steps, int32_t* episode, float* obs_io, float* done_io,
+                                const float* noise, int N, int T, int D, int A, int continuous, int hidden, int num_layers,
+                                const float* params, const int* layout_h, int n_params, float* states, float* terminals,
+                                float* actions, float* logp, float* values, float* rewards, int32_t* ep_len, int env0,
+                                uint32_t seed_lo, uint32_t seed_hi, double gravity, double masscart, double masspole,
+                                double length, double force_mag, double tau, double theta_lim, double x_lim, int max_steps,
+                                void* stream);
+
+/* ---- K7w / K8w:the same two operators for the other MLP shapes of the reference's CLI --------------------------------
  * src/run_ppo.py:33,37 expose -d/--hidden_dim and -nl/--num_layers and src/nets/nets.py:19-53 builds any of them:
  * `num_layers` (1..3) Tanh layers of `hidden` (1..128) units over a state of D (1..128) floats, A <= 16.  Same
  * arguments and results as aurppo_mlp_ppo_step_ev_f32 / aurppo_mlp_act_f32 except
