@@ -5,15 +5,18 @@
 //                                  auto-reset and the finished episode's length.
 //   * k_cartpole_rollout (K16)  -- the T steps of src/ppo.py:201-205 for K8's shape (2 x 64, Categorical, A = 2, D = 4): one workgroup
 //                                  per 32-env tile stages both nets' weights and its envs ONCE and loops over the steps -- the two
-//                                  state / terminal row stores, K8's three layers and sampler (the helpers k_mlp_act runs, in its
-//                                  order), K15's step on the 32 lanes that sampled, the four row stores behind it.  Tiles share
-//                                  nothing: no inter-workgroup traffic, only __syncthreads() between phases.  An MFMA row depends on
-//                                  its own operand row alone, so every value is, bit for bit, what T x (K8, K15) leave.
+//                                  state / terminal row stores, K8's three layers and sampler, K15's step on the 32 lanes that
+//                                  sampled, the four row stores behind it.  The LDS plan, the weight staging and the three layers
+//                                  are mlp_act.h's (ActLds, act_stage_weights, act_forward): K8's passages as functions (k_mlp_act
+//                                  takes the plan and keeps the other two inline: the note above it, mlp.hip); the sampler is
+//                                  ppo_math.h's, shared with K8.  Tiles share nothing: no inter-workgroup traffic, only
+//                                  __syncthreads() between phases.  An MFMA row depends on its own operand row alone, so every value
+//                                  is, bit for bit, what T x (K8, K15) leave.
 // The state is fp64 (as gym and the host class keep it; observations are its fp32 rounding).  A reset is a function of (seed, global
 // env index, episode number) alone -- Philox4x32-10 on the counter (env0 + n, episode, 0, 0) under the key (seed lo, seed hi) -- so it
 // does not depend on how a rollout is cut into launches.  The dynamics and the draw are one __device__ function each, shared by
 // K15 and K16.
-#include "mlp_common.h"
+#include "mlp_act.h"
 
 using namespace aurppo_mlp;
 
@@ -150,22 +153,15 @@ struct RolloutArgs {
     CartConst c;
 };
 
-// K8's LDS layout (k_mlp_act, mlp.hip) without the Gaussian head's log-std rows
+// K8's LDS plan without the Gaussian head's log-std rows, its weight staging and its three layers: mlp_act.h (ActLds,
+// act_stage_weights, act_forward).  Here: the zero fill of sX and the step's row writes from registers, the Categorical sampler's call,
+// the env lanes.
 __global__ __launch_bounds__(256, 1) void k_cartpole_rollout(const RolloutArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* sX = lds;                    // [R][LD]
-    float* sH1 = sX + R * LD;           // [2][R][LD]
-    float* sH2 = sH1 + 2 * R * LD;      // [2][R][LD]
-    float* sW1 = sH2 + 2 * R * LD;      // [2][H][LD]
-    float* sW2 = sW1 + 2 * H * LD;      // [2][H][LD]
-    float* sW3 = sW2 + 2 * H * LD;      // [2][AP][LD]
-    float* sOut = sW3 + 2 * AP * LD;    // [2][R][LDO]
-    float* sB1 = sOut + 2 * R * LDO;    // [2][H]
-    float* sB2 = sB1 + 2 * H;
-    float* sB3 = sB2 + 2 * H;           // [2][AP]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int net = wave >> 1, cb = wave & 1;
-    const int out_dim[2] = {kA, 1};
+    const ActLds s(lds);
+    float* const sX = s.sX;
+    const float* const sOut = s.sOut;
+    const int tid = threadIdx.x;
     const int row0 = blockIdx.x * R;
     // ---- once per launch: the weights (as k_mlp_act stages them), a zero sX, this lane's env
 #pragma unroll
@@ -174,26 +170,7 @@ __global__ __launch_bounds__(256, 1) void k_cartpole_rollout(const RolloutArgs a
         sX[(e >> 6) * LD + (e & 63)] = 0.0f;     // columns kD .. stay zero for the whole launch, and so do a ragged tile's dead rows
     }
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-#pragma unroll
-        for (int u = 0; u < H * H / kThreads; ++u) {
-            const int e = tid + u * kThreads, o = e >> 6, c = e & 63;
-            const float w1v = a.params[a.L.w1[n] + o * kD + (c < kD ? c : kD - 1)];
-            const float w2v = a.params[a.L.w2[n] + e];
-            sW1[(n * H + o) * LD + c] = c < kD ? w1v : 0.0f;
-            sW2[(n * H + o) * LD + c] = w2v;
-        }
-#pragma unroll
-        for (int u = 0; u < AP * H / kThreads; ++u) {
-            const int e = tid + u * kThreads, o = e >> 6, i = e & 63;
-            sW3[(n * AP + o) * LD + i] = o < out_dim[n] ? a.params[a.L.w3[n] + o * H + i] : 0.0f;
-        }
-        if (tid < H) {
-            sB1[n * H + tid] = a.params[a.L.b1[n] + tid];
-            sB2[n * H + tid] = a.params[a.L.b2[n] + tid];
-        }
-        if (tid < AP) sB3[n * AP + tid] = tid < out_dim[n] ? a.params[a.L.b3[n] + tid] : 0.0f;
-    }
+    for (int n = 0; n < 2; ++n) act_stage_weights(s, a.params, a.L, kD, kA, n);
     // the 32 lanes that sample own one env each for the T steps: its state, observation and done flag live in their registers
     const int n = row0 + tid;
     const bool live = tid < R && n < a.N;
@@ -219,38 +196,7 @@ __global__ __launch_bounds__(256, 1) void k_cartpole_rollout(const RolloutArgs a
             a.terminals[tn] = dn;
         }
         __syncthreads();
-        {
-            f32x16 acc = zero16();
-            const float* W = sW1 + (net * H + cb * 32) * LD;
-            mma32<H>(acc, [&](int i, int k) { return sX[i * LD + k]; }, [&](int k, int j) { return W[j * LD + k]; });
-            const int col = cb * 32 + (lane & 31);
-            const float bias = sB1[net * H + col];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sH1[(net * R + acc_row(e, lane)) * LD + col] = tanh_fast(acc[e] + bias);
-        }
-        __syncthreads();
-        {
-            f32x16 acc = zero16();
-            const float* W = sW2 + (net * H + cb * 32) * LD;
-            const float* Hin = sH1 + net * R * LD;
-            mma32<H>(acc, [&](int i, int k) { return Hin[i * LD + k]; }, [&](int k, int j) { return W[j * LD + k]; });
-            const int col = cb * 32 + (lane & 31);
-            const float bias = sB2[net * H + col];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sH2[(net * R + acc_row(e, lane)) * LD + col] = tanh_fast(acc[e] + bias);
-        }
-        __syncthreads();
-        {
-            const float* W = sW3 + net * AP * LD;
-            const float* Hin = sH2 + (net * R + cb * 16) * LD;
-            const f32x4 acc = mma16<H>([&](int i, int k) { return Hin[i * LD + k]; },
-                                       [&](int k, int j) { return W[j * LD + k]; });
-            const int col = lane & 15;
-            const float bias = sB3[net * AP + col];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sOut[(net * R + cb * 16 + 4 * (lane >> 4) + e) * LDO + col] = acc[e] + bias;
-        }
-        __syncthreads();
+        act_forward(s);
         // (the next step's sX / sOut writes are behind its own barriers: nothing here races with them)
         if (live) {
             const float* mu = sOut + tid * LDO;
@@ -275,10 +221,6 @@ __global__ __launch_bounds__(256, 1) void k_cartpole_rollout(const RolloutArgs a
         for (int j = 0; j < kD; ++j) a.obs_io[(size_t)n * kD + j] = ob[j];
         a.done_io[n] = dn;
     }
-}
-
-constexpr size_t rollout_lds_bytes() {
-    return sizeof(float) * (size_t)(R * LD + 2 * 2 * R * LD + 2 * 2 * H * LD + 2 * AP * LD + 2 * R * LDO + 4 * H + 2 * AP);
 }
 
 int fill_const(CartConst& c, const char* who, int N, int env0, uint32_t seed_lo, uint32_t seed_hi, double gravity, double masscart,
@@ -336,21 +278,13 @@ extern "C" int aurppo_cartpole_rollout_f32(double* state, int32_t* steps, int32_
     AURPPO_REQUIRE(D == kD && A == kA && !continuous, AURPPO_ESHAPE,
                    "%s: state_dim=%d action_dim=%d continuous=%d (CartPole: %d floats, a Categorical head of %d)", who, D, A, continuous, kD, kA);
     RolloutArgs a;
-    // the twelve offsets, checked as aurppo_mlp_act_f32 checks them (mlp.hip: fill_layout); a Categorical head reads no log-std
-    for (int n = 0; n < 2; ++n) {
-        a.L.w1[n] = layout_h[6 * n + 0]; a.L.b1[n] = layout_h[6 * n + 1]; a.L.w2[n] = layout_h[6 * n + 2];
-        a.L.b2[n] = layout_h[6 * n + 3]; a.L.w3[n] = layout_h[6 * n + 4]; a.L.b3[n] = layout_h[6 * n + 5];
-    }
-    a.L.logstd = 0;
-    a.L.n_params = n_params;
-    for (int k = 0; k < 12; ++k)
-        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "%s: layout[%d]=%d", who, k, layout_h[k]);
+    if (const int rc = fill_layout(a.L, layout_h, 0, n_params, who)) return rc;     // a Categorical head reads no log-std
     if (const int rc = fill_const(a.c, who, N, env0, seed_lo, seed_hi, gravity, masscart, masspole, length, force_mag, tau, theta_lim, x_lim,
                                   max_steps))
         return rc;
     a.state = state; a.steps = steps; a.episode = episode; a.obs_io = obs_io; a.done_io = done_io; a.noise = noise; a.params = params;
     a.states = states; a.terminals = terminals; a.actions = actions; a.logp = logp; a.values = values; a.rewards = rewards; a.ep_len = ep_len;
     a.N = N; a.T = T;
-    return launch_dyn_lds<k_cartpole_rollout>("k_cartpole_rollout", (N + R - 1) / R, kThreads, rollout_lds_bytes(), rollout_lds_bytes(),
+    return launch_dyn_lds<k_cartpole_rollout>("k_cartpole_rollout", (N + R - 1) / R, kThreads, ActLds::bytes(false), ActLds::bytes(false),
                                               (hipStream_t)stream, a);
 }

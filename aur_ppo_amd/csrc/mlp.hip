@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "bf16x3.h"
+#include "mlp_act.h"
 #include "mlp_tail.h"
 
 using namespace aurppo_mlp;
@@ -72,18 +73,27 @@ struct ActArgs {
     MlpLayout L;
 };
 
+// K8 takes its LDS plan from mlp_act.h -- every pointer below is ActLds's offset of that member, the launch's byte count is
+// ActLds::bytes(true), so a member cannot be added to one and not the other -- but keeps its own text of the weight staging and the
+// three layers.  On act_stage_weights / act_forward it computed the same bits (tools/build_bitdiff.py: 2250 arrays identical) and
+// ran slower than the parent build in every one of five alternating rounds: 8.67-8.71 us for 8.61-8.65 us (Gaussian head), 9.90-9.92 us
+// for 9.83-9.85 us (Categorical), N = 4096, tools/head_time.py; profiles/refactor_act_forward.txt, section 4.  So a change to the
+// staging or the layers below is a change to mlp_act.h too: tests/test_cartpole_gpu.py (K16 == T x (K8, K15), no tolerance) is what
+// holds the two texts together.
 __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* sX = lds;                    // [R][LD]
-    float* sH1 = sX + R * LD;           // [2][R][LD]
-    float* sH2 = sH1 + 2 * R * LD;      // [2][R][LD]
-    float* sW1 = sH2 + 2 * R * LD;      // [2][H][LD]
-    float* sW2 = sW1 + 2 * H * LD;      // [2][H][LD]
-    float* sW3 = sW2 + 2 * H * LD;      // [2][AP][LD]
-    float* sOut = sW3 + 2 * AP * LD;    // [2][R][LDO]
-    float* sB1 = sOut + 2 * R * LDO;    // [2][H]
-    float* sB2 = sB1 + 2 * H;
-    float* sB3 = sB2 + 2 * H;           // [2][AP]
+    float* sX = lds + ActLds::at(ActLds::kX);
+    float* sH1 = lds + ActLds::at(ActLds::kH1);
+    float* sH2 = lds + ActLds::at(ActLds::kH2);
+    float* sW1 = lds + ActLds::at(ActLds::kW1);
+    float* sW2 = lds + ActLds::at(ActLds::kW2);
+    float* sW3 = lds + ActLds::at(ActLds::kW3);
+    float* sOut = lds + ActLds::at(ActLds::kOut);
+    float* sB1 = lds + ActLds::at(ActLds::kB1);
+    float* sB2 = lds + ActLds::at(ActLds::kB2);
+    float* sB3 = lds + ActLds::at(ActLds::kB3);
+    float* sLs = lds + ActLds::at(ActLds::kLs);
+    float* sSd = lds + ActLds::at(ActLds::kSd);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int net = wave >> 1, cb = wave & 1;
     const int D = a.D, A = a.A;
@@ -92,8 +102,6 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
     // Staging: every element's address comes from shifts of a flat index over rows padded to 64 columns (no division,
     // no zero-fill pass), and all of a thread's loads are independent, so they go out together -- the kernel is a
     // latency chain (launch, staging, three layers, sampling) and this was its longest link.
-    float* sLs = sB3 + 2 * AP;          // [AP] log-std
-    float* sSd = sLs + AP;              // [AP] exp(log-std)
 #pragma unroll
     for (int u = 0; u < R * H / kThreads; ++u) {
         const int e = tid + u * kThreads, r = e >> 6, c = e & 63;
@@ -194,9 +202,6 @@ __global__ __launch_bounds__(256, 1) void k_mlp_act(const ActArgs a) {
     }
 }
 
-constexpr size_t act_lds_bytes() {
-    return sizeof(float) * (size_t)(R * LD + 2 * 2 * R * LD + 2 * 2 * H * LD + 2 * AP * LD + 2 * R * LDO + 4 * H + 2 * AP + 2 * AP);
-}
 }  // namespace
 
 namespace {
@@ -224,18 +229,6 @@ WsView ws_view(void* workspace, int n_params) {
     v.wop3 = c.take<unsigned short>(mlp_step3_wop_bytes(), 64);
     v.bytes = c.bytes;
     return v;
-}
-// layout_h: w1a,b1a,w2a,b2a,w3a,b3a, w1c,b1c,w2c,b2c,w3c,b3c, logstd (read, and checked, only for a Gaussian head)
-int fill_layout(MlpLayout& L, const int* layout_h, int continuous, int n_params, const char* who) {
-    for (int n = 0; n < 2; ++n) {
-        L.w1[n] = layout_h[6 * n + 0]; L.b1[n] = layout_h[6 * n + 1]; L.w2[n] = layout_h[6 * n + 2];
-        L.b2[n] = layout_h[6 * n + 3]; L.w3[n] = layout_h[6 * n + 4]; L.b3[n] = layout_h[6 * n + 5];
-    }
-    L.logstd = continuous ? layout_h[12] : 0;
-    L.n_params = n_params;
-    for (int k = 0; k < (continuous ? 13 : 12); ++k)
-        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "%s: layout[%d]=%d", who, k, layout_h[k]);
-    return AURPPO_OK;
 }
 }  // namespace
 
@@ -454,5 +447,5 @@ extern "C" int aurppo_mlp_act_f32(const float* obs, const float* noise, int N, i
     a.obs = obs; a.noise = noise; a.params = params; a.actions = actions; a.logp = logp; a.value = value;
     a.N = N; a.D = D; a.A = A; a.continuous = continuous ? 1 : 0;
     if (const int rc = fill_layout(a.L, layout_h, continuous, n_params, "aurppo_mlp_act_f32")) return rc;
-    return launch_dyn_lds<k_mlp_act>("k_mlp_act", (N + R - 1) / R, kThreads, act_lds_bytes(), act_lds_bytes(), (hipStream_t)stream, a);
+    return launch_dyn_lds<k_mlp_act>("k_mlp_act", (N + R - 1) / R, kThreads, ActLds::bytes(true), ActLds::bytes(true), (hipStream_t)stream, a);
 }

@@ -218,6 +218,19 @@ int check_step_args(const char* who, bool pointers, const float* actions, int co
     AURPPO_REQUIRE(vloss_mode >= 0 && vloss_mode <= 2, AURPPO_EINVAL, "%s: bad vloss_mode %d", who, vloss_mode);
     return AURPPO_OK;
 }
+// The parameter offsets every MLP entry of the 2 x 64 policy is given (K7, K8, the optimizer launch, K16), read and range-checked.
+// layout_h: w1a,b1a,w2a,b2a,w3a,b3a, w1c,b1c,w2c,b2c,w3c,b3c, logstd (read, and checked, only for a Gaussian head)
+inline int fill_layout(MlpLayout& L, const int* layout_h, int continuous, int n_params, const char* who) {
+    for (int n = 0; n < 2; ++n) {
+        L.w1[n] = layout_h[6 * n + 0]; L.b1[n] = layout_h[6 * n + 1]; L.w2[n] = layout_h[6 * n + 2];
+        L.b2[n] = layout_h[6 * n + 3]; L.w3[n] = layout_h[6 * n + 4]; L.b3[n] = layout_h[6 * n + 5];
+    }
+    L.logstd = continuous ? layout_h[12] : 0;
+    L.n_params = n_params;
+    for (int k = 0; k < (continuous ? 13 : 12); ++k)
+        AURPPO_REQUIRE(layout_h[k] >= 0 && layout_h[k] < n_params, AURPPO_ESHAPE, "%s: layout[%d]=%d", who, k, layout_h[k]);
+    return AURPPO_OK;
+}
 // CUs the step kernels leave to the side stream's shuffle kernels: AURPPO_MLP_SPARE_CUS, default 8 (one per XCD)
 inline int spare_cus() {
     const int k = aurppo_knobs().k7_spare_cus;

@@ -1,5 +1,5 @@
 """Do two builds of the library compute the same BITS in the fused MLP kernels (K7, K7w, K8, K8w, their reduce / optimizer launches),
-the head kernels (K13, K14) and the layered rollout step?
+the head kernels (K13, K14), the layered rollout step and the device CartPole (K15, K16)?
     AURPPO_LIB=<build> python tools/build_bitdiff.py run OUT.npz     (once per build, each in a process of its own)
     python tools/build_bitdiff.py cmp A.npz B.npz                    (raw bytes of every array; exit 1 + the first that differs)
 `run` drives every build of the step (K7 ids 3, 2; K7w ids 1, 3, 2) with AURPPO_STATIC_TILES=1 (a fixed summation order; the
@@ -11,7 +11,11 @@ workspace is zero-filled before each sequence, so that bytes no kernel writes ar
 The head kernels run at every threads-per-row build (H = 32, 96, 256, 512, 1024: 8, 32, 64, 128, 256), Gaussian heads of 1 and 16
 actions, Categorical heads of 2 and 16, M = N = 1, 65, 4099: head_ppo with records beside actions and packed (where the action row
 fits a packed record) -- gz of both nets, gradient, scalars, workspace (K13's grid depends on (M, H) only, so its slabs repeat) --
-head_act with noise and for the value alone, and mlp_layered_prepare + mlp_layered_act on layered policies of those widths."""
+head_act with noise and for the value alone, and mlp_layered_prepare + mlp_layered_act on layered policies of those widths.
+The CartPole section builds the default Categorical 2 x 64 policy over D = 4, A = 2 (the actor's last layer scaled so that both actions
+occur), resets a device CartPole under a fixed seed (every third env 5 steps short of truncation, every third entering as done) and runs
+cartpole_rollout at (N, T) = (1, 1), (33, 5), (70, 40): the six buffer tensors (poisoned first), the episode table, next_obs, next_done
+and the env's state, step counts and episode numbers behind K16; then one cartpole_step (K15) from there."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -26,6 +30,8 @@ MS, B = (1, 65, 1071, 70001), 71000
 HEAD_HS, HEAD_KINDS, HEAD_NS, HEAD_B = (32, 96, 256, 512, 1024), ((1, True), (16, True), (2, False), (16, False)), (1, 65, 4099), 4200
 # (layers, hidden, D): widths no fused kernel takes, or (32, 96) a state no fused kernel takes
 LAYERED_SHAPES = [(2, 32, 144), (1, 96, 144), (2, 256, 16), (1, 512, 16), (1, 1024, 16)]
+# K16's (N, T): one env and one step; two tiles, the second ragged; three tiles over 40 steps (tests/test_cartpole_gpu.py's shapes)
+CART_SHAPES, CART_SEED = [(1, 1), (33, 5), (70, 40)], 21
 
 
 def head_layout(H, pol, bucket, Hd, A, cont):
@@ -137,6 +143,31 @@ def run(out_path):
             keep(key + "act/", actions=a_, logp=lp_, value=v_)
             keep(key + "act/value_only/", value=H.mlp_layered_act(obs, None, bucket.flat_param, lay, wop=wop)[2])
 
+    def cartpole_case(N, T):
+        from aur_ppo_amd.envs import CartPoleDeviceVecEnv
+        pol, bucket = policy(4, 2, False, 64, 2)
+        with torch.no_grad():
+            pol.actor.net[4].weight.mul_(40.0)          # logits that move with the state, so both actions occur
+        lay = H.mlp_layout(pol, bucket)
+        assert H.cartpole_rollout_ok(lay), lay
+        env = CartPoleDeviceVecEnv(N, dev, seed=CART_SEED)
+        state0, _, _ = env.get_state()
+        obs = env.set_state(state0, np.where(np.arange(N) % 3 == 1, 495, 0)).contiguous()    # every third env truncates inside T >= 5
+        done = (torch.arange(N) % 3 == 0).float().to(dev)
+        noise = torch.rand(T, N).to(dev)
+        z = lambda *s, dt=torch.float32: torch.full(s, -7, dtype=dt, device=dev)
+        buf = dict(states=z(T, N, 4), terminals=z(T, N), actions=z(T, N), log_probs=z(T, N), values=z(T, N), rewards=z(T, N))
+        table = env.begin_rollout(T)
+        H.cartpole_rollout(env.native_state(), bucket.flat_param, lay, noise, buf["states"], buf["terminals"], buf["actions"], buf["log_probs"],
+                           buf["values"], buf["rewards"], table, obs, done)
+        key = f"cartpole/N{N}-T{T}/"
+        keep(key + "rollout/", ep_len=table, next_obs=obs, next_done=done, env_state=env.state, env_steps=env.steps, env_episode=env.episode, **buf)
+        row = env.begin_rollout(1)                              # K15 alone, from where K16 left the envs
+        o2, r2, d2, _, _ = env.step(buf["actions"][T - 1])
+        keep(key + "step/", obs=o2, reward=r2, done=d2, ep_len=row, env_state=env.state, env_steps=env.steps, env_episode=env.episode)
+
+    for N, T in CART_SHAPES:
+        cartpole_case(N, T)
     for Hd in HEAD_HS:
         for A, cont in HEAD_KINDS:
             head_case(Hd, A, cont)
