@@ -40,6 +40,7 @@ SYMBOLS = (
     "aurppo_mlp_layered_wa_step_workspace_bytes", "aurppo_mlp_layered_wa_step_f32", "aurppo_mlp_layered_wa_minibatch_f32",
     "aurppo_mlp_layered_wa_act_f32", "aurppo_mlp_layered_wa_act_paired_f32",
     "aurppo_cartpole_reset", "aurppo_cartpole_step", "aurppo_cartpole_rollout_f32",
+    "aurppo_pendulum_reset", "aurppo_pendulum_step", "aurppo_pendulum_rollout_f32",
 )
 
 _lib = None
@@ -187,6 +188,12 @@ def _declare(lib):
     lib.aurppo_cartpole_reset.argtypes = cart_env + [vp, i32] + cart_seed + [vp]
     lib.aurppo_cartpole_step.argtypes = cart_env + [vp] * 5 + [i32] + cart_seed + cart_consts + [vp]
     lib.aurppo_cartpole_rollout_f32.argtypes = (cart_env + [vp] * 3 + [i32] * 7 + [vp, pi32, i32] + [vp] * 7 + cart_seed + cart_consts
+                                                + [vp])
+    # K17, K18: the device Pendulum and the one-launch rollout on it
+    pend_consts = [f64] * 6 + [i32]                         # g, m, l, dt, max_speed, max_torque, max_steps
+    lib.aurppo_pendulum_reset.argtypes = cart_env + [vp, i32] + cart_seed + [vp]
+    lib.aurppo_pendulum_step.argtypes = cart_env + [vp] * 6 + [i32] + cart_seed + pend_consts + [vp]
+    lib.aurppo_pendulum_rollout_f32.argtypes = (cart_env + [vp] * 3 + [i32] * 7 + [vp, pi32, i32] + [vp] * 8 + cart_seed + pend_consts
                                                 + [vp])
     # K6, K6b
     lib.aurppo_clip_workspace_bytes.argtypes = [i64]

@@ -17,6 +17,7 @@
 // does not depend on how a rollout is cut into launches.  The dynamics and the draw are one __device__ function each, shared by
 // K15 and K16.
 #include "mlp_act.h"
+#include "philox.h"
 
 using namespace aurppo_mlp;
 
@@ -36,23 +37,6 @@ struct CartEnv {
     double s[4];
     int steps, episode;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds of (c0, c1, c2, c3) -> (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),
-// the key bumped by the Weyl constants between rounds.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // The reset state of global env `genv`, episode `episode`: component j = -0.05 + 0.1 * u_j, u_j the top 24 bits of word j in [0, 1)
 __device__ __forceinline__ void cart_reset_draw(double s[4], int genv, int episode, const CartConst& c) {

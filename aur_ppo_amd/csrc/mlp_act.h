@@ -74,6 +74,17 @@ __device__ __forceinline__ void act_stage_weights(const ActLds& s, const float* 
     if (tid < AP) s.sB3[n * AP + tid] = tid < out_dim ? params[L.b3[n] + tid] : 0.0f;
 }
 
+// The Gaussian head's log-std rows, as K8 fills them: sLs = log-std (0 beyond A, and for a Categorical head), sSd = exp(sLs).  For
+// kernels that asked for bytes(true).
+__device__ __forceinline__ void act_stage_logstd(const ActLds& s, const float* params, const MlpLayout& L, int A, bool continuous) {
+    const int tid = threadIdx.x;
+    if (tid < AP) {
+        const float ls = (continuous && tid < A) ? params[L.logstd + tid] : 0.0f;
+        s.sLs[tid] = ls;
+        s.sSd[tid] = expf(ls);
+    }
+}
+
 // The three layers of this wave's (net, column block) on the tile in sX, a barrier behind each: sH1 = tanh(sX W1' + b1), sH2 =
 // tanh(sH1 W2' + b2), sOut = sH2 W3' + b3 (rows 0 .. R of sOut the actor's head, R .. 2R the critic's).  The barrier in FRONT of
 // layer 1 -- behind whatever filled sX -- is the caller's.

@@ -1574,17 +1574,17 @@ def _cart_tensor(who, name, t, shape, dtype=torch.float32):
                          f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
 
 
-def _cart_env(who, env_state):
-    """N after the env-state checks."""
+def _cart_env(who, env_state, doubles=4, n_consts=9, consts_of="nine CartPole"):
+    """N after the env-state checks (the device Pendulum's calls pass their own block width and constant count)."""
     steps = env_state["steps"]
     N = steps.numel() if isinstance(steps, torch.Tensor) else 0
     if N < 1:
         raise ValueError(f"{who}: no envs")
-    _cart_tensor(who, "state", env_state["state"], (N, 4), torch.float64)
+    _cart_tensor(who, "state", env_state["state"], (N, doubles), torch.float64)
     _cart_tensor(who, "steps", steps, (N,), torch.int32)
     _cart_tensor(who, "episode", env_state["episode"], (N,), torch.int32)
-    if len(env_state["consts"]) != 9 or int(env_state["env0"]) < 0:
-        raise ValueError(f"{who}: consts must be the nine CartPole constants and env0 >= 0")
+    if len(env_state["consts"]) != n_consts or int(env_state["env0"]) < 0:
+        raise ValueError(f"{who}: consts must be the {consts_of} constants and env0 >= 0")
     return N
 
 
@@ -1663,4 +1663,87 @@ def cartpole_rollout(env_state, flat_param, layout, noise, states, terminals, ac
                                            lay, layout["n_params"], _ptr(states), _ptr(terminals), _ptr(actions), _ptr(log_probs),
                                            _ptr(values), _ptr(rewards), _ptr(ep_len, torch.int32), *_cart_seed(env_state),
                                            *_cart_consts(env_state), _stream()), "aurppo_cartpole_rollout_f32")
+    return next_obs, next_done
+
+
+# ------------------------------------------------------------------ K17 / K18: the device Pendulum and the one-launch rollout on it
+# ``env_state``: what ``envs.PendulumDeviceVecEnv.native_state()`` returns -- ``state`` (N, 16) float64 (the row layout: include/aurppo.h),
+# ``steps`` / ``episode`` (N,) int32, ``seed``, ``env0`` and ``consts`` (g, m, l, dt, max_speed, max_torque, max_steps).  Shapes and
+# dtypes are checked (ValueError) before the library is reached, by the CartPole calls' helpers.
+PENDULUM_STATE_DOUBLES = 16
+
+
+def _pend_env(who, env_state):
+    """N after the env-state checks."""
+    return _cart_env(who, env_state, PENDULUM_STATE_DOUBLES, 7, "seven Pendulum")
+
+
+def _pend_consts(env_state):
+    """g, m, l, dt, max_speed, max_torque, max_steps."""
+    c = env_state["consts"]
+    return (*[float(v) for v in c[:6]], int(c[6]))
+
+
+def pendulum_reset(env_state, obs):
+    """Every env starts over: ``episode = steps = 0``, the state from the reset draw, fresh statistics that have taken the first raw
+    observation; ``obs`` (N, 3) = its normalised form."""
+    N = _pend_env("pendulum_reset", env_state)
+    _cart_tensor("pendulum_reset", "obs", obs, (N, 3))
+    lib = _lib_or_raise()
+    _check(lib.aurppo_pendulum_reset(*_cart_env_ptrs(env_state), _ptr(obs), N, *_cart_seed(env_state), _stream()), "aurppo_pendulum_reset")
+    return obs
+
+
+def pendulum_step(env_state, action, obs, reward, done, ep_len, ep_ret):
+    """K17: one step of every env.  ``action`` (N,) or (N, 1) fp32, the unclipped sample as K8 writes it; writes the normalised ``obs``
+    (N, 3) (the reset observation where the episode ended) and ``reward``, ``done`` 0.0 / 1.0, and the finished episode's length
+    ``ep_len`` (N,) int32 and raw return ``ep_ret`` (N,) fp32, or 0."""
+    who = "pendulum_step"
+    N = _pend_env(who, env_state)
+    _cart_tensor(who, "action", action, (N, 1) if isinstance(action, torch.Tensor) and action.dim() == 2 else (N,))
+    _cart_tensor(who, "obs", obs, (N, 3))
+    _cart_tensor(who, "reward", reward, (N,))
+    _cart_tensor(who, "done", done, (N,))
+    _cart_tensor(who, "ep_len", ep_len, (N,), torch.int32)
+    _cart_tensor(who, "ep_ret", ep_ret, (N,))
+    lib = _lib_or_raise()
+    _check(lib.aurppo_pendulum_step(*_cart_env_ptrs(env_state), _ptr(action), _ptr(obs), _ptr(reward), _ptr(done), _ptr(ep_len, torch.int32),
+                                    _ptr(ep_ret), N, *_cart_seed(env_state), *_pend_consts(env_state), _stream()), "aurppo_pendulum_step")
+    return obs, reward, done, ep_len, ep_ret
+
+
+def pendulum_rollout_ok(layout):
+    """K18's shape rule: K8's default layout (two layers of 64) with a Gaussian head of 1 over Pendulum's 3 floats."""
+    return bool(layout is not None and not layout.get("wide") and not layout.get("layered") and layout["continuous"]
+                and layout["D"] == 3 and layout["A"] == 1 and layout["hidden"] == MLP_HIDDEN and layout["num_layers"] == 2)
+
+
+def pendulum_rollout(env_state, flat_param, layout, noise, states, terminals, actions, log_probs, values, rewards, ep_len, ep_ret, next_obs,
+                     next_done):
+    """K18: T rollout steps in one launch -- per step t what ``mlp_act`` on ``noise[t]`` and ``pendulum_step`` leave, bit for bit, in
+    the buffer rows ``states[t]`` (N, 3), ``terminals[t]``, ``actions[t]`` (N, 1), ``log_probs[t]``, ``values[t]``, ``rewards[t]``,
+    ``ep_len[t]`` (int32) and ``ep_ret[t]``.  ``noise``: (T, N, 1) standard-normal draws.  ``next_obs`` (N, 3) / ``next_done`` (N,) are
+    read and written: on entry the current observation and done flag, on exit those behind the last step.  The env state is updated in
+    place.  A policy shape other than ``pendulum_rollout_ok``'s is refused by the library (RuntimeError)."""
+    who = "pendulum_rollout"
+    N = _pend_env(who, env_state)
+    if not isinstance(noise, torch.Tensor) or noise.dim() != 3 or noise.shape[0] < 1:
+        raise ValueError(f"{who}: noise must be (T, N, 1) standard-normal draws")
+    T = noise.shape[0]
+    _cart_tensor(who, "noise", noise, (T, N, 1))
+    _cart_tensor(who, "states", states, (T, N, 3))
+    _cart_tensor(who, "actions", actions, (T, N, 1))
+    for name, t in (("terminals", terminals), ("log_probs", log_probs), ("values", values), ("rewards", rewards), ("ep_ret", ep_ret)):
+        _cart_tensor(who, name, t, (T, N))
+    _cart_tensor(who, "ep_len", ep_len, (T, N), torch.int32)
+    _cart_tensor(who, "next_obs", next_obs, (N, 3))
+    _cart_tensor(who, "next_done", next_done, (N,))
+    _bucket_fits(layout["n_params"], flat_param, who=who)
+    lib = _lib_or_raise()
+    lay = (C.c_int * len(layout["offsets"]))(*layout["offsets"])
+    _check(lib.aurppo_pendulum_rollout_f32(*_cart_env_ptrs(env_state), _ptr(next_obs), _ptr(next_done), _ptr(noise), N, T, layout["D"],
+                                           layout["A"], int(layout["continuous"]), layout["hidden"], layout["num_layers"], _ptr(flat_param),
+                                           lay, layout["n_params"], _ptr(states), _ptr(terminals), _ptr(actions), _ptr(log_probs),
+                                           _ptr(values), _ptr(rewards), _ptr(ep_len, torch.int32), _ptr(ep_ret), *_cart_seed(env_state),
+                                           *_pend_consts(env_state), _stream()), "aurppo_pendulum_rollout_f32")
     return next_obs, next_done

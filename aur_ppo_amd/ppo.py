@@ -25,7 +25,7 @@ from torch import nn
 
 from . import dist as D
 from .actor_critic import actor_critic
-from .envs import CartPoleDeviceVecEnv, episode_triples, make_vec_env
+from .envs import episode_triples, make_vec_env
 from .flat import FlatAdamMixin, FlatBucket
 from .scalars import make_writer
 
@@ -369,7 +369,7 @@ class ppo(FlatAdamMixin):
                 # rollout too, so a replay prepares from the updated parameters)
                 self._act_wop = self.ops.mlp_layered_prepare(self.bucket.flat_param, lay)
         if hasattr(self.envs, "begin_rollout"):
-            self.envs.begin_rollout(self.num_steps)     # the device CartPole: step t fills row t of its episode table
+            self.envs.begin_rollout(self.num_steps)     # a device env with episode tables: step t fills their row t
         for step in range(0, self.num_steps):
             global_step += 1 * self.num_envs * self.world
             self.buffer.states[step] = next_obs
@@ -380,31 +380,35 @@ class ppo(FlatAdamMixin):
         return next_obs, next_done, global_step
 
     def _one_launch_rollout(self):
-        """Is the rollout one K16 launch?  The device CartPole, K8's shape (``ops.cartpole_rollout_ok``), and AURPPO_ROLLOUT_KERNEL
-        not 0 (0 keeps the device env on the per-step route, for A/B runs).  Every process runs its own shard's launch: nothing in it
-        crosses a rank."""
-        return (isinstance(self.envs, CartPoleDeviceVecEnv) and self.device.type == "cuda" and hasattr(self.ops, "cartpole_rollout")
-                and self.ops.cartpole_rollout_ok(self._mlp) and os.environ.get("AURPPO_ROLLOUT_KERNEL", "1") != "0")
+        """Is the rollout one launch (K16 on the device CartPole, K18 on the device Pendulum)?  An env that names its rollout call
+        (``rollout_op``), a policy of that call's shape (``ops.<rollout_op>_ok``: K8's), and AURPPO_ROLLOUT_KERNEL not 0 (0 keeps the
+        device env on the per-step route, for A/B runs).  Every process runs its own shard's launch: nothing in it crosses a rank."""
+        op = getattr(self.envs, "rollout_op", None)
+        return (op is not None and self.device.type == "cuda" and hasattr(self.ops, op)
+                and getattr(self.ops, op + "_ok")(self._mlp) and os.environ.get("AURPPO_ROLLOUT_KERNEL", "1") != "0")
 
     def _rollout(self, next_obs, next_done, global_step, writer):
-        """One rollout.  On the device CartPole the finished episodes are read from the env's table behind it (one host read), on
-        whichever route the steps ran."""
+        """One rollout.  On a device env with episode tables (CartPole, Pendulum) the finished episodes are read from the env's tables
+        behind it (one host read), on whichever route the steps ran."""
         env = self.envs
-        if not isinstance(env, CartPoleDeviceVecEnv):
+        if getattr(env, "rollout_op", None) is None:
             return self._rollout_captured(next_obs, next_done, global_step, writer)
         first_step = global_step
         if self._one_launch_rollout():
-            # K16: the noise of all T steps in one generator call (as _rollout_steps draws it), then one launch that writes the six
-            # buffer tensors and the episode table and updates next_obs / next_done in place
+            # K16 / K18: the noise of all T steps in one generator call (as _rollout_steps draws it), then one launch that writes the six
+            # buffer tensors and the episode tables and updates next_obs / next_done in place
             b, T = self.buffer, self.num_steps
-            noise = torch.rand((T, self.num_envs), device=self.device)
-            table = env.begin_rollout(T, clear=False)      # every row is written
-            self.ops.cartpole_rollout(env.native_state(), self.bucket.flat_param, self._mlp, noise, b.states, b.terminals, b.actions,
-                                      b.log_probs, b.values, b.rewards, table, next_obs, next_done)
+            noise = (torch.randn((T, self.num_envs, self._mlp["A"]), device=self.device) if self._mlp["continuous"]
+                     else torch.rand((T, self.num_envs), device=self.device))
+            tables = env.begin_rollout(T, clear=False)      # every row is written
+            getattr(self.ops, env.rollout_op)(env.native_state(), self.bucket.flat_param, self._mlp, noise, b.states, b.terminals,
+                                              b.actions, b.log_probs, b.values, b.rewards,
+                                              *(tables if isinstance(tables, tuple) else (tables,)), next_obs, next_done)
             global_step += T * self.num_envs * self.world
         else:
             next_obs, next_done, global_step = self._rollout_captured(next_obs, next_done, global_step, writer)
-        for ret, length, at in episode_triples(env.ep_len, first_step, self.num_envs * self.world):
+        ep_len, ep_ret = env.episode_tables()
+        for ret, length, at in episode_triples(ep_len, first_step, self.num_envs * self.world, ep_ret=ep_ret):
             if writer is not None:
                 writer.add_scalar("charts/episodic_return", ret, at)
                 writer.add_scalar("charts/episodic_length", length, at)

@@ -620,6 +620,43 @@ int aurppo_cartpole_rollout_f32(double* state, int32_t* steps, int32_t* episode,
                                 double length, double force_mag, double tau, double theta_lim, double x_lim, int max_steps,
                                 void* stream);
 
+/* ---- K17 / K18: Pendulum-v1 on the device behind the continuous wrapper chain, and a whole rollout on it in one launch ----
+ * The env of the reference CLI's Gaussian route (src/run_ppo.py --gym_id Pendulum-v1 -c true) behind src/ppo.py:85-99's
+ * wrappers, per env as SyncVectorEnv over wrapped envs has them: RecordEpisodeStatistics, ClipAction, NormalizeObservation,
+ * clip +-10, NormalizeReward (its own gamma 0.99), clip +-10 -- gym 0.26.2's arithmetic in fp64, PendulumVecEnv's formulas
+ * (envs.py) operation for operation.  Env state, caller-owned device memory for N envs: steps (N,) and episode (N,) int32 and
+ * state (N,16) fp64, a row being
+ *   [0] th  [1] thdot  [2..4] observation mean  [5..7] observation var  [8] observation count
+ *   [9] return mean  [10] return var  [11] return count  [12] the reward wrapper's discounted return
+ *   [13] the running episode's raw return  [14..15] spare (a reset writes 0, nothing else touches them).
+ * A reset draw is Philox4x32-10 on the counter (env0 + n, episode, 1, 0) under the key (seed_lo, seed_hi), u_j = (word_j >> 8)
+ * * 2^-24: th = -pi + 2 pi u_0, thdot = -1 + 2 u_1.  The dynamics' constants (g, m, l, dt, max_speed, max_torque, max_steps)
+ * arrive as arguments: PendulumVecEnv's class attributes.
+ *
+ * aurppo_pendulum_reset starts every env over: episode = 0, steps = 0, the state from the draw, both sets of statistics at
+ *   (mean 0, var 1, count 1e-4), both returns 0; the statistics take the first raw observation and obs (N,3) is its normalised form.
+ * aurppo_pendulum_step (K17): action (N,) fp32, the unclipped sample (clipped to +-max_torque inside); the core step; steps += 1;
+ *   done = steps >= max_steps (a truncation; there is no termination).  The observation statistics take the raw fp32 observation
+ *   [cos th, sin th, thdot]; where done: ep_len[n] = steps and ep_ret[n] = the raw return in fp32 (else both 0), episode += 1, the
+ *   state from the next draw, steps = 0, and the statistics take the reset observation too.  Writes obs (N,3) = clip((x - mean) /
+ *   sqrt(var + 1e-8), +-10) of the observation handed out, reward = clip(r / sqrt(return var + 1e-8), +-10), done as 0.0 / 1.0.
+ * aurppo_pendulum_rollout_f32 (K18) is aurppo_cartpole_rollout_f32 for K8's Gaussian build (hidden == 64, num_layers == 2,
+ *   D == 3, A == 1, continuous != 0; anything else: AURPPO_ESHAPE): noise (T,N,1) standard normal; states (T,N,3); actions
+ *   (T,N,1); ep_ret (T,N) fp32 beside ep_len, meaningful where ep_len > 0; every other row table (T,N).  Bit for bit what T x
+ *   (aurppo_mlp_act_f32, aurppo_pendulum_step) leave.  layout_h: the thirteen offsets (actor_logstd last).                    */
+int aurppo_pendulum_reset(double* state, int32_t* steps, int32_t* episode, float* obs, int N, int env0, uint32_t seed_lo,
+                          uint32_t seed_hi, void* stream);
+int aurppo_pendulum_step(double* state, int32_t* steps, int32_t* episode, const float* action, float* obs, float* reward,
+                         float* done, int32_t* ep_len, float* ep_ret, int N, int env0, uint32_t seed_lo, uint32_t seed_hi,
+                         double g, double m, double l, double dt, double max_speed, double max_torque, int max_steps,
+                         void* stream);
+int aurppo_pendulum_rollout_f32(double* state, int32_t* steps, int32_t* episode, float* obs_io, float* done_io,
+                                const float* noise, int N, int T, int D, int A, int continuous, int hidden, int num_layers,
+                                const float* params, const int* layout_h, int n_params, float* states, float* terminals,
+                                float* actions, float* logp, float* values, float* rewards, int32_t* ep_len, float* ep_ret,
+                                int env0, uint32_t seed_lo, uint32_t seed_hi, double g, double m, double l, double dt,
+                                double max_speed, double max_torque, int max_steps, void* stream);
+
 /* ---- K7w / K8w:the same two operators for the other MLP shapes of the reference's CLI --------------------------------
  * src/run_ppo.py:33,37 expose -d/--hidden_dim and -nl/--num_layers and src/nets/nets.py:19-53 builds any of them:
  * `num_layers` (1..3) Tanh layers of `hidden` (1..128) units over a state of D (1..128) floats, A <= 16.  Same
